@@ -18,10 +18,14 @@ beside it as fwd_ms_per_img).  Weak scaling: every rank keeps batch 12.  Rank 0 
 `--workload matterport` runs configs[4] (512x640 bs=4) instead of the KITTI step; the metric name carries the workload.
 
 Output (round 6): the LAST stdout line is a compact record (<= 4 KB: the contract keys, `roofline`, `cpu_baseline` and a handful of
-scalars -- compact_record()); the full record described below is written to bench_detail.json (repo root, and gpurun_out/ when present).
---sustain and --other-format are opt-in; the default run is one timed region + the instrumented passes + the bounded CPU baseline.
+scalars -- compact_record()); with --full the full record described below is also written to bench_detail.json (repo root, and the
+run's output folder when one is present).
+A plain run is setup, --warmup steps, the --steps timed steps and the line (`value`, `ms_per_step` = wall time of the timed region / steps,
+`step_ms`, `final_loss`).  --full adds, after the timed region, the instrumented passes, the decoder backward, the device data path, the
+forward latency, the exposed communication of data-parallel runs and the bounded CPU baseline; --sustain and --other-format are opt-in.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs()), before any of the extra legs run.
 
-Objects in the full record (bench_detail.json):
+Objects in the full record (bench_detail.json, --full):
   roofline      the DOMINANT kernel of the step = the convolution entry point with the largest exclusive time per step, found by an
                 extra pass outside the timed region with concurrency switched off (one stream; HIP events on that stream around
                 every convolution launch of 3 steps).  achieved = MFMA FLOPs the kernel EXECUTES per launch / its average launch
@@ -514,7 +518,7 @@ def other_format_leg(fmt, args):
     env = dict(os.environ)
     env.update(format_env(fmt))
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--sustain", str(args.sustain), "--no-cpu-baseline", "--no-loader"]
+           "--sustain", str(args.sustain), "--no-cpu-baseline", "--no-loader"] + (["--full"] if args.full else [])
     try:
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -718,6 +722,34 @@ def mfma_random_operand_peak(lib, seconds=0.7, iters=4000):
             "how": "fp_mfma_probe mode 1 (pseudo-random bf16 operands, MFMAs only) back to back for %.1f s; mean of the last third" % seconds}
 
 
+DUMP_SAMPLE = 1 << 20             # elements kept of each prediction tensor; the state keeps 4x as many
+
+
+def dump_outputs(path, step, model):
+    """what the timed path hands its caller after its last step -> `path`/<name>.npy, float32, ~32 MB in all: `losses` (the 21 values
+    TrainStep returns, LOSS_KEYS order), `pred_1_8` .. `pred_1_1` (the four [B,4,H,W] predictions of its forward) and `state` (every
+    floating entry of the model's state_dict after the step -- parameters after Adam, BatchNorm running statistics -- flattened and
+    concatenated in state_dict order).  Tensors larger than the sample keep the elements at sorted indices drawn from a torch.Generator
+    seeded with 0, the same for every run of the same workload."""
+    import numpy as np
+    from footprints_amd.training.losses import SCALES
+    os.makedirs(path, exist_ok=True)
+
+    def sample(flat, k):
+        if flat.numel() <= k:
+            return flat
+        idx = torch.randint(0, flat.numel(), (k,), generator=torch.Generator().manual_seed(0)).sort().values
+        return flat[idx.to(flat.device)]
+    torch.cuda.synchronize()
+    arrays = {"losses": step.losses}
+    for s, p in zip(SCALES, step.outputs):
+        arrays["pred_" + s.replace("/", "_")] = sample(p.reshape(-1), DUMP_SAMPLE)
+    sd = model.state_dict()
+    arrays["state"] = sample(torch.cat([v.reshape(-1) for v in sd.values() if v.is_floating_point()]), 4 * DUMP_SAMPLE)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v.detach().float().cpu().numpy())
+
+
 COMPACT_LIMIT = 4096              # bytes: the driver parses the LAST stdout line; round 5's 34.6 KB line came back unparsed (VERDICT r5 #1)
 
 
@@ -836,7 +868,14 @@ def main():
     ap.add_argument("--leg", choices=["train-only"], default=None, help="internal: time the training step only and print a small JSON object")
     ap.add_argument("--dry-run-dist", action="store_true", help="N > 1: spawn / rendezvous / one collective / ONE JSON line, no GPU "
                     "work (what the CPU test of the launch path runs)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline after the timed steps: kernel events and "
+                    "roofline, decoder backward, device data path, forward latency, exposed communication, CPU baseline, the full record "
+                    "(bench_detail.json); without it the run is setup, warm-up, the timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (losses, predictions, "
+                    "updated state; fixed seeded samples of the large ones) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_kernels and not args.full:
+        ap.error("--dump-kernels needs --full (the per-launch tables come from the kernel-event pass)")
     wl = WORKLOADS[args.workload]
     B, H, W = wl["B"], wl["H"], wl["W"]
 
@@ -913,6 +952,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)                   # host tensor: the gloo side of the group
     dt = float(t.item())
     final_loss = float(step.losses[20])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, mm.model)
     if args.leg == "train-only":
         if rank == 0:
             print(json.dumps({"img_per_s": round(world * B * args.steps / dt, 2), "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -925,7 +966,7 @@ def main():
     # one (--force-dist) it prices the branch itself (event edges, the communicator's launches); with N ranks it is the exposed, i.e.
     # un-overlapped, communication.  (The replicas' weights drift apart during the blocks without exchange: nothing after this reads them.)
     exposed = None
-    if step.reducer is not None:
+    if args.full and step.reducer is not None:
         step_nc = TrainStep(mm.model, mm.optimiser, distributed=False)
         mm.optimiser.grad_scale = step.reducer.grad_scale
 
@@ -966,7 +1007,7 @@ def main():
     # kernel-exclusive pass (outside the timed region): same steps on ONE stream, HIP events around every convolution launch
     # (every rank runs it when data-parallel: the steps contain the bucket all-reduces; rank 0 reports)
     xtimer, xsteps, ktable, ktable_conc = None, 3, None, None
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         was, was_plan = step.eng.concurrent, step.use_plan
         step.eng.concurrent, step.use_plan = False, False            # eager, one stream: the instrumented wrappers see every launch
         step(batch)
@@ -993,7 +1034,7 @@ def main():
     # decoder backward alone: both decoders, from d loss / d outputs to d loss / d features plus all decoder
     # weight gradients, HIP events around repeated runs on one saved forward (all five streams, joined inside the bracket)
     dec_bwd = None
-    if rank == 0:
+    if args.full and rank == 0:
         eng = step.eng
         eng.forward(batch["image"], training=True, save_for_backward=True, outputs=step.outputs)
         ops.loss_fwd_bwd(step.outputs, batch, step.losses, step.dpreds, step.depth_range, step.prior)
@@ -1020,7 +1061,7 @@ def main():
     # host samples (resized uint8 images + float64 label maps, as the file readers deliver them) -> pinned double-buffered H2D ->
     # flip / ColorJitter / ToTensor / label algebra kernels on a copy stream -> TrainStep.  Decode + resize stay host-side.
     loader_leg = None
-    if rank == 0 and not distributed and not args.no_loader and args.workload == "kitti":
+    if args.full and rank == 0 and not distributed and not args.no_loader and args.workload == "kitti":
         import random as _random
         import numpy as np
         from footprints_amd.datasets import DeviceBatchAssembler, DeviceLoader
@@ -1062,27 +1103,29 @@ def main():
                               "of this leg only memcpy's pre-decoded samples into pinned memory (decode / resize are dataset plumbing, out of scope)"}
 
     # forward-only latency (configs[1]): eval-mode, no_grad, same batch
-    mm.model.eval()
-    with torch.no_grad():
-        for _ in range(2):
-            mm.model(batch["image"])
-        torch.cuda.synchronize()
-        f0 = time.perf_counter()
-        for _ in range(5):
-            mm.model(batch["image"])
-        torch.cuda.synchronize()
-        fwd_ms_img = (time.perf_counter() - f0) / 5 / B * 1e3
-        # opt-in two-term inference mode of the tile convolutions (NOT exact: ~2e-5 of the channel max, tests/test_gpu_network.py)
-        mm.model.inference_precision = "bf16x2"
-        for _ in range(2):
-            mm.model(batch["image"])
-        torch.cuda.synchronize()
-        f0 = time.perf_counter()
-        for _ in range(5):
-            mm.model(batch["image"])
-        torch.cuda.synchronize()
-        fwd_ms_img_bf2 = (time.perf_counter() - f0) / 5 / B * 1e3
-        mm.model.inference_precision = "exact"
+    fwd_ms_img = fwd_ms_img_bf2 = None
+    if args.full:
+        mm.model.eval()
+        with torch.no_grad():
+            for _ in range(2):
+                mm.model(batch["image"])
+            torch.cuda.synchronize()
+            f0 = time.perf_counter()
+            for _ in range(5):
+                mm.model(batch["image"])
+            torch.cuda.synchronize()
+            fwd_ms_img = (time.perf_counter() - f0) / 5 / B * 1e3
+            # opt-in two-term inference mode of the tile convolutions (NOT exact: ~2e-5 of the channel max, tests/test_gpu_network.py)
+            mm.model.inference_precision = "bf16x2"
+            for _ in range(2):
+                mm.model(batch["image"])
+            torch.cuda.synchronize()
+            f0 = time.perf_counter()
+            for _ in range(5):
+                mm.model(batch["image"])
+            torch.cuda.synchronize()
+            fwd_ms_img_bf2 = (time.perf_counter() - f0) / 5 / B * 1e3
+            mm.model.inference_precision = "exact"
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
@@ -1103,21 +1146,23 @@ def main():
                               "(x = h + m + l in bf16, 6 of 9 bf16 MFMA products: error <= fp32 MFMA); remaining convs native fp32 MFMA"),
                "config": {"workload": wl["name"], "per_gpu_batch": B, "global_batch": B * world, "height": H, "width": W,
                           "parallelism": ("dp%d" % world if world > 1 else "single") + (" (forced data-parallel branch, world of one)" if args.force_dist and world == 1 else "")},
-               "fwd_ms_per_img": round(fwd_ms_img, 4),
-               "fwd_ms_per_img_optin_bf16x2": {"value": round(fwd_ms_img_bf2, 4), "note": "model.inference_precision = 'bf16x2': two bf16 terms per operand "
-                                               "in the 3x3 tile convolutions, three MFMA products; outputs within ~2e-5 of the channel max (bar 1e-4), not the default"},
                "final_loss": round(final_loss, 5),
                "step_ms": {"median": round(step_ms[len(step_ms) // 2], 3), "p10": round(step_ms[len(step_ms) // 10], 3),
                            "p90": round(step_ms[min(len(step_ms) - 1, (len(step_ms) * 9) // 10)], 3),
                            "note": "GPU-side durations between per-step HIP events inside the timed region (rank 0)"},
                "sustained": sustained, "decoder_backward": dec_bwd, "device_data_path": loader_leg}
-        gf_fwd, gf_step = network_conv_gflop(B, H, W)
-        # whole-step figure: the reference graph's conv FLOPs (fwd + dgrad + wgrad) over the measured step time, i.e. including
-        # every non-conv kernel, launch gap and the FLOPs the nearest-x2 phase decomposition does not execute
-        out["step_conv_tflops"] = {"algorithmic_gflop_per_step": round(gf_step, 1), "tflops": round(gf_step / ms_per_step, 2),
-                                   "frac_of_f32_mfma_peak": round(gf_step / ms_per_step / MFMA_F32_PEAK_TFLOPS, 4),
-                                   "frac_of_bf16x6_roof": round(gf_step / ms_per_step / BF16X6_PEAK_TFLOPS, 4),
-                                   "fwd_algorithmic_gflop": round(gf_fwd, 1), "fwd_tflops": round(gf_fwd / (fwd_ms_img * B), 2)}
+        if args.full:
+            out["fwd_ms_per_img"] = round(fwd_ms_img, 4)
+            out["fwd_ms_per_img_optin_bf16x2"] = {"value": round(fwd_ms_img_bf2, 4), "note": "model.inference_precision = 'bf16x2': two bf16 terms per "
+                                                  "operand in the 3x3 tile convolutions, three MFMA products; outputs within ~2e-5 of the channel max (bar "
+                                                  "1e-4), not the default"}
+            gf_fwd, gf_step = network_conv_gflop(B, H, W)
+            # whole-step figure: the reference graph's conv FLOPs (fwd + dgrad + wgrad) over the measured step time, i.e. including
+            # every non-conv kernel, launch gap and the FLOPs the nearest-x2 phase decomposition does not execute
+            out["step_conv_tflops"] = {"algorithmic_gflop_per_step": round(gf_step, 1), "tflops": round(gf_step / ms_per_step, 2),
+                                       "frac_of_f32_mfma_peak": round(gf_step / ms_per_step / MFMA_F32_PEAK_TFLOPS, 4),
+                                       "frac_of_bf16x6_roof": round(gf_step / ms_per_step / BF16X6_PEAK_TFLOPS, 4),
+                                       "fwd_algorithmic_gflop": round(gf_fwd, 1), "fwd_tflops": round(gf_fwd / (fwd_ms_img * B), 2)}
         if xtimer is not None:
             groups = xtimer.groups(xsteps)
             # kernel-only durations (fp_ktime_*: events around the kernel launch itself, per kernel symbol) next to each entry
@@ -1225,7 +1270,7 @@ def main():
             other = [f for f in FORMATS if f != FMT][0]
             out[other] = {"what": "the same command re-run in a child process with FP_OPERANDS=%s (%s): same steps / warm-up / sustain, same "
                                   "instrumentation; `value` above is NOT this leg" % (other, DTYPE_LABEL[other]), **other_format_leg(other, args)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
     destroy_communicators()
     if world > 1:
@@ -1237,7 +1282,7 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
-        print(compact_record(out, write_detail(out)), flush=True)
+        print(compact_record(out, write_detail(out) if args.full else None), flush=True)
 
 
 if __name__ == "__main__":

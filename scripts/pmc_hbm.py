@@ -3,7 +3,7 @@ into profiles/round<N>_pmc_hbm_<workload>.json, the file bench.py's `roofline.tr
 
     rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_f -o pmc -- python scripts/step_loop.py kitti 2 1
     rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_w -o pmc -- python scripts/step_loop.py kitti 2 1
-    python scripts/pmc_hbm.py kitti gpurun_out/pmc_f gpurun_out/pmc_w [kernels.json from bench.py --dump-kernels] profiles/round2_pmc_hbm_kitti.json
+    python scripts/pmc_hbm.py kitti <pmc_f dir> <pmc_w dir> [kernels.json from bench.py --full --dump-kernels] profiles/round2_pmc_hbm_kitti.json
 
 Units / corrections (MI355X_MICROARCH.md, HBM section): the counters are in KB; on gfx950 FETCH_SIZE reports exactly 1/2 of the
 bytes of wide coalesced reads -> x2; WRITE_SIZE is uncalibrated and is given as reported.  Per kernel family: average per launch."""

@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3prof; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for wl in kitti matterport; do
-  python $R/bench.py --workload $wl --dump-kernels $O/kernels_$wl.json --no-cpu-baseline --no-exact-split --no-loader > $O/bench_pre_$wl.json 2>/dev/null
+  python $R/bench.py --full --workload $wl --dump-kernels $O/kernels_$wl.json --no-cpu-baseline --no-exact-split --no-loader > $O/bench_pre_$wl.json 2>/dev/null
   rm -rf /tmp/pf /tmp/pw /tmp/ps
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pf -o pmc -- python $R/scripts/step_loop.py $wl 2 1 > /dev/null 2>&1
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pw -o pmc -- python $R/scripts/step_loop.py $wl 2 1 > /dev/null 2>&1
@@ -18,6 +18,6 @@ python $R/scripts/rocprof_summary.py $DB $O/round3_kernel_stats_concurrent_kitti
 python $R/scripts/timeline.py $DB > $O/round3_timeline_concurrent_step.txt 2>&1
 cp $O/round3_pmc_hbm_*.json $R/profiles/ 2>/dev/null
 cd $R
-for wl in kitti matterport; do python bench.py --workload $wl > $O/round3_bench_line_$wl.json 2> $O/bench_$wl.err; done
-python bench.py --force-dist --no-cpu-baseline --no-loader --no-kernel-events > $O/round3_bench_line_kitti_forced_dp.json 2>/dev/null
+for wl in kitti matterport; do python bench.py --full --workload $wl > $O/round3_bench_line_$wl.json 2> $O/bench_$wl.err; done
+python bench.py --full --force-dist --no-cpu-baseline --no-loader --no-kernel-events > $O/round3_bench_line_kitti_forced_dp.json 2>/dev/null
 ls -la $O

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r4prof; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 t0=$(date +%s)
 for wl in kitti matterport; do
-  python $R/bench.py --workload $wl --steps 20 --warmup 5 --dump-kernels $O/kernels_$wl.json --no-cpu-baseline --no-exact-split --no-loader > $O/bench_pre_$wl.json 2>/dev/null
+  python $R/bench.py --full --workload $wl --steps 20 --warmup 5 --dump-kernels $O/kernels_$wl.json --no-cpu-baseline --no-exact-split --no-loader > $O/bench_pre_$wl.json 2>/dev/null
   rm -rf /tmp/pf /tmp/pw /tmp/ps
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pf -o pmc -- python $R/scripts/step_loop.py $wl 2 1 > /dev/null 2>&1
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pw -o pmc -- python $R/scripts/step_loop.py $wl 2 1 > /dev/null 2>&1
@@ -46,7 +46,7 @@ cd $R
 python scripts/hbm_microbench.py > $O/round4_hbm_kernels.txt 2>&1
 python scripts/tile_bench.py default 30 > $O/round4_tile_bench.txt 2>&1
 cp $O/round4_pmc_hbm_*.json $R/profiles/ 2>/dev/null       # bench.py attaches the traffic of THIS build (digest checked)
-for wl in kitti matterport; do python bench.py --workload $wl > $O/round4_bench_line_$wl.json 2> $O/bench_$wl.err; done
-python bench.py --force-dist --no-cpu-baseline --no-loader > $O/round4_bench_line_kitti_forced_dp.json 2>/dev/null
+for wl in kitti matterport; do python bench.py --full --workload $wl > $O/round4_bench_line_$wl.json 2> $O/bench_$wl.err; done
+python bench.py --full --force-dist --no-cpu-baseline --no-loader > $O/round4_bench_line_kitti_forced_dp.json 2>/dev/null
 echo "all done t=$(( $(date +%s)-t0 ))"
 ls -la $O

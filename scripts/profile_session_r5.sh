@@ -10,7 +10,7 @@ SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_
 for fmt in exact fp16_pair; do
   export FP_OPERANDS=$fmt
   wl=kitti
-  python $R/bench.py --workload $wl --steps 20 --warmup 5 --sustain 0 --dump-kernels $O/kernels_${wl}_$fmt.json --no-cpu-baseline --no-other-format --no-loader > $O/bench_pre_${wl}_$fmt.json 2>/dev/null
+  python $R/bench.py --full --workload $wl --steps 20 --warmup 5 --sustain 0 --dump-kernels $O/kernels_${wl}_$fmt.json --no-cpu-baseline --no-other-format --no-loader > $O/bench_pre_${wl}_$fmt.json 2>/dev/null
   ms=$(python -c "import json,sys; print(json.loads(open('$O/bench_pre_${wl}_$fmt.json').read().strip().splitlines()[-1])['ms_per_step'])")
   rm -rf /tmp/pf /tmp/pw /tmp/pq /tmp/ps
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pf -o pmc -- python $R/scripts/step_loop.py $wl 2 1 > /dev/null 2>&1
@@ -31,8 +31,8 @@ echo "timeline done t=$(( $(date +%s)-t0 ))"
 cd $R
 python scripts/hbm_microbench.py > $O/round5_hbm_kernels.txt 2>&1
 cp $O/round5_pmc_hbm_*.json $O/round5_pmc_step_*.json $R/profiles/ 2>/dev/null       # bench.py attaches the counters of THIS build (digest checked)
-python bench.py > $O/round5_bench_line_kitti.json 2> $O/bench_kitti.err
-python bench.py --workload matterport --no-cpu-baseline > $O/round5_bench_line_matterport.json 2> $O/bench_matterport.err
-python bench.py --force-dist --no-cpu-baseline --no-loader --sustain 0 > $O/round5_bench_line_kitti_forced_dp.json 2>/dev/null
+python bench.py --full > $O/round5_bench_line_kitti.json 2> $O/bench_kitti.err
+python bench.py --full --workload matterport --no-cpu-baseline > $O/round5_bench_line_matterport.json 2> $O/bench_matterport.err
+python bench.py --full --force-dist --no-cpu-baseline --no-loader --sustain 0 > $O/round5_bench_line_kitti_forced_dp.json 2>/dev/null
 echo "all done t=$(( $(date +%s)-t0 ))"
 ls -la $O

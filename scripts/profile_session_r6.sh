@@ -10,7 +10,7 @@ SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_
 for fmt in exact fp16_pair; do
   export FP_OPERANDS=$fmt
   wl=kitti
-  python $R/bench.py --workload $wl --steps 20 --warmup 5 --sustain 0 --dump-kernels $O/kernels_${wl}_$fmt.json --no-cpu-baseline --no-other-format --no-loader > $O/bench_pre_${wl}_$fmt.json 2>/dev/null
+  python $R/bench.py --full --workload $wl --steps 20 --warmup 5 --sustain 0 --dump-kernels $O/kernels_${wl}_$fmt.json --no-cpu-baseline --no-other-format --no-loader > $O/bench_pre_${wl}_$fmt.json 2>/dev/null
   ms=$(python -c "import json,sys; print(json.loads(open('$O/bench_pre_${wl}_$fmt.json').read().strip().splitlines()[-1])['ms_per_step'])")
   rm -rf /tmp/pf /tmp/pw /tmp/pq /tmp/ps
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pf -o pmc -- python $R/scripts/step_loop.py $wl 2 1 > /dev/null 2>&1
@@ -33,10 +33,10 @@ python scripts/hbm_microbench.py > $O/round6_hbm_kernels.txt 2>&1
 cp $O/round6_pmc_hbm_*.json $O/round6_pmc_step_*.json $R/profiles/ 2>/dev/null       # bench.py attaches the counters of THIS build (digest checked)
 # the stdout line is the compact record (round 6); the full record is bench_detail.json beside it -- both are kept
 S=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/round6_bench_line_kitti.json 2> $O/bench_kitti.err; cp bench_detail.json $O/round6_bench_detail_kitti.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/round6_bench_line_kitti.json 2> $O/bench_kitti.err; cp bench_detail.json $O/round6_bench_detail_kitti.json
 echo "driver-form bench wall: $(( $(date +%s)-S )) s" > $O/round6_bench_wall.txt
-python bench.py --other-format --sustain 10 > $O/round6_bench_line_kitti_all_legs.json 2> $O/bench_kitti_all.err; cp bench_detail.json $O/round6_bench_detail_kitti_all_legs.json
-python bench.py --workload matterport --no-cpu-baseline > $O/round6_bench_line_matterport.json 2> $O/bench_matterport.err; cp bench_detail.json $O/round6_bench_detail_matterport.json
-python bench.py --force-dist --no-cpu-baseline --no-loader > $O/round6_bench_line_kitti_forced_dp.json 2>/dev/null; cp bench_detail.json $O/round6_bench_detail_kitti_forced_dp.json
+python bench.py --full --other-format --sustain 10 > $O/round6_bench_line_kitti_all_legs.json 2> $O/bench_kitti_all.err; cp bench_detail.json $O/round6_bench_detail_kitti_all_legs.json
+python bench.py --full --workload matterport --no-cpu-baseline > $O/round6_bench_line_matterport.json 2> $O/bench_matterport.err; cp bench_detail.json $O/round6_bench_detail_matterport.json
+python bench.py --full --force-dist --no-cpu-baseline --no-loader > $O/round6_bench_line_kitti_forced_dp.json 2>/dev/null; cp bench_detail.json $O/round6_bench_detail_kitti_forced_dp.json
 echo "all done t=$(( $(date +%s)-t0 ))"
 ls -la $O

@@ -20,5 +20,5 @@ FP_TILE_PERSIST=0 FP_LIB=$B/lib_persist3.so TILE_SHAPES=0,1,4,5 timeout 300 pyth
 echo "bench done t=$(( $(date +%s)-t0 ))" >> $out/summary.txt
 scripts/ab_lib_step.sh kitti rounds=2 r3 default persist3 default@FP_TILE_BIG_MIN_WG=512 persist3@FP_TILE_BIG_MIN_WG=512 > $out/ab_step.txt 2>&1
 echo "ab done t=$(( $(date +%s)-t0 ))" >> $out/summary.txt
-timeout 300 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$? t=$(( $(date +%s)-t0 ))" >> $out/summary.txt
+timeout 300 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$? t=$(( $(date +%s)-t0 ))" >> $out/summary.txt
 cat $out/summary.txt; cat $out/tile_bench.txt; cat $out/ab_step.txt; tail -3 $out/pytest_*.log

@@ -7,7 +7,7 @@ t0=$(date +%s)
 timeout 1500 python -m pytest tests -m gpu -q --durations=25 -p no:cacheprovider > $O/pytest_gpu.log 2>&1; echo "pytest rc=$? t=$(( $(date +%s)-t0 ))" > $O/summary.txt
 tail -40 $O/pytest_gpu.log
 cp -r gpurun_out/parity $O/ 2>/dev/null
-timeout 600 python bench.py > $O/bench_kitti.json 2> $O/bench_kitti.err; echo "bench rc=$? t=$(( $(date +%s)-t0 ))" >> $O/summary.txt
+timeout 600 python bench.py --full > $O/bench_kitti.json 2> $O/bench_kitti.err; echo "bench rc=$? t=$(( $(date +%s)-t0 ))" >> $O/summary.txt
 cat $O/summary.txt
 python - <<'P'
 import json,sys

@@ -8,7 +8,7 @@ tail -30 $O/pytest_gpu.log
 cp -r gpurun_out/parity $O/ 2>/dev/null
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$? t=$(( $(date +%s)-t0 ))" >> $O/summary.txt
 tail -2 $O/smoke.log
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench.err; echo "bench rc=$? t=$(( $(date +%s)-t0 ))" >> $O/summary.txt
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench.err; echo "bench rc=$? t=$(( $(date +%s)-t0 ))" >> $O/summary.txt
 python -c "
 import json; d=json.loads(open('$O/bench_driver_cmd.json').read().strip().splitlines()[-1])
 print('value', d['value'], d['ms_per_step'], d['dtype'][:50]); print('sustained', d['sustained']['img_per_s'], d['sustained']['shader_clock_mhz'])

@@ -42,8 +42,55 @@ def digest(name, t, full_limit=1 << 15):
             name + "#sample": flat[::STRIDE].numpy().copy(), name + "#shape": np.array(t.shape)}
 
 
+def sparse_sample(t, n=512):
+    """strided sample of at most `n` elements of the flattened tensor (shared by the generator and the tests)"""
+    flat = t.detach().cpu().reshape(-1)
+    return flat[::max(1, -(-flat.numel() // n))]
+
+
+PART_LIMIT = 1 << 20               # bytes: a fixture that does not fit one file goes on in <name>.part2.npz, <name>.part3.npz, ...
+
+
+def _part_path(name, k):
+    return os.path.join(GOLDEN_DIR, name + (".npz" if k == 1 else ".part%d.npz" % k))
+
+
+class _Parts:
+    """the parts of one fixture seen as one archive (`.files`, `[name]`, like np.load's)"""
+
+    def __init__(self, parts):
+        self.parts = parts
+        self.files = [f for p in parts for f in p.files]
+
+    def __getitem__(self, key):
+        for p in self.parts:
+            if key in p.files:
+                return p[key]
+        raise KeyError(key)
+
+
+def save(name, arrays):
+    """np.savez_compressed of `arrays` as tests/golden/<name>.npz, split into consecutive parts when one file would reach PART_LIMIT"""
+    keys = list(arrays)
+    for n in range(1, len(keys) + 1):
+        cut = [len(keys) * i // n for i in range(n + 1)]
+        for k in range(n):
+            np.savez_compressed(_part_path(name, k + 1), **{key: arrays[key] for key in keys[cut[k]:cut[k + 1]]})
+        if all(os.path.getsize(_part_path(name, k + 1)) < PART_LIMIT for k in range(n)):
+            break
+    k = n + 1
+    while os.path.exists(_part_path(name, k)):     # parts of an earlier, larger version
+        os.remove(_part_path(name, k))
+        k += 1
+    return [_part_path(name, k + 1) for k in range(n)]
+
+
 def load(name):
-    return np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False)
+    parts, k = [], 1
+    while k == 1 or os.path.exists(_part_path(name, k)):
+        parts.append(np.load(_part_path(name, k), allow_pickle=False))
+        k += 1
+    return parts[0] if len(parts) == 1 else _Parts(parts)
 
 
 def compare(gold, name, t, rtol=1e-4, atol_scale=1e-4):

@@ -2,12 +2,13 @@
 
 Run in the build container only (needs /root/reference):
     python tests/golden/make_golden.py
-Writes tests/golden/*.npz.  Inputs and weights are regenerated from
+Writes tests/golden/*.npz (split into parts below 1 MiB, see digest.save).  Inputs and weights are regenerated from
 oracle/filler.py (counter hash) by name, so only outputs / digests are stored.
 
 What is reference-authored arithmetic and what is not:
   * G1 blocks, G2 decoder, G4 loss            -> reference classes, directly.
-  * G3 whole net, G5 train steps, G6 predict  -> reference FootprintNetwork /
+  * G3 whole net, G5 train steps, G6 predict,
+    G12 vs-reference step                     -> reference FootprintNetwork /
     LossManager / Adam, but the ENCODER inside is oracle/standin_resnet.py
     (torchvision is absent) => encoder part "parity unpinned" by the reference.
 """
@@ -21,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from oracle import filler, ref_import, restatement as R  # noqa: E402
-from tests.golden.digest import digest, GOLDEN_DIR, fill, fill_value      # noqa: E402
+from tests.golden.digest import digest, GOLDEN_DIR, fill, fill_value, save, sparse_sample      # noqa: E402
 
 
 def fill_module(mod, tag):
@@ -196,6 +197,54 @@ def g6_predict(net):
     pred = m(x)["1/1"].data.cpu().numpy().squeeze(0)          # predict_simple.py:67-68 (no no_grad: quirk)
     out.update(digest("predict.npy", torch.from_numpy(pred), full_limit=0))
     out["predict.mask_logit_gt_half"] = np.packbits(pred[1] > 0.5)   # predict_simple.py:77 threshold on the LOGIT
+    return out
+
+
+def g12_vs_reference(net, loss_mod):
+    """What tests/test_oracle_vs_reference.py holds the restatement to: the reference FootprintNetwork's state_dict layout (keys and
+    shapes), and one training forward + LossManager + backward on the "vsref" state and batch -- the four outputs whole, the losses,
+    and per parameter its gradient's max |g|, float64 sum and abs-sum and a strided sample (tests/golden/digest.py sparse_sample)."""
+    out = {}
+    sd = net.FootprintNetwork(pretrained=False).state_dict()
+    out["layout.keys"] = np.array(list(sd))
+    out["layout.shapes"] = np.array([list(v.shape) + [-1] * (4 - v.dim()) for v in sd.values()], dtype=np.int64)
+    P, B = R.make_state(tag="vsref")
+    batch = R.make_batch(2, 64, 64, tag="vsref")
+    m = net.FootprintNetwork(pretrained=False)
+    m.load_state_dict({**P, **B})
+    m.train()
+    o = m(batch["image"])
+    losses = loss_mod.LossManager((0.1, 100), 0.25)(dict(o), batch)
+    losses["loss"].backward()
+    for k in o:
+        out["out" + k] = o[k].detach().numpy()
+    out["loss.keys"] = np.array([repr(k) for k in losses])          # some keys are (name, scale) tuples
+    out["loss.values"] = np.array([float(losses[k]) for k in losses], dtype=np.float64)
+    names, none, gmax, gsum, gabs, samples = [], [], [], [], [], []
+    for k, p in m.named_parameters():
+        names.append(k)
+        none.append(p.grad is None)
+        g = p.grad if p.grad is not None else torch.zeros(0)
+        gmax.append(float(g.abs().max()) if g.numel() else 0.0)
+        gsum.append(float(g.double().sum()))
+        gabs.append(float(g.double().abs().sum()))
+        samples.append(sparse_sample(g).numpy())
+    out["grad.names"] = np.array(names)
+    out["grad.none"] = np.array(none)
+    out["grad.max"], out["grad.sum"], out["grad.abs"] = np.array(gmax), np.array(gsum), np.array(gabs)
+    out["grad.sample"] = np.concatenate(samples)
+    out["grad.sample_offsets"] = np.cumsum([0] + [len(s) for s in samples]).astype(np.int64)
+    # the reference's command-line defaults (footprints/options.py:13-128), parsed by its own Options class with no arguments
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("ref_options", os.path.join(ref_import.REFERENCE_ROOT, "footprints", "options.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    argv, sys.argv = sys.argv, ["x"]
+    try:
+        out["options.json"] = np.array(json.dumps(vars(mod.Options().parse()), sort_keys=True))
+    finally:
+        sys.argv = argv
     return out
 
 
@@ -440,13 +489,13 @@ def main():
                      ("g5_train", lambda: g5_train(net, loss_mod)), ("g6_predict", lambda: g6_predict(net)),
                      ("g7_metrics", g7_metrics), ("g8_evaluator", g8_evaluator),
                      ("g9_segmentor", g9_segmentor), ("g10_data_path", g10_data_path),
-                     ("g11_data_path_matterport", g11_data_path_matterport)):
+                     ("g11_data_path_matterport", g11_data_path_matterport),
+                     ("g12_vs_reference", lambda: g12_vs_reference(net, loss_mod))):
         if only and name not in only:
             continue
         d = fn()
-        path = os.path.join(GOLDEN_DIR, name + ".npz")
-        np.savez_compressed(path, **d)
-        print("%-12s %4d arrays %8.1f KB" % (name, len(d), os.path.getsize(path) / 1024))
+        paths = save(name, d)
+        print("%-12s %4d arrays %8.1f KB in %d file(s)" % (name, len(d), sum(os.path.getsize(p) for p in paths) / 1024, len(paths)))
 
 
 if __name__ == "__main__":

@@ -86,13 +86,19 @@ def test_compact_line_is_small_and_round_trips():
 
 
 def test_default_run_skips_the_lab_notebook_legs():
-    """the default command line (what the driver runs) has the sustained leg and the second-format child switched off"""
+    """the default command line (what the driver runs) has the sustained leg and the second-format child switched off, and every leg
+    beyond the timed steps (kernel events, decoder backward, data path, forward latency, exposed communication, CPU baseline, the full
+    record) behind --full, which is off by default"""
     sys.path.insert(0, ROOT)
     import bench
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'ap.add_argument("--sustain", type=float, default=0.0' in src
     assert 'ap.add_argument("--other-format", dest="other_format", action="store_true"' in src
-    assert "print(compact_record(out, write_detail(out)), flush=True)" in src and "print(json.dumps(out)" not in src
+    assert 'ap.add_argument("--full", action="store_true"' in src
+    for gate in ("if args.full and step.reducer is not None:", "if args.full and not args.no_kernel_events:", "if args.full and rank == 0:",
+                 "if args.full and rank == 0 and not distributed and not args.no_loader", "if args.full and world == 1 and not args.no_cpu_baseline:"):
+        assert gate in src, gate
+    assert "print(compact_record(out, write_detail(out) if args.full else None), flush=True)" in src and "print(json.dumps(out)" not in src
 
 
 def test_whole_step_algorithmic_bytes_reproduce_the_survey_figures():

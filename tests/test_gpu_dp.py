@@ -443,7 +443,7 @@ def test_ranks_on_one_physical_gpu_are_refused_unless_asked_for():
 
 # ---- bench.py's forced data-parallel line (world of one): the RCCL communicator counts its ranks itself, and the exchange costs nothing measurable --
 def test_bench_forced_data_parallel_line_counts_its_ranks_and_prices_the_exchange():
-    """`bench.py --force-dist` (what the N > 1 launches run, in a world of one): transport rccl, ncclCommCount == 1 (bench.py exits non-zero when the
+    """`bench.py --full --force-dist` (what the N > 1 launches run, in a world of one): transport rccl, ncclCommCount == 1 (bench.py exits non-zero when the
     communicator's own count differs from the ranks it was launched with), the bucket all-reduces inside the recorded plan, and
     `exposed_communication` -- the same step with and without its all-reduces, alternating blocks in one process -- within 5 % of the step."""
     import json
@@ -453,7 +453,7 @@ def test_bench_forced_data_parallel_line_counts_its_ranks_and_prices_the_exchang
     env = dict(os.environ)
     for k in ("FP_DP_TRANSPORT", "FP_DP_FORCE", "WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "10", "--warmup", "5", "--sustain", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--steps", "10", "--warmup", "5", "--sustain", "0",
                         "--no-cpu-baseline", "--no-loader", "--no-other-format", "--no-kernel-events"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, (r.stderr or r.stdout)[-2000:]

@@ -137,3 +137,35 @@ def test_frozen_parameter_is_refused_and_mixed_grad_accumulation():
     out = m(batch["image"])
     with pytest.raises(RuntimeError, match="frozen parameters"):
         lm(out, batch)["loss"].backward()
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: the line carries the contract keys for K timed steps, and DIR holds what the last
+    timed step computed (float32 .npy, well under 64 MB): the 21 losses -- the last one is the line's final_loss -- the four predictions
+    and the updated state, all finite; a second run with the same arguments starts from the same inputs and lands on the same losses."""
+    import json
+    import subprocess
+    import sys
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stderr or r.stdout)[-2000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in rec, k
+        assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["ms_per_step"] > 0 and rec["unit"] == "img/s" and rec["higher_is_better"] is True
+        assert "detail" not in rec and "roofline" not in rec and "cpu_baseline" not in rec         # the extra legs are --full's
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["losses.npy", "pred_1_1.npy", "pred_1_2.npy", "pred_1_4.npy", "pred_1_8.npy", "state.npy"], files
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        arr = {p.stem: np.load(p) for p in d.iterdir()}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arr.values())
+        assert arr["losses"].shape == (21,) and abs(float(arr["losses"][20]) - rec["final_loss"]) <= 1e-5 * max(1.0, abs(rec["final_loss"]))
+        assert arr["state"].size == 1 << 22 and all(arr["pred_" + s].size == 1 << 20 for s in ("1_8", "1_4", "1_2", "1_1"))
+        lines.append(rec)
+        dumps.append(arr)
+    np.testing.assert_allclose(dumps[0]["losses"], dumps[1]["losses"], rtol=1e-4)

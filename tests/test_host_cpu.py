@@ -273,8 +273,9 @@ def test_no_register_spills_in_the_matrix_kernels(tmp_path):
 
 def test_options_surface_matches_reference_flags():
     """footprints_amd/options.py mirrors footprints/options.py:13-128: every reference flag with the same default (checked against
-    the reference's own parser when /root/reference is present, else against the committed table)"""
-    import importlib.util
+    the reference's own parser, as recorded in tests/golden/g12_vs_reference.npz by tests/golden/make_golden.py)"""
+    import json
+    from tests.golden.digest import load
     from footprints_amd.options import Options
     ours = vars(Options().parse([]))
     table = {"mode": "train", "height": 192, "width": 640, "depth_range": [0.1, 100], "training_dataset": "kitti", "epochs": 10,
@@ -282,18 +283,7 @@ def test_options_surface_matches_reference_flags():
              "no_depth_mask": False, "moving_objects_method": "ours", "project_down_baseline": False, "num_workers": 8,
              "config_path": "paths.yaml", "model_name": "model", "log_path": "./logs", "inference_data_type": "kitti",
              "load_path": None, "inference_save_path": None, "save_test_visualisations": False}
-    ref_path = "/root/reference/footprints/options.py"
-    if os.path.exists(ref_path):
-        spec = importlib.util.spec_from_file_location("ref_options", ref_path)
-        mod = importlib.util.module_from_spec(spec)
-        sys.dont_write_bytecode = True
-        spec.loader.exec_module(mod)
-        argv, sys.argv = sys.argv, ["x"]
-        try:
-            ref = vars(mod.Options().parse())
-        finally:
-            sys.argv = argv
-        assert ref == table
+    assert json.loads(str(load("g12_vs_reference")["options.json"])) == table
     for k, v in table.items():
         assert ours[k] == v, k
     assert set(ours) - set(table) == {"synthetic_steps", "device_augment"}
