@@ -124,6 +124,18 @@ SIGNATURES = {
     "fp_scale_rows": (C.c_int, [_P, _P, _P, _I64, _I64, _P]),
     "fp_eval_mask_counts": (C.c_int, [_P, _I32, _P, _P, _I32, _I32, _I64, _I64, _P, _P]),
     "fp_eval_depth_sums": (C.c_int, [_P, _I32, _P, _I32, _I64, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P]),
+    "fp_gt_workspace": (_I64, [_I32, _I32, _I32]),
+    "fp_gt_project": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "fp_gt_splat": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_gt_warp_splat": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_gt_aggregate": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "fp_gt_moving_mask": (C.c_int, [_P, _P, _P, _P, _P, _D, _I32, _I32, _P, _P]),
+    "fp_gt_ground_count": (C.c_int, [_P, _D, _I32, _I32, _P, _P]),
+    "fp_gt_project_to_world": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
+    "fp_gt_project_to_camera": (C.c_int, [_P, _P, _P, _I32, _I64, _P, _P]),
+    "fp_gt_plane_score": (C.c_int, [_P, _P, _D, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "fp_gt_flatten_splat": (C.c_int, [_P, _P, _D, _P, _P, _I32, _I32, _P, _I64, _P, _P]),
+    "fp_gt_depth_mask": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     "fp_pack_pred_fp16": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "fp_colsum_workspace": (_I64, [_I64, _I32]),
     "fp_colsum": (C.c_int, [_P, _I64, _I32, _P, C.c_int, _P, _I64, _P]),

@@ -896,3 +896,169 @@ def seg_loss_fwd_bwd(preds, ground_mask, loss_mask, losses_out, dpreds=None):
     _lib.check(lib.fp_seg_loss_fwd_bwd(P, D, hs, wss, bs, _f32(ground_mask), _f32(loss_mask), B, H, W, _f32(losses_out), ws.data_ptr(), ws.numel(),
                                        stream()), "fp_seg_loss_fwd_bwd")
     return losses_out
+
+
+# ---- training-label generation (csrc/gt_gen.hip; semantics in include/footprints_hip.h) ----------------------------------------------
+def _typed(t, dtype, name):
+    if t is not None and t.dtype != dtype:
+        raise RuntimeError("footprints_amd.ops: %s must be %s" % (name, dtype))
+    return _chk(t, name)
+
+
+def gt_workspace_bytes(B, H, W):
+    """bytes of key plane for B frames of H x W (host-only query; raises on B > 512 or H * W * 64 >= 2^32 - 1)"""
+    n = _lib.load().fp_gt_workspace(B, H, W)
+    if n < 0:
+        _lib.check(-1, "fp_gt_workspace")
+    return n
+
+
+def gt_keys(B, H, W, device):
+    """a key plane of its own (uint64 as int64 [B, H*W]): the splats fill it, gt_aggregate / gt_depth_mask read it"""
+    return torch.empty(gt_workspace_bytes(B, H, W) // 8, dtype=torch.int64, device=device).view(B, H * W)
+
+
+def _gt_mats(B, **mats):
+    out = []
+    for name, m in mats.items():
+        if tuple(m.shape) != (B, 4, 4):
+            raise RuntimeError("footprints_amd.ops: %s must be [%d, 4, 4]" % (name, B))
+        out.append(_f32(m, name))
+    return out
+
+
+def gt_project(depths, inv_intrinsics, poses, intrinsics):
+    """depths [B,H,W] -> cam_pix [B,4,H*W] = u, v, z, c3 (the staged warp)"""
+    B, H, W = depths.shape
+    iK, T, K = _gt_mats(B, inv_intrinsics=inv_intrinsics, poses=poses, intrinsics=intrinsics)
+    d = _f32(depths, "depths")
+    cam_pix = torch.empty((B, 4, H * W), dtype=torch.float32, device=depths.device)
+    _lib.check(_lib.load().fp_gt_project(d, iK, T, K, B, H, W, _chk(cam_pix), stream()), "fp_gt_project")
+    return cam_pix
+
+
+def gt_project_to_world(depths, inv_intrinsics):
+    """depths [B,H,W] -> world points [B,4,H*W] = (invK[:3,:3] . (x, y, 1)) * d and the homogeneous (d > 0)"""
+    B, H, W = depths.shape
+    (iK,) = _gt_mats(B, inv_intrinsics=inv_intrinsics)
+    d = _f32(depths, "depths")
+    world = torch.empty((B, 4, H * W), dtype=torch.float32, device=depths.device)
+    _lib.check(_lib.load().fp_gt_project_to_world(d, iK, B, H, W, _chk(world), stream()), "fp_gt_project_to_world")
+    return world
+
+
+def gt_project_to_camera(world, poses, intrinsics):
+    """world points [B,4,N] -> cam_pix [B,4,N] = K . (T . world) with u, v divided by (z + 1e-7)"""
+    B, four, N = world.shape
+    if four != 4:
+        raise RuntimeError("footprints_amd.ops.gt_project_to_camera: world points must be [B, 4, N]")
+    T, K = _gt_mats(B, poses=poses, intrinsics=intrinsics)
+    w = _f32(world, "world points")
+    cam_pix = torch.empty((B, 4, N), dtype=torch.float32, device=world.device)
+    _lib.check(_lib.load().fp_gt_project_to_camera(w, T, K, B, N, _chk(cam_pix), stream()), "fp_gt_project_to_camera")
+    return cam_pix
+
+
+def gt_splat(cam_pix, H, W, keys=None):
+    """cam_pix [B,4,H*W] -> keys [B,H*W] (highest source index wins a pixel)"""
+    B = cam_pix.shape[0]
+    if tuple(cam_pix.shape) != (B, 4, H * W):
+        raise RuntimeError("footprints_amd.ops.gt_splat: cam_pix must be [B, 4, H*W]")
+    c = _f32(cam_pix, "cam_pix")
+    keys = gt_keys(B, H, W, cam_pix.device) if keys is None else keys
+    _lib.check(_lib.load().fp_gt_splat(c, B, H, W, _typed(keys, torch.int64, "keys"), keys.numel() * 8, stream()), "fp_gt_splat")
+    return keys
+
+
+def gt_warp_splat(depths, inv_intrinsics, poses, intrinsics, keys=None):
+    """the production path: warp and splat in one kernel, depths [B,H,W] -> keys [B,H*W]"""
+    B, H, W = depths.shape
+    iK, T, K = _gt_mats(B, inv_intrinsics=inv_intrinsics, poses=poses, intrinsics=intrinsics)
+    d = _f32(depths, "depths")
+    keys = gt_keys(B, H, W, depths.device) if keys is None else keys
+    _lib.check(_lib.load().fp_gt_warp_splat(d, iK, T, K, B, H, W, _typed(keys, torch.int64, "keys"), keys.numel() * 8, stream()),
+               "fp_gt_warp_splat")
+    return keys
+
+
+def gt_aggregate(keys, H, W, robust, want_projections=False):
+    """keys [B,H*W] -> median [H,W] (and the per-frame projections [B,H,W] when asked)"""
+    B = keys.shape[0]
+    if keys.numel() != B * H * W:
+        raise RuntimeError("footprints_amd.ops.gt_aggregate: keys must be [B, H*W]")
+    k = _typed(keys, torch.int64, "keys")
+    median = torch.empty((H, W), dtype=torch.float32, device=keys.device)
+    proj = torch.empty((B, H, W), dtype=torch.float32, device=keys.device) if want_projections else None
+    _lib.check(_lib.load().fp_gt_aggregate(k, B, H, W, int(bool(robust)), _chk(median), _chk(proj) if proj is not None else None, stream()),
+               "fp_gt_aggregate")
+    return (median, proj) if want_projections else median
+
+
+def gt_moving_mask(disparity, flow, inv_intrinsics, pose, intrinsics, fx_baseline):
+    """disparity [H,W], flow [2,H,W], matrices [1,4,4] -> bool [H,W]"""
+    H, W = disparity.shape[-2:]
+    if disparity.numel() != H * W or tuple(flow.shape) != (2, H, W):
+        raise RuntimeError("footprints_amd.ops.gt_moving_mask: disparity must be [H, W] and flow [2, H, W]")
+    iK, T, K = _gt_mats(1, inv_intrinsics=inv_intrinsics, pose=pose, intrinsics=intrinsics)
+    d, f = _f32(disparity, "disparity"), _f32(flow, "flow")
+    mask = torch.empty((H, W), dtype=torch.uint8, device=disparity.device)
+    _lib.check(_lib.load().fp_gt_moving_mask(d, f, iK, T, K, float(fx_baseline), H, W, _chk(mask), stream()), "fp_gt_moving_mask")
+    return mask.view(torch.bool)
+
+
+def gt_ground_count(ground_seg, threshold):
+    """number of pixels with ground_seg > threshold (int32 device scalar)"""
+    H, W = ground_seg.shape
+    g = _f32(ground_seg, "ground_seg")
+    count = torch.empty(1, dtype=torch.int32, device=ground_seg.device)
+    _lib.check(_lib.load().fp_gt_ground_count(g, float(threshold), H, W, _chk(count), stream()), "fp_gt_ground_count")
+    return count
+
+
+def gt_plane_score(world, ground_seg, threshold, samples, want_inlier_mask=False):
+    """world [4,H*W] (one frame of gt_project_to_world), ground_seg [H,W], samples int32 [C,3] (indices into the ground pixels in raster order) -> dict of sample_pix [C,3],
+    planes float64 [C,4], counts int32 [C], best_plane float64 [4], best int32 [2] = (index, count), inlier_mask bool [H,W] or None"""
+    H, W = ground_seg.shape
+    if world.numel() != 4 * H * W or samples.dim() != 2 or samples.shape[1] != 3:
+        raise RuntimeError("footprints_amd.ops.gt_plane_score: world must be [4, H*W] and samples [C, 3]")
+    d, g, s = _f32(world, "world points"), _f32(ground_seg, "ground_seg"), _typed(samples, torch.int32, "samples")
+    C_, dev = samples.shape[0], world.device
+    out = {"sample_pix": torch.empty((C_, 3), dtype=torch.int32, device=dev), "planes": torch.empty((C_, 4), dtype=torch.float64, device=dev),
+           "counts": torch.empty(C_, dtype=torch.int32, device=dev), "best_plane": torch.empty(4, dtype=torch.float64, device=dev),
+           "best": torch.empty(2, dtype=torch.int32, device=dev),
+           "inlier_mask": torch.empty((H, W), dtype=torch.uint8, device=dev) if want_inlier_mask else None}
+    _lib.check(_lib.load().fp_gt_plane_score(d, g, float(threshold), s, C_, H, W, _chk(out["sample_pix"]), _chk(out["planes"]),
+                                             _chk(out["counts"]), _chk(out["best_plane"]), _chk(out["best"]),
+                                             _chk(out["inlier_mask"]) if want_inlier_mask else None, stream()), "fp_gt_plane_score")
+    if want_inlier_mask:
+        out["inlier_mask"] = out["inlier_mask"].view(torch.bool)
+    return out
+
+
+def gt_flatten_splat(world, ground_seg, threshold, intrinsics, plane, keys=None, want_cam_pix=False):
+    """non-ground points of `world` [4,H*W] flattened onto `plane` (float64 [4] on the device), 8 x 8 offset copies projected and splatted -> keys [1,H*W]
+    (and the copies' coordinates [4, 64*H*W] when asked: tests only)"""
+    H, W = ground_seg.shape
+    if world.numel() != 4 * H * W:
+        raise RuntimeError("footprints_amd.ops.gt_flatten_splat: world must be [4, H*W]")
+    (K,) = _gt_mats(1, intrinsics=intrinsics)
+    d, g, pl = _f32(world, "world points"), _f32(ground_seg, "ground_seg"), _typed(plane, torch.float64, "plane")
+    if plane.numel() != 4:
+        raise RuntimeError("footprints_amd.ops.gt_flatten_splat: plane must hold 4 float64")
+    keys = gt_keys(1, H, W, world.device) if keys is None else keys
+    cam_pix = torch.empty((4, 64 * H * W), dtype=torch.float32, device=world.device) if want_cam_pix else None
+    _lib.check(_lib.load().fp_gt_flatten_splat(d, g, float(threshold), K, pl, H, W, _typed(keys, torch.int64, "keys"), keys.numel() * 8,
+                                               _chk(cam_pix) if want_cam_pix else None, stream()), "fp_gt_flatten_splat")
+    return (keys, cam_pix) if want_cam_pix else keys
+
+
+def gt_depth_mask(keys, depth, ground_seg, want_projection=False):
+    """keys [1,H*W] of gt_flatten_splat -> bool [H,W] mask of untraversable pixels (and the splatted projection when asked)"""
+    H, W = ground_seg.shape
+    if depth.numel() != H * W or keys.numel() < H * W:
+        raise RuntimeError("footprints_amd.ops.gt_depth_mask: depth must be [H, W] and keys hold H*W entries")
+    k, d, g = _typed(keys, torch.int64, "keys"), _f32(depth, "depth"), _f32(ground_seg, "ground_seg")
+    mask = torch.empty((H, W), dtype=torch.uint8, device=depth.device)
+    proj = torch.empty((H, W), dtype=torch.float32, device=depth.device) if want_projection else None
+    _lib.check(_lib.load().fp_gt_depth_mask(k, d, g, H, W, _chk(mask), _chk(proj) if want_projection else None, stream()), "fp_gt_depth_mask")
+    return (mask.view(torch.bool), proj) if want_projection else mask.view(torch.bool)

@@ -1,0 +1,283 @@
+"""Generators of the training labels (reference preprocessing/ground_truth_generation/ground_truth_generator.py): hidden ground depth
+(warp every source frame into the target camera, splat, per-pixel median), moving-object masks and depth masks.
+
+The compute between "frames loaded" and "label saved" runs in HIP kernels (csrc/gt_gen.hip).  The file readers are out of scope, so
+each generator takes a `loader` instead of constructing one.  A loader has what the reference's KITTILoader / MatterportLoader have:
+
+* ``load_data(...)`` -> dict with ``depths`` and ``ground_segs`` [B,H,W] float32 tensors, ``poses`` / ``intrinsics`` /
+  ``inv_intrinsics`` [B,4,4] float32 tensors (camera-to-world poses), on the host, and for KITTI ``sides`` (list of 'image_02' / 'image_03');
+* ``load_frame_data(...)`` -> for KITTI a dict with ``pose`` (4x4 array), ``disparity`` and ``ground_seg`` [H,W] float32 arrays and, with
+  ``load_flow=True``, ``flow`` [2,H,W]; ``None`` for a frame that does not exist; for Matterport the tuple
+  ``(ground_seg, depth, pose, K)``;
+* KITTI: ``K`` / ``invK`` (4x4 arrays), ``stereo_baseline``, ``buffer`` and ``purge_buffer()``; Matterport: ``pose_tracker``.
+
+`process_data` takes arrays (uploaded as the reference uploads them) or CUDA tensors; CPU tensors are refused: there is no CPU path.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from ... import ops
+from .geometry import BatchProjector, draw_samples, require_cuda
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("footprints_amd.preprocessing.ground_truth_generation: needs a GPU (no CPU path in the product)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _upload(x, name):
+    """numpy array -> float32 CUDA tensor (what the reference's `torch.from_numpy(x).float().cuda()` does); CUDA tensors pass"""
+    if isinstance(x, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(_device())
+    t = require_cuda(x, name)
+    if t.dtype != torch.float32:
+        raise RuntimeError("footprints_amd.preprocessing.ground_truth_generation: %s must be float32" % name)
+    return t
+
+
+def readlines(filename):
+    with open(filename, "r") as fh:
+        return fh.read().splitlines()
+
+
+class GroundTruthGenerator:
+    """Generates the ground truth depths of both visible and hidden ground"""
+
+    height, width = None, None
+
+    def __init__(self, opts, loader, training_datapath=None):
+        self.opts = opts
+        self.loader = loader
+        self.training_datapath = training_datapath
+        self.filenames = []
+        if getattr(opts, "textfile", None):
+            self.filenames = sorted(readlines(opts.textfile))
+            end = None if opts.idx_end == -1 else opts.idx_end
+            self.filenames = self.filenames[opts.idx_start:end]
+        self.projector = BatchProjector(self.height, self.width)
+        self.save_folder = opts.save_folder_name
+        if self.save_folder is None:
+            self.save_folder = "hidden_depths"
+        self.footprint_threshold = opts.footprint_threshold
+
+    def load_data(self, idx, filename):
+        raise NotImplementedError
+
+    def save_result(self, result, savepath, filename, save_viz=False):
+        """<savepath>/data/<filename, zero-filled to 10>.npy, the layout the datasets read.  Visualisation images are not written."""
+        _savepath = os.path.join(savepath, "data")
+        os.makedirs(_savepath, exist_ok=True)
+        np.save(os.path.join(_savepath, "{}.npy".format(str(filename).zfill(10))), result)
+
+    def compute_depth_mask(self, depth, ground_seg, K, invK, samples=None):
+        """The depth mask of *untraversable* pixels: depth [1,H,W], ground_seg [H,W], K / invK [1,4,4] -> bool array [H,W].
+
+        Back-project, fit the ground plane (geometry.fit_plane: sample indices from the host's numpy.random stream, planes and inlier
+        counts on the device), move every non-ground point onto the plane, splat its 8 x 8 offset copies and keep the pixels whose
+        splatted depth is within 10 % of the visible depth, closer than 30 m and not ground.  The copies are never stored."""
+        depth, ground_seg = _upload(depth, "depth"), _upload(ground_seg, "ground_seg")
+        K, invK = _upload(K, "K"), _upload(invK, "invK")
+        H, W = ground_seg.shape
+        world = self.projector.project_to_world(depth.reshape(1, H, W), invK)[0]
+        if samples is None:
+            samples = draw_samples(int(ops.gt_ground_count(ground_seg, self.footprint_threshold).item()))
+        if not torch.is_tensor(samples):
+            samples = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int32)).to(world.device)
+        fit = ops.gt_plane_score(world, ground_seg, self.footprint_threshold, samples)
+        keys = ops.gt_flatten_splat(world, ground_seg, self.footprint_threshold, K, fit["best_plane"])
+        return ops.gt_depth_mask(keys, depth, ground_seg).cpu().numpy()
+
+    def process_data(self, data, robust_aggregation=True):
+        """data: `depths` [B,H,W], `poses`, `intrinsics`, `inv_intrinsics` [B,4,4] on the device -> the [H,W] float32 array that is
+        saved: per pixel the median of the depths the source frames project there (0 unless more than 2 frames agree on the pixel
+        when `robust_aggregation`, more than 0 otherwise)"""
+        keys = self.projector.warp_splat(data["depths"], data["inv_intrinsics"], data["poses"], data["intrinsics"])
+        return ops.gt_aggregate(keys, self.height, self.width, robust_aggregation).cpu().numpy()
+
+    def run(self):
+        for i, filename in enumerate(self.filenames):
+            data = self.load_data(i, filename)
+            result = self.process_data(data, robust_aggregation=self.robust_aggregation)
+            self.save_result(result, filename)
+
+
+def _side(side):
+    return "image_02" if side == "l" else "image_03"
+
+
+class KITTIGroundTruthGenerator(GroundTruthGenerator):
+
+    height, width = 192, 640
+
+    def __init__(self, opts, loader, training_datapath=None):
+        super().__init__(opts, loader, training_datapath)
+        self.sequence_in_buffer = None
+        self.robust_aggregation = True
+
+    def _keep_buffer_small(self, sequence):
+        if sequence != self.sequence_in_buffer:
+            self.loader.purge_buffer()
+            self.sequence_in_buffer = sequence
+        if len(self.loader.buffer) > 1000:
+            self.loader.purge_buffer()
+
+    def load_data(self, idx, filename):
+        sequence, frame, side = filename.split(" ")
+        self._keep_buffer_small(sequence)
+        side = _side(side)
+        stereo_baseline = self.loader.stereo_baseline * (1.0 if side == "image_02" else -1.0)
+        data = self.loader.load_data(sequence, int(frame))
+        # only the depths of ground pixels are projected (a product on the host, where the loader's tensors live)
+        depths = data["depths"] * data["ground_segs"]
+        # relative poses, and the baseline for the cameras of the other side
+        base_pose = self.loader.load_frame_data(sequence, frame, side)["pose"]
+        base_pose = torch.from_numpy(np.linalg.pinv(base_pose)).float().unsqueeze(0)
+        poses = torch.matmul(base_pose, data["poses"])
+        for frame_num in range(len(poses)):
+            if data["sides"][frame_num] != side:
+                poses[frame_num, 0, 3] += stereo_baseline
+        dev = _device()
+        out = dict(data)
+        out.update(depths=depths.float().to(dev), poses=poses.to(dev), intrinsics=data["intrinsics"].float().to(dev),
+                   inv_intrinsics=data["inv_intrinsics"].float().to(dev))
+        return out
+
+    def save_result(self, result, filename, save_viz=False):
+        sequence, frame, side = filename.split(" ")
+        savepath = os.path.join(self.training_datapath, self.save_folder, sequence, _side(side))
+        super().save_result(result, savepath, frame, save_viz=save_viz)
+
+
+class KITTIMovingObjectDetector(KITTIGroundTruthGenerator):
+
+    def __init__(self, opts, loader, training_datapath=None):
+        super().__init__(opts, loader, training_datapath)
+        if opts.save_folder_name is None:
+            self.save_folder = "moving_object_masks"
+        self.robust_aggregation = None
+        self.K = np.asarray(loader.K, np.float32)[None]
+        self.invK = np.asarray(loader.invK, np.float32)[None]
+
+    def load_data(self, idx, filename):
+        sequence, frame, side = filename.split(" ")
+        self._keep_buffer_small(sequence)
+        side = _side(side)
+        base_data = self.loader.load_frame_data(sequence, int(frame), side, load_flow=True)
+        # the previous frame in time; the next one for the first frame of a sequence
+        lookup_data = self.loader.load_frame_data(sequence, int(frame) - 1, side, load_flow=True)
+        if lookup_data is None:
+            lookup_data = self.loader.load_frame_data(sequence, int(frame) + 1, side, load_flow=True)
+        return {"base_data": base_data, "lookup_data": lookup_data}
+
+    def process_data(self, data, robust_aggregation=None):
+        """-> bool array [H,W]: pixels whose optical flow differs by more than 3 pixels from the flow the camera motion induces"""
+        base_data, lookup_data = data["base_data"], data["lookup_data"]
+        T = np.matmul(np.linalg.pinv(lookup_data["pose"]), base_data["pose"]).astype(np.float32)[None]
+        disparity, flow = _upload(base_data["disparity"], "disparity"), _upload(base_data["flow"], "flow")
+        fx_baseline = float(self.K[0, 0, 0]) * self.loader.stereo_baseline
+        mask = ops.gt_moving_mask(disparity, flow, _upload(self.invK, "invK"), _upload(T, "T"), _upload(self.K, "K"), fx_baseline)
+        return mask.cpu().numpy()
+
+
+class _DepthMasking:
+    """what the two depth-mask generators share: fewer than 100 ground pixels give an all-zero mask"""
+
+    def _mask_or_zeros(self, depth, ground_seg, K, invK):
+        ground_seg = _upload(ground_seg, "ground_seg")
+        if int(ops.gt_ground_count(ground_seg, self.footprint_threshold).item()) < 100:
+            return np.zeros([self.height, self.width])
+        return self.compute_depth_mask(depth, ground_seg, K, invK)
+
+
+class KITTIDepthMaskingGenerator(_DepthMasking, KITTIGroundTruthGenerator):
+    """Mask of *untraversable* pixels from the visible depth map and the ground segmentation"""
+
+    def __init__(self, opts, loader, training_datapath=None):
+        super().__init__(opts, loader, training_datapath)
+        if opts.save_folder_name is None:
+            self.save_folder = "depth_masks"
+        self.robust_aggregation = None
+        self.K = np.asarray(loader.K, np.float32)[None]
+        self.invK = np.asarray(loader.invK, np.float32)[None]
+
+    def load_data(self, idx, filename):
+        sequence, frame, side = filename.split(" ")
+        return self.loader.load_frame_data(sequence, int(frame), _side(side), use_buffer=False, threshold_ground=False)
+
+    def process_data(self, data, robust_aggregation=None):
+        disparity = _upload(data["disparity"], "disparity")
+        # depth = fx * baseline / disparity, on the host scalar and the device array like the reference's expression
+        fb = torch.tensor(float(self.K[0, 0, 0]) * self.loader.stereo_baseline, dtype=torch.float32, device=disparity.device)
+        return self._mask_or_zeros((fb / disparity).unsqueeze(0), data["ground_seg"], self.K, self.invK)
+
+
+class MatterportGroundTruthGenerator(GroundTruthGenerator):
+
+    height, width = 480, 640
+
+    def __init__(self, opts, loader, training_datapath=None):
+        super().__init__(opts, loader, training_datapath)
+        self.robust_aggregation = False
+
+    def load_data(self, idx, filename):
+        scan, pos, height, direction = filename.split()
+        data = self.loader.load_data(scan, pos, height, direction)
+        depths = data["depths"] * data["ground_segs"]
+        # only the cameras close to the target one
+        base_pose = self.loader.pose_tracker[(pos, height, direction)]
+        inv_pose = torch.from_numpy(np.linalg.pinv(base_pose)).float().unsqueeze(0)
+        base_pose = torch.from_numpy(base_pose).float().unsqueeze(0)
+        poses = data["poses"]
+        close = (torch.abs(base_pose[:, 0, 3] - poses[:, 0, 3]) < 10) * (torch.abs(base_pose[:, 1, 3] - poses[:, 1, 3]) < 10) * \
+                (torch.abs(base_pose[:, 2, 3] - poses[:, 2, 3]) < 1)
+        dev = _device()
+        out = dict(data)
+        out.update(depths=depths[close].float().to(dev), poses=torch.matmul(inv_pose, poses[close]).to(dev),
+                   intrinsics=data["intrinsics"][close].float().to(dev), inv_intrinsics=data["inv_intrinsics"][close].float().to(dev))
+        return out
+
+    def save_result(self, result, filename, save_viz=False):
+        scan, pos, height, direction = filename.split()
+        savepath = os.path.join(self.training_datapath, self.save_folder, scan)
+        super().save_result(result, savepath, "{}_{}_{}".format(pos, height, direction), save_viz=save_viz)
+
+
+class MatterportDepthMaskingGenerator(_DepthMasking, MatterportGroundTruthGenerator):
+    """Mask of *untraversable* pixels from the visible depth map and the ground segmentation"""
+
+    def __init__(self, opts, loader, training_datapath=None):
+        super().__init__(opts, loader, training_datapath)
+        if opts.save_folder_name is None:
+            self.save_folder = "depth_masks"
+        self.robust_aggregation = None
+
+    def load_data(self, idx, filename):
+        scan, pos, height, direction = filename.split()
+        ground_seg, depth, _, K = self.loader.load_frame_data(scan, pos, height, direction)
+        return {"depth": np.asarray(depth, np.float32)[None], "ground_seg": ground_seg, "intrinsics": np.asarray(K, np.float32)[None],
+                "inv_intrinsics": np.linalg.pinv(K).astype(np.float32)[None]}
+
+    def process_data(self, data, robust_aggregation=None):
+        return self._mask_or_zeros(data["depth"], data["ground_seg"], data["intrinsics"], data["inv_intrinsics"])
+
+
+def get_options(argv=None):
+    """the reference's command line: same flags, same defaults"""
+    parser = argparse.ArgumentParser(description="process frames to generate footprint training data")
+    parser.add_argument("--config_path", type=str, default="paths.yaml", help="path to config file containing dataset information")
+    parser.add_argument("--type", type=str, choices=["hidden_depths", "moving_objects", "depth_masks"],
+                        help="type of data to compute: hidden depths (reprojected from other views), moving object masks or depth masks "
+                             "(untraversable pixels)")
+    parser.add_argument("--data_type", type=str, choices=["kitti", "matterport"])
+    parser.add_argument("--save_folder_name", type=str,
+                        help="folder name to save to; defaults to 'hidden_depths', 'moving_object_masks' or 'depth_masks' by type")
+    parser.add_argument("--save_visualisations", action="store_true", help="accepted for compatibility: images are not written")
+    parser.add_argument("--textfile", type=str, help="textfile containing frames to be computed")
+    parser.add_argument("--idx_start", type=int, default=0, help="first index of the textfile to process (splitting work across GPUs)")
+    parser.add_argument("--idx_end", type=int, default=-1, help="index after the last one to process, -1 for all")
+    parser.add_argument("--footprint_threshold", type=float, default=0.75, help="threshold for ground segmentation")
+    return parser.parse_args(argv)

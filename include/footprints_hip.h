@@ -376,6 +376,50 @@ int fp_eval_mask_counts(const void* pred, int32_t pred_is_half, const float* gt,
 int fp_eval_depth_sums(const void* pred_disp, int32_t pred_is_half, const float* gt, int32_t B, int64_t pixels, int64_t pred_stride,
                        double min_depth, double max_depth, double clip_min, double clip_max, double* sums, fp_stream_t stream);
 
+/* ---- training-label generation (reference preprocessing/ground_truth_generation/{geometry,ground_truth_generator}.py) -------------
+ * Matrices are row-major fp32 4 x 4 per frame ([B][16]); depths fp32 [B][H*W]; cam_pix fp32 [B][4][H*W] = u, v, z, c3.
+ * Warp: w = (invK[:3,:3] . (x, y, 1)) * d, m = (d > 0); c = K . (T . (w, m)); u = c0 / (c2 + 1e-7f), v = c1 / (c2 + 1e-7f), z = c2.  An
+ * infinite depth is not special-cased: it gives NaN coordinates and an invalid point.
+ * Splat: a point is valid when u > 0 && u < W && v > 0 && v < H && z > 0 && c3 > 0; it writes z to pixel (trunc(v), trunc(u)) of its
+ * frame, and of several valid points in one pixel the one with the HIGHEST source index wins.  `keys` is the device-only plane that
+ * decides this: uint64 [B][H*W], (source_index + 1) << 32 | float_bits(z), fp_gt_workspace(B, H, W) bytes; the splats clear it first.
+ * Aggregate: n = frames with depth > 0 at the pixel; 0 unless n > 2 (robust) / n > 0, else (s[(n-1)/2] + s[n/2]) * 0.5f of the sorted
+ * positive depths (= numpy.ma.median(...).filled(0)); `projections` (optional) receives the per-frame depths [B][H*W].
+ * All of them refuse B > 512 and H * W * 64 >= 2^32 - 1 (the source index of the depth mask's 64 offset copies).
+ * fp_gt_workspace is host-only: bytes of key plane, or -1 with the error string set. */
+int64_t fp_gt_workspace(int32_t B, int32_t H, int32_t W);
+int fp_gt_project(const float* depths, const float* inv_intrinsics, const float* poses, const float* intrinsics, int32_t B, int32_t H,
+                  int32_t W, float* cam_pix, fp_stream_t stream);
+/* the two halves of the warp on their own (BatchProjector.project_to_world / project_to_camera): world fp32 [B][4][points] = x, y, z, m */
+int fp_gt_project_to_world(const float* depths, const float* inv_intrinsics, int32_t B, int32_t H, int32_t W, float* world,
+                           fp_stream_t stream);
+int fp_gt_project_to_camera(const float* world, const float* poses, const float* intrinsics, int32_t B, int64_t points, float* cam_pix,
+                            fp_stream_t stream);
+int fp_gt_splat(const float* cam_pix, int32_t B, int32_t H, int32_t W, uint64_t* keys, int64_t keys_bytes, fp_stream_t stream);
+int fp_gt_warp_splat(const float* depths, const float* inv_intrinsics, const float* poses, const float* intrinsics, int32_t B, int32_t H,
+                     int32_t W, uint64_t* keys, int64_t keys_bytes, fp_stream_t stream);
+int fp_gt_aggregate(const uint64_t* keys, int32_t B, int32_t H, int32_t W, int32_t robust, float* median, float* projections,
+                    fp_stream_t stream);
+/* moving-object mask of one frame: depth = (float)fx_baseline / disparity, warp by `pose`, induced flow (u - x, v - y) against
+ * flow fp32 [2][H*W]; mask uint8 [H*W] = sqrt(d0^2 + d1^2) > 3 (float64 on the fp32 differences; NaN compares false) */
+int fp_gt_moving_mask(const float* disparity, const float* flow, const float* inv_intrinsics, const float* pose, const float* intrinsics,
+                      double fx_baseline, int32_t H, int32_t W, uint8_t* mask, fp_stream_t stream);
+/* depth mask, on the back-projected frame `world` (fp32 [4][H*W] of fp_gt_project_to_world).  fp_gt_ground_count: count[0] = pixels with ground_seg > threshold.  fp_gt_plane_score: `samples` int32 [C][3] index the
+ * ground pixels in raster order (the host draws them); sample_pix [C][3] receives their pixel indices, planes float64 [C][4] the planes
+ * (p1 - p0) x (p2 - p0), d = -n . p0 through the sampled world points (all zero for a degenerate sample, which scores 0), counts [C]
+ * the ground points with |distance| < 0.05 in float64, best_plane [4] / best [2] = {index, count} the first candidate with the strictly
+ * largest count ({-1, 0} when every count is 0), inlier_mask (optional) uint8 [H*W] its inliers.  fp_gt_flatten_splat: every non-ground
+ * point moved onto `plane` (device pointer, 4 float64), copied to the 8 x 8 offsets numpy.arange(-0.1, 0.1, 0.025) along n x (0,0,1) and
+ * n x (n x (0,0,1)), projected with K and splatted with source index k * H*W + p into keys [H*W]; cam_pix (optional, for tests) fp32
+ * [4][64 * H*W] receives the copies' coordinates (NaN for ground pixels).  fp_gt_depth_mask: mask uint8 [H*W] = projection > 0 &&
+ * ground_seg < 0.5 && |projection - depth| / (depth + 1e-7) < 0.10 && projection < 30 && depth > 0; projection (optional) fp32 [H*W]. */
+int fp_gt_ground_count(const float* ground_seg, double threshold, int32_t H, int32_t W, int32_t* count, fp_stream_t stream);
+int fp_gt_plane_score(const float* world, const float* ground_seg, double threshold, const int32_t* samples, int32_t C, int32_t H, int32_t W, int32_t* sample_pix, double* planes, int32_t* counts, double* best_plane,
+                      int32_t* best, uint8_t* inlier_mask, fp_stream_t stream);
+int fp_gt_flatten_splat(const float* world, const float* ground_seg, double threshold, const float* intrinsics, const double* plane, int32_t H, int32_t W, uint64_t* keys, int64_t keys_bytes, float* cam_pix, fp_stream_t stream);
+int fp_gt_depth_mask(const uint64_t* keys, const float* depth, const float* ground_seg, int32_t H, int32_t W, uint8_t* mask,
+                     float* projection, fp_stream_t stream);
+
 /* ---- maxpool 3x3 stride 2 pad 1 (encoder.maxpool, network.py:41) ---------- */
 int fp_maxpool_fwd(const float* x, float* y, uint8_t* argmax, int32_t N, int32_t H, int32_t W, int32_t C,
                    const fp_aux* aux, fp_stream_t stream);
