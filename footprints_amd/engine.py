@@ -25,6 +25,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import weight_layouts as WL
 from ._format import operand_format
 
 # Concurrency: the two decoders are independent, and every weight gradient is off the critical dgrad chain.
@@ -65,12 +66,16 @@ _LAZY32 = bool(int(os.environ.get("FP_PACK_LAZY32", "1")))     # 0: every fp32 p
 _PACK_SIDE_WGS = int(os.environ.get("FP_PACK_SIDE_WGS", "0"))        # workgroups of the side-stream weight repack (0 = one per tile)
 _PACK_DGRAD_LATE = bool(int(os.environ.get("FP_PACK_DGRAD_LATE", "0")))   # 1: the data-gradient layouts are repacked under the decoders' forward instead of the encoder's
 
+FLAGS = WL.Flags(bf3=_BF3, hp=_HP, hp_igemm=_HP_IGEMM, bf3_igemm=_BF3_IGEMM, phase=_PHASE, hp_stem=_HP_STEM)
+# kernel families of a convolution / data-gradient launch (_route)
+TILE_HP, TILE_BF3, IGEMM_BF3, IGEMM_HP, IGEMM_F32 = "tile-hp", "tile-bf3", "igemm-bf3", "igemm-hp", "igemm-f32"
+
 SCALE_KEYS = ("1/8", "1/4", "1/2", "1/1")
 _ALL_SCALES = frozenset(range(4))
 
 
 class ConvRec:
-    """One convolution: parameters + packed copies for the implicit-GEMM kernels."""
+    """One convolution: parameters + packed copies for the implicit-GEMM kernels (self.lay)."""
 
     def __init__(self, name, conv, stem=False, head=False):
         self.name = name
@@ -80,23 +85,16 @@ class ConvRec:
         self.stride = conv.stride[0]
         self.pad = self.K // 2
         self.stem, self.head = stem, head
-        self.wp = None    # forward packing
-        self.wpd = None   # dgrad packing
-        self.up2 = None   # (C0, C1) for convs fed by cat[nearest_x2(low C0), skip C1]: phase-decomposed packings below
-        self.wph = self.wsk = self.wdu = self.wds = None   # fwd phase / fwd skip slice / dgrad 4x4 s2 / dgrad skip slice
-        # bf16x3-split copies (3x3 stride-1 convs): forward, dgrad, and the skip-slice pair of the upsample convs
-        self.bf3 = _BF3 and self.K == 3 and self.stride == 1 and not stem and not head
-        self.wp3 = self.wpd3 = self.wsk3 = self.wds3 = self.wph3 = self.wdu3 = None
-        # fp16-pair copies of the same four tile packings, and the slot holding max |w| they were scaled by
-        self.hp = self.bf3 and _HP
-        # ... and of the flattened-kernel packings for the convolutions the tile kernel does not take (3x3 stride 2, 1x1): fp_conv_igemm_hp
-        self.hp_ig = _HP_IGEMM and not self.bf3 and not stem and not head and self.K in (1, 3)
-        # ... or, with the exact operand format, bf16x3 copies of the same packings in the wp3 / wpd3 slots: fp_conv_igemm_bf3
-        self.bf3_ig = _BF3_IGEMM and not self.bf3 and not stem and not head and self.K in (1, 3) and self.Cin % 4 == 0
-        self.hp_f = self.hp_d = self.hp_sk = self.hp_ds = self.hp_ph = self.hp_du = None      # + phase forward / phase data-gradient
-        self.wslot = None
+        self.up2 = None   # (C0, C1) for convs fed by cat[nearest_x2(low C0), skip C1]: phase-decomposed packings (DecoderRec)
+        # split copies: bf3 / hp = for the tile kernel (3x3 stride 1), hp_ig / bf3_ig = for the flattened kernel (3x3 stride 2, 1x1)
+        self.bf3, self.hp, self.hp_ig, self.bf3_ig = WL.classify(self.facts(), FLAGS)
+        self.lay = None      # packed copies by role and format (weight_layouts.py; Engine._alloc_packed)
+        self.folded = None   # ... of the BN-folded weights self.fw: a second `fwd` role (Engine._build_fold)
         self.gw = None    # gradient views (flat grad buffer)
         self.gb = None
+
+    def facts(self):
+        return WL.Facts(self.Cout, self.Cin, self.K, self.stride, self.stem, self.head, self.up2)
 
 
 class BNRec:
@@ -404,57 +402,18 @@ class Engine:
         return out
 
     def _alloc_packed(self):
-        total = 0
-        plan = []
-        for c in self.all_convs():
-            nf = ops.packed_weight_elems(c.Cout, c.Cin, c.K, False, c.stem)
-            nd = 0 if c.stem else ops.packed_weight_elems(c.Cout, c.Cin, c.K, True, False)
-            ex = [0, 0, 0, 0]
-            if c.up2 is not None:
-                C0, C1 = c.up2
-                ex = [ops.up2_packed_weight_elems(c.Cout, C0), ops.packed_weight_elems(c.Cout, C1, 3) if C1 else 0,
-                      ops.up2_packed_weight_elems(C0, c.Cout), ops.packed_weight_elems(c.Cout, C1, 3, True) if C1 else 0]
-            if c.bf3:
-                if c.up2 is None:
-                    ex += [ops.packed_weight_elems_bf3(c.Cout, c.Cin, 3, False), ops.packed_weight_elems_bf3(c.Cout, c.Cin, 3, True), 0, 0, 0, 0]
-                else:
-                    C0, C1 = c.up2
-                    ex += [ops.packed_weight_elems_bf3(c.Cout, c.Cin, 3, False) if C1 else 0, 0,      # full concat pack: small images
-                           ops.packed_weight_elems_bf3(c.Cout, C1, 3, False) if C1 else 0,
-                           ops.packed_weight_elems_bf3(c.Cout, C1, 3, True) if C1 else 0, ops.up2_packed_weight_elems(c.Cout, C0) * 3 // 2,
-                           ops.up2_packed_weight_elems(C0, c.Cout) * 3 // 2]
-            elif c.bf3_ig:           # stride-2 3x3 / 1x1: the flattened kernel's bf16x3 packings live in the wp3 / wpd3 slots
-                ex += [ops.packed_weight_elems_bf3(c.Cout, c.Cin, c.K, False), ops.packed_weight_elems_bf3(c.Cout, c.Cin, c.K, True), 0, 0, 0, 0]
-            else:
-                ex += [0, 0, 0, 0, 0, 0]
-            if c.hp or c.hp_ig:      # fp16-pair copies of the tile packings (same roles as wp3 / wpd3 / wsk3 / wds3)
-                if c.up2 is None:
-                    ex += [ops.packed_weight_elems_hp(c.Cout, c.Cin, c.K, False), ops.packed_weight_elems_hp(c.Cout, c.Cin, c.K, True), 0, 0, 0, 0]
-                else:
-                    C0, C1 = c.up2
-                    ex += [ops.packed_weight_elems_hp(c.Cout, c.Cin, 3, False) if C1 else 0, 0,
-                           ops.packed_weight_elems_hp(c.Cout, C1, 3, False) if C1 else 0, ops.packed_weight_elems_hp(c.Cout, C1, 3, True) if C1 else 0,
-                           ops.up2_packed_weight_elems(c.Cout, C0), ops.up2_packed_weight_elems(C0, c.Cout)]      # two fp16 = one float per weight
-            else:
-                ex += [0, 0, 0, 0, 0, 0]
-            plan.append((c, total, nf, nd, ex))
-            total += nf + nd + sum(ex)
-        self.packed = torch.full((total,), float("nan"), device=self.device)      # see _need32
-        for c, o, nf, nd, ex in plan:
-            c.wp = self.packed[o:o + nf]
-            c.wpd = self.packed[o + nf:o + nf + nd] if nd else None
-            o += nf + nd
-            views = []
-            for n in ex:
-                views.append(self.packed[o:o + n] if n else None)
-                o += n
-            c.wph, c.wsk, c.wdu, c.wds, c.wp3, c.wpd3, c.wsk3, c.wds3, c.wph3, c.wdu3, c.hp_f, c.hp_d, c.hp_sk, c.hp_ds, c.hp_ph, c.hp_du = views
         convs = self.all_convs()
+        plans = [WL.plan(c.facts(), FLAGS) for c in convs]
+        self.packed = torch.full((sum(l.numel for p in plans for l in p if l.pooled),), float("nan"), device=self.device)      # see _need32
         self.wamax = torch.zeros(len(convs) * ops.amax_elems(), dtype=torch.int32, device=self.device)
-        for i, c in enumerate(convs):
-            c.wslot = self.wamax[i * ops.amax_elems():(i + 1) * ops.amax_elems()]
-        if _HP and _HP_STEM:        # the stem's fp16-pair layout (FP_PACK_STEM_HP: 11 K-steps x 2 planes x 64 x 16 halves)
-            self.stem.hp_f = torch.full((11 * 64 * 16,), float("nan"), device=self.device)
+        o = 0
+        for i, (c, p) in enumerate(zip(convs, plans)):
+            c.lay = WL.conv_layouts(self.wamax[i * ops.amax_elems():(i + 1) * ops.amax_elems()])
+            for l in p:
+                t = self.packed[o:o + l.numel] if l.pooled else torch.full((l.numel,), float("nan"), device=self.device)
+                o += l.numel if l.pooled else 0
+                setattr(getattr(c.lay, l.role), l.fmt, t)
+                c.lay.all.append((l, t))
 
     def refresh_packed(self, force=False, overlap=False):
         """repack every convolution's weights if they changed.  overlap=True (Engine.forward only): all but the stem / layer1
@@ -469,51 +428,19 @@ class Engine:
             if _NEED32_SYNC and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
                 torch.cuda.synchronize(self.device)
 
-            def jobs_of(convs):
+            def jobs_of(convs, dgrad=None):
+                """the pack jobs of `convs` in table order; dgrad: only the data-gradient roles' (True) / only the others' (False)"""
                 jobs = []
                 for c in convs:
-                    jobs.append((L.PACK_STEM if c.stem else L.PACK_FWD, c.w.data, c.wp, 0, c.Cin))
-                    if c.stem and c.hp_f is not None:
-                        jobs.append((L.PACK_STEM_HP, c.w.data, c.hp_f, 0, c.Cin, c.wslot))
-                    if c.wpd is not None:
-                        jobs.append((L.PACK_DGRAD, c.w.data, c.wpd, 0, c.Cin))
-                    if c.hp or c.hp_ig:      # fp16-pair packings, scaled by the weight tensor's amax slot
-                        if c.hp_f is not None:
-                            jobs.append((L.PACK_FWD_HP, c.w.data, c.hp_f, 0, c.Cin, c.wslot))
-                        if c.hp_d is not None:
-                            jobs.append((L.PACK_DGRAD_HP, c.w.data, c.hp_d, 0, c.Cin, c.wslot))
-                        if c.hp_sk is not None:
-                            jobs.append((L.PACK_FWD_HP, c.w.data, c.hp_sk, c.up2[0], c.up2[1], c.wslot))
-                            jobs.append((L.PACK_DGRAD_HP, c.w.data, c.hp_ds, c.up2[0], c.up2[1], c.wslot))
-                        if c.hp_ph is not None:
-                            jobs.append((L.PACK_UP2_FWD_HP, c.w.data, c.hp_ph, 0, c.up2[0], c.wslot))
-                            jobs.append((L.PACK_UP2_DGRAD_HP, c.w.data, c.hp_du, 0, c.up2[0], c.wslot))
-                    keep3 = (not c.hp) or self.inference_bf16x2 or not _HP_TILE       # the bf16 tile packings: only where a kernel still reads them
-                    if c.wp3 is not None and keep3:
-                        jobs.append((L.PACK_FWD_BF3, c.w.data, c.wp3, 0, c.Cin))
-                    if c.wpd3 is not None and keep3:
-                        jobs.append((L.PACK_DGRAD_BF3, c.w.data, c.wpd3, 0, c.Cin))
-                    if c.wsk3 is not None and keep3:
-                        jobs.append((L.PACK_FWD_BF3, c.w.data, c.wsk3, c.up2[0], c.up2[1]))
-                        jobs.append((L.PACK_DGRAD_BF3, c.w.data, c.wds3, c.up2[0], c.up2[1]))
-                    if c.wph3 is not None and (not c.hp or not _HP_TILE):
-                        jobs.append((L.PACK_UP2_FWD_BF3, c.w.data, c.wph3, 0, c.up2[0]))
-                        jobs.append((L.PACK_UP2_DGRAD_BF3, c.w.data, c.wdu3, 0, c.up2[0]))
-                    if c.up2 is not None:
-                        C0, C1 = c.up2
-                        jobs.append((L.PACK_UP2_FWD, c.w.data, c.wph, 0, C0))
-                        jobs.append((L.PACK_UP2_DGRAD, c.w.data, c.wdu, 0, C0))
-                        if C1:
-                            jobs.append((L.PACK_FWD, c.w.data, c.wsk, C0, C1))
-                            jobs.append((L.PACK_DGRAD, c.w.data, c.wds, C0, C1))
-                keep = []
-                for j in jobs:
-                    if _LAZY32 and j[0] in (L.PACK_FWD, L.PACK_DGRAD, L.PACK_UP2_FWD, L.PACK_UP2_DGRAD):
-                        self._w32_lazy[j[2].data_ptr()] = j
-                        if j[2].data_ptr() not in self._w32_used:
-                            continue
-                    keep.append(j)
-                return keep
+                    for l, t in WL.pack_jobs(c.lay.all, c.hp, _HP_TILE, self.inference_bf16x2):
+                        j = (l.kind, c.w.data, t, l.c_begin, l.c_count) + ((getattr(c.lay, l.role).wslot,) if l.fmt == "hp" else ())
+                        if l.lazy and _LAZY32:
+                            self._w32_lazy[t.data_ptr()] = j
+                            if t.data_ptr() not in self._w32_used:
+                                continue
+                        if dgrad is None or l.role.endswith("dgrad") == dgrad:
+                            jobs.append(j)
+                return jobs
             # the stem and layer1 (0.2 M parameters) on the calling stream; everything else (31 M) on a side stream under the stem / layer1
             # kernels, in two parts with an event each: the forward layouts (the forward waits for them where layer2 starts, self._pack_ev) and
             # the data-gradient layouts (first read by the decoder backward, self._pack_ev_dgrad).  The side-stream launches are persistent
@@ -521,11 +448,8 @@ class Engine:
             # convolutions from 30 to 142 us (ordered trace, profiles/round4_notes.md)
             first = [self.stem] + [c for blk in self.blocks if blk.Cout == 64 and blk.stride == 1 for c in (blk.c1, blk.c2)]
             rest = [c for c in self.all_convs() if not any(c is f for f in first)]
-            rest_jobs = jobs_of(rest)
-            is_dgrad = lambda j: j[0] in (L.PACK_DGRAD, L.PACK_DGRAD_BF3, L.PACK_DGRAD_HP, L.PACK_UP2_DGRAD, L.PACK_UP2_DGRAD_BF3, L.PACK_UP2_DGRAD_HP)
-            self._pack_table = (ops.build_pack_table(jobs_of(first), self.device), ops.build_pack_table(rest_jobs, self.device),
-                                ops.build_pack_table([j for j in rest_jobs if not is_dgrad(j)], self.device),
-                                ops.build_pack_table([j for j in rest_jobs if is_dgrad(j)], self.device))
+            self._pack_table = tuple(ops.build_pack_table(jobs, self.device)
+                                     for jobs in (jobs_of(first), jobs_of(rest), jobs_of(rest, dgrad=False), jobs_of(rest, dgrad=True)))
             self._pack_table_key = key      # parameters live in self.flat_param: pointers are stable
             ops.bump_alloc_generation()     # the previous tables (device-resident job lists) are gone
         first_t, rest_all, rest_fwd, rest_dgrad = self._pack_table
@@ -533,10 +457,8 @@ class Engine:
             ops.zero_u32(self.wamax)
             ops.pack_weights_amax(first_t)
         ops.pack_weights_batched(first_t)
-        cur = ops.current_stream()
         if self.concurrent and overlap:
-            ops.event_wait(self.wg, self._record(cur))
-            with ops.on_stream(self.wg):
+            def side_part():
                 if _HP:
                     ops.pack_weights_amax(rest_all)
                 ops.pack_weights_batched(rest_fwd, max_wgs=_PACK_SIDE_WGS)
@@ -546,6 +468,7 @@ class Engine:
                 else:
                     ops.pack_weights_batched(rest_dgrad, max_wgs=_PACK_SIDE_WGS)
                     self._pack_ev_dgrad = self._record(self.wg)
+            self._on_side(self.wg, side_part)
         else:
             if _HP:
                 ops.pack_weights_amax(rest_all)
@@ -604,11 +527,9 @@ class Engine:
 
     def _bn_apply(self, rec, z, out, residual=None, relu=True):
         M = z.numel() // rec.C
-        so = self.amax.out_slot(out) if _HP else None        # the next convolution's operand scale comes out of this pass
-        ops.bn_apply(z.view(M, rec.C), rec.scale, rec.shift, out.view(M, rec.C),
-                     residual=None if residual is None else residual.view(M, rec.C), relu=relu, amax_out=so)
-        if so is not None:
-            self.amax.published(out, so)
+        ops.bn_apply(z.view(M, rec.C), rec.scale, rec.shift, out.view(M, rec.C), residual=None if residual is None else residual.view(M, rec.C),
+                     relu=relu, amax_out=self._sink_slot(out))        # the next convolution's operand scale comes out of this pass
+        self._sink_done(out)
         return out
 
     def _bn(self, rec, z, out, training, residual=None, relu=True):
@@ -636,25 +557,58 @@ class Engine:
             else:
                 hd.gw.copy_(hd.gw2[0:1])
                 hd.gb.copy_(hd.gb2[0:1])
-        if side is None or not _HEAD_WGRAD_SIDE:
-            return launch()
-        ops.event_wait(side, self._record(ops.current_stream()))
-        with ops.on_stream(side):
-            launch()
+        self._on_side(side if _HEAD_WGRAD_SIDE else None, launch)
 
-    def _cv(self, d, src, w32, w3, out, hp=None, publish=True, **kw):
-        """one 3x3 / 1x1 convolution or data-gradient launch: the split-operand tile kernel where it applies (hp = (fp16-pair packing,
-        weight amax slot): three fp16 products; else w3: six bf16 products), else fp_conv_igemm"""
-        use_hp = _HP_TILE and hp is not None and hp[0] is not None and not ops._bf16x2
-        if (w3 is not None or use_hp) and ops.conv3x3_bf3_supported(d):
-            if use_hp:
-                return self._cv_hp(d, src, hp[0], hp[1], out, publish=publish, **kw)
-            return ops.conv3x3_bf3(d, src, w3, out, **kw)
-        if _BF3_IGEMM and w3 is not None and not ops._bf16x2 and ops.conv_igemm_hp_supported(d):
-            return ops.conv_igemm_bf3(d, src, w3, out, **kw)
-        if _HP_IGEMM and hp is not None and hp[0] is not None and not ops._bf16x2 and ops.conv_igemm_hp_supported(d):
-            return ops.conv_igemm_hp(d, src, hp[0], out, self.amax.get(src), hp[1], **kw)
-        return ops.conv_igemm(d, src, None, self._need32(w32), out, **kw)
+    def _on_side(self, side, launch, fork=True):
+        """launch() on the stream `side`, ordered behind everything queued on the current stream (fork=False: the caller has just forked
+        `side` from this stream and launched nothing since); side = None: here"""
+        if side is None:
+            return launch()
+        if fork:
+            ops.event_wait(side, self._record(ops.current_stream()))
+        with ops.on_stream(side):
+            return launch()
+
+    @staticmethod
+    def _route(d, lay):
+        """THE kernel family of a launch of descriptor `d` over the copies `lay` (one role of ConvRec.lay): the split-operand tile kernel where it
+        applies (fp16 pairs: three products; else six bf16 products), else the flattened kernel in the exact split / in fp16 pairs, else fp32 MFMA"""
+        use_hp = _HP_TILE and lay.hp is not None and not ops._bf16x2
+        if (lay.bf3 is not None or use_hp) and ops.conv3x3_bf3_supported(d):
+            return TILE_HP if use_hp else TILE_BF3
+        if not ops._bf16x2:
+            if _BF3_IGEMM and lay.bf3 is not None and ops.conv_igemm_hp_supported(d):
+                return IGEMM_BF3
+            if _HP_IGEMM and lay.hp is not None and ops.conv_igemm_hp_supported(d):
+                return IGEMM_HP
+        return IGEMM_F32
+
+    @staticmethod
+    def _route_phase(lay, fits):
+        """... of a phase kernel of an upsample conv (no descriptor, no two-term inference mode); fits: its 8 x 16 tiling takes the grid"""
+        return IGEMM_F32 if (not fits or lay.bf3 is None) else TILE_HP if (_HP_TILE and lay.hp is not None) else TILE_BF3
+
+    def _cv(self, d, src, lay, out, src1=None, publish=True, route=None, **kw):
+        """one 3x3 / 1x1 convolution or data-gradient launch on the kernel family _route names (route: the caller has asked already; src1: the
+        skip tensor of a concat gather -- only the tile and the fp32 kernels have one)"""
+        route = route or self._route(d, lay)
+        assert src1 is None or route in (TILE_HP, TILE_BF3, IGEMM_F32), route
+        if route == TILE_HP:
+            book = self.amax
+            sa = book.get(src)
+            sa1 = book.get(src1) if (src1 is not None and d.C1) else None
+            so = None if ((d.epi & L.EPI_ACCUM) or not publish) else book.out_slot(out)        # an accumulated tensor is never a tile-conv operand
+            ops.conv3x3_hp(d, src, lay.hp, out, sa, lay.wslot, amax_out=so, src1=src1, amax_src1=sa1, **kw)
+            if so is not None:
+                book.published(out, so)
+            return out
+        if route == TILE_BF3:
+            return ops.conv3x3_bf3(d, src, lay.bf3, out, src1=src1, **kw)
+        if route == IGEMM_BF3:
+            return ops.conv_igemm_bf3(d, src, lay.bf3, out, **kw)
+        if route == IGEMM_HP:
+            return ops.conv_igemm_hp(d, src, lay.hp, out, self.amax.get(src), lay.wslot, **kw)
+        return ops.conv_igemm(d, src, src1, self._need32(lay.f32), out, **kw)
 
     def _sink_slot(self, t):
         """amax slot the producer of `t` publishes into (None with the bf16 operand format); follow the launch with _sink_done(t)"""
@@ -663,16 +617,6 @@ class Engine:
     def _sink_done(self, t):
         if _HP:
             self.amax.published(t, self.amax.out_slot(t))
-
-    def _cv_hp(self, d, src, wh, wslot, out, src1=None, publish=True, **kw):
-        book = self.amax
-        sa = book.get(src)
-        sa1 = book.get(src1) if (src1 is not None and d.C1) else None
-        so = None if ((d.epi & L.EPI_ACCUM) or not publish) else book.out_slot(out)        # an accumulated tensor is never a tile-conv operand
-        ops.conv3x3_hp(d, src, wh, out, sa, wslot, amax_out=so, src1=src1, amax_src1=sa1, **kw)
-        if so is not None:
-            book.published(out, so)
-        return out
 
     # ------------------------------------------------------------------------------------------------
     # inference fast path: eval-mode BatchNorm folded into the encoder convs
@@ -690,38 +634,31 @@ class Engine:
         bias (+ residual) + ReLU replaces conv -> coefficients -> apply.  Rebuilt when weights or running statistics changed."""
         pairs = self._enc_pairs()
         if self._fold_buf is None:
-            total = 0
-            for c, _ in pairs:
-                n3 = ops.packed_weight_elems_bf3(c.Cout, c.Cin, c.K, False) if (c.bf3 or c.bf3_ig) else 0
-                n3 += ops.packed_weight_elems_hp(c.Cout, c.Cin, c.K, False) if (c.hp or c.hp_ig) else 0
-                total += c.w.numel() + ops.packed_weight_elems(c.Cout, c.Cin, c.K, False, c.stem) + n3 + c.Cout
-            self._fold_buf = torch.empty(total, device=self.device)
+            plans = [[l for l in WL.plan(c.facts(), FLAGS) if l.role == "fwd" and l.pooled] for c, _ in pairs]
+            self._fold_buf = torch.empty(sum(c.w.numel() + sum(l.numel for l in p) + c.Cout for (c, _), p in zip(pairs, plans)), device=self.device)
             o = 0
-            for c, rec in pairs:
-                n = c.w.numel()
-                c.fw = self._fold_buf[o:o + n].view(c.w.shape)
+            def take(n):
+                nonlocal o
                 o += n
-                n = ops.packed_weight_elems(c.Cout, c.Cin, c.K, False, c.stem)
-                c.fwp = self._fold_buf[o:o + n]
-                o += n
-                n = ops.packed_weight_elems_bf3(c.Cout, c.Cin, c.K, False) if (c.bf3 or c.bf3_ig) else 0
-                c.fwp3 = self._fold_buf[o:o + n] if n else None
-                o += n
-                n = ops.packed_weight_elems_hp(c.Cout, c.Cin, c.K, False) if (c.hp or c.hp_ig) else 0
-                c.fhp = self._fold_buf[o:o + n] if n else None
-                o += n
-                c.fslot = torch.zeros(ops.amax_elems(), dtype=torch.int32, device=self.device) if n else None
-                rec.fshift = self._fold_buf[o:o + c.Cout]
-                o += c.Cout
+                return self._fold_buf[o - n:o]
+            for (c, rec), p in zip(pairs, plans):
+                c.fw = take(c.w.numel()).view(c.w.shape)
+                c.folded = WL.Formats()
+                for l in p:
+                    setattr(c.folded, l.fmt, take(l.numel))
+                if c.folded.hp is not None:
+                    c.folded.wslot = torch.zeros(ops.amax_elems(), dtype=torch.int32, device=self.device)
+                rec.fshift = take(c.Cout)
         for c, rec in pairs:
             bn = rec.bn
             ops.bn_eval_coeffs(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, rec.scale, rec.fshift, bn.eps)
             ops.scale_rows(c.w.data, rec.scale, c.fw)
-            ops.pack_conv_weight(c.fw, c.fwp, c.stem)
-            if c.fwp3 is not None and (c.fhp is None or self.inference_bf16x2):
-                ops.pack_conv_weight_bf3(c.fw, c.fwp3, False)
-            if c.fhp is not None:
-                ops.pack_conv_weight_hp(c.fw, c.fhp, c.fslot, False)
+            f = c.folded
+            ops.pack_conv_weight(c.fw, f.f32, c.stem)
+            if f.bf3 is not None and (f.hp is None or self.inference_bf16x2):
+                ops.pack_conv_weight_bf3(c.fw, f.bf3, False)
+            if f.hp is not None:
+                ops.pack_conv_weight_hp(c.fw, f.hp, f.wslot, False)
         self._fold_ready = True
 
     def _encoder_eval_folded(self, image, N, H, W, S):
@@ -732,14 +669,9 @@ class Engine:
             self._fold_vers = vers
         h, w = H // 2, W // 2
         f0 = buf("f0", (N, h, w, 64))
-        ops.conv_igemm(ops.make_desc(N, h, w, H, W, 3, 0, 64, 7, 2, 3, L.GATHER_STEM, act=L.ACT_RELU), image, None, self.stem.fwp, f0,
+        ops.conv_igemm(ops.make_desc(N, h, w, H, W, 3, 0, 64, 7, 2, 3, L.GATHER_STEM, act=L.ACT_RELU), image, None, self.stem.folded.f32, f0,
                        bias=self.bn0.fshift)
-        hp, wp_ = (h + 1) // 2, (w + 1) // 2
-        pool = buf("pool", (N, hp, wp_, 64))
-        so = self.amax.out_slot(pool) if _HP else None
-        ops.maxpool_fwd(f0, pool, buf("pool.argmax", (N, hp, wp_, 64), torch.uint8), amax_out=so)
-        if so is not None:
-            self.amax.published(pool, so)
+        pool, hp, wp_ = self._maxpool(f0, N, h, w)
         feats, dims = [f0], [(h, w)]
         x, h, w = pool, hp, wp_
         self._wait_pack()          # the decoders' packed weights (the folded encoder copies are packed by _build_fold)
@@ -747,35 +679,32 @@ class Engine:
             s = blk.stride
             oh, ow = (h - 1) // s + 1, (w - 1) // s + 1
             d1 = ops.make_desc(N, oh, ow, h, w, blk.c1.Cin, 0, blk.Cout, 3, s, 1, L.GATHER_FWD_ZERO, act=L.ACT_RELU)
-            ev_idt = None
+            idt, ev_idt = x, None
             if blk.ds is not None:
                 dd = ops.make_desc(N, oh, ow, h, w, blk.ds.Cin, 0, blk.Cout, 1, s, 0, L.GATHER_FWD_ZERO)
-                if self.concurrent and _DS_AUX:           # 1x1 shortcut beside conv1 on the (still idle) aux stream
-                    if _HP_IGEMM:
-                        self.amax.get(x, any_stream=True)
-                    ops.event_wait(self.aux, self._record(ops.current_stream()))
-                    with ops.on_stream(self.aux):
-                        idt = self._cv(dd, x, blk.ds.fwp, blk.ds.fwp3, buf("b%d.idt" % i, (N, oh, ow, blk.Cout)), hp=(blk.ds.fhp, blk.ds.fslot),
-                                       bias=blk.bnd.fshift)
-                        ev_idt = self._record(self.aux)
-                else:
-                    idt = self._cv(dd, x, blk.ds.fwp, blk.ds.fwp3, buf("b%d.idt" % i, (N, oh, ow, blk.Cout)), hp=(blk.ds.fhp, blk.ds.fslot),
-                                   bias=blk.bnd.fshift)
-            else:
-                idt = x
-            a1 = self._cv(d1, x, blk.c1.fwp, blk.c1.fwp3, buf("b%d.a1" % i, (N, oh, ow, blk.Cout)), hp=(blk.c1.fhp, blk.c1.fslot),
-                          bias=blk.bn1.fshift)
+                side = self.aux if (self.concurrent and _DS_AUX) else None      # 1x1 shortcut beside conv1 on the (still idle) aux stream
+                if side is not None and _HP_IGEMM:
+                    self.amax.get(x, any_stream=True)
+                idt = self._on_side(side, lambda: self._cv(dd, x, blk.ds.folded, buf("b%d.idt" % i, (N, oh, ow, blk.Cout)), bias=blk.bnd.fshift))
+                ev_idt = None if side is None else self._record(side)
+            a1 = self._cv(d1, x, blk.c1.folded, buf("b%d.a1" % i, (N, oh, ow, blk.Cout)), bias=blk.bn1.fshift)
             if ev_idt is not None:
                 ops.event_wait(ops.current_stream(), ev_idt)
             d2 = ops.make_desc(N, oh, ow, oh, ow, blk.Cout, 0, blk.Cout, 3, 1, 1, L.GATHER_FWD_ZERO, act=L.ACT_RELU)
-            out = self._cv(d2, a1, blk.c2.fwp, blk.c2.fwp3, buf("b%d.out" % i, (N, oh, ow, blk.Cout)), hp=(blk.c2.fhp, blk.c2.fslot),
-                           bias=blk.bn2.fshift, addend=idt)
+            out = self._cv(d2, a1, blk.c2.folded, buf("b%d.out" % i, (N, oh, ow, blk.Cout)), bias=blk.bn2.fshift, addend=idt)
             x, h, w = out, oh, ow
             if (i + 1 == len(self.blocks)) or (self.blocks[i + 1].stride == 2):
                 feats.append(out)
                 dims.append((h, w))
         S["blocks"] = []
         S["feats"], S["dims"] = feats, dims
+
+    def _maxpool(self, f0, N, h, w):
+        hp, wp_ = (h + 1) // 2, (w + 1) // 2
+        pool = self.buf("pool", (N, hp, wp_, 64))
+        ops.maxpool_fwd(f0, pool, self.buf("pool.argmax", (N, hp, wp_, 64), torch.uint8), amax_out=self._sink_slot(pool))
+        self._sink_done(pool)
+        return pool, hp, wp_
 
     def _wait_pack(self):
         """the side-stream part of the weight repack (everything after layer1) must have landed"""
@@ -824,10 +753,10 @@ class Engine:
         """FP_PACK_DGRAD_LATE: the deferred part of refresh_packed, on the repack stream behind everything queued on the calling stream"""
         if self._pack_dgrad_pending:
             self._pack_dgrad_pending = False
-            ops.event_wait(self.wg, self._record(ops.current_stream()))
-            with ops.on_stream(self.wg):
+            def late():
                 ops.pack_weights_batched(self._pack_table[3], max_wgs=_PACK_SIDE_WGS)
                 self._pack_ev_dgrad = self._record(self.wg)
+            self._on_side(self.wg, late)
 
     def _wait_pack_dgrad(self):
         """... and the data-gradient layouts, before the first backward kernel that reads one"""
@@ -841,25 +770,30 @@ class Engine:
         Welford partials of its output (ops.bn_stats_out -> the launch's fp_aux) and _bn_coeffs skips the statistics pass over the activation"""
         OH, OW = (H + 2 * c.pad - c.K) // c.stride + 1, (W + 2 * c.pad - c.K) // c.stride + 1
         d = ops.make_desc(N, OH, OW, H, W, c.Cin, 0, c.Cout, c.K, c.stride, c.pad, L.GATHER_FWD_ZERO)
-        bo = None
+        bo, route = None, None
         if bn is not None:
             bn.stats_nblk = 0
-            tile = (c.wp3 is not None or (_HP_TILE and c.hp_f is not None and not ops._bf16x2)) and ops.conv3x3_bf3_supported(d)
-            # ... or a strided / 1 x 1 convolution through the fp16-pair implicit GEMM: its split grids emit from their reduce launch
-            tile = tile or (_HP_IGEMM and c.hp_f is not None and not ops._bf16x2 and ops.conv_igemm_hp_supported(d))
-            tile = tile or (_BF3_IGEMM and c.bf3_ig and not ops._bf16x2 and ops.conv_igemm_hp_supported(d))      # ... or the exact one
-            if tile and ops._BN_EPI:
-                # one (count, mean, M2) triple per pixel tile and channel: tiles of 8 x 16 or 6 x 20 pixels, bounded by 6 x 16-pixel ones
-                cap = N * ((OH + 5) // 6) * ((OW + 15) // 16) * c.Cout * 3
-                if c.Cout % 4 == 0 and 256 % (c.Cout // 4) == 0:       # split-K grids: one triple per block of the reduce launch (fp_splitk_reduce_stats_launch)
-                    rows = 256 // (c.Cout // 4) * 4
-                    cap = max(cap, min(512, (N * OH * OW + rows - 1) // rows) * c.Cout * 3)
-                bn.stats_part = self.buf(part, (max(cap, 1),))      # (`part`: the shortcut branch runs beside conv1 on another stream: its own buffer)
+            # the tile kernels emit from their epilogue, the split-operand flattened kernels from the reduce launch of their split grids -- but
+            # a 3x3 stride-1 convolution that fell off the tile kernel onto the EXACT flattened one keeps its statistics pass, as it always has
+            route = self._route(d, c.lay.fwd)
+            if ops._BN_EPI and route != IGEMM_F32 and not (route == IGEMM_BF3 and c.bf3):
+                # one (count, mean, M2) triple per tile and channel (`part`: the shortcut branch runs beside conv1 on another stream: its own buffer)
+                bn.stats_part = self.buf(part, (self._partials_cap(N, OH, OW, c.Cout, 3),))
                 bo = ops.bn_stats_out(bn.stats_part)
-        y = self._cv(d, x, c.wp, c.wp3, out, hp=(c.hp_f, c.wslot), bn_out=bo)
+        y = self._cv(d, x, c.lay.fwd, out, route=route, bn_out=bo)
         if bo is not None:
             bn.stats_nblk = bo.nblk
         return y
+
+    @staticmethod
+    def _partials_cap(N, h, w, C, per):
+        """floats of a tile launch's BatchNorm side output: `per` values per pixel tile (8 x 16 or 6 x 20 pixels, bounded by 6 x 16-pixel ones)
+        and channel; split-K grids: per block of the reduce launch (fp_splitk_reduce_stats_launch / fp_splitk_reduce_bnb_launch)"""
+        cap = N * ((h + 5) // 6) * ((w + 15) // 16) * C * per
+        if C % 4 == 0 and 256 % (C // 4) == 0:
+            rows = 256 // (C // 4) * 4
+            cap = max(cap, min(512, (N * h * w + rows - 1) // rows) * C * per)
+        return max(cap, 1)
 
     @staticmethod
     def _phase_ok(h, w):
@@ -870,24 +804,19 @@ class Engine:
         if up2 and c.up2 is not None and self._phase_ok(H // 2, W // 2):
             if C1:      # skip half at full resolution (raw partial sums), then the four phases of the upsampled half on top
                 d = ops.make_desc(N, H, W, H, W, C1, 0, c.Cout, 3, 1, 1, L.GATHER_FWD_REFLECT)
-                self._cv(d, x1, c.wsk, c.wsk3, out, hp=(c.hp_sk, c.wslot), publish=False)   # raw partial sums: not the tensor's amax
-            if c.hp_ph is not None and _HP_TILE:
-                so = self.amax.out_slot(out)
-                ops.conv_up2_phase_fwd_hp(x0, c.hp_ph, c.b.data, out, self.amax.get(x0), c.wslot, amax_out=so, act=L.ACT_ELU,
+                self._cv(d, x1, c.lay.skip_fwd, out, publish=False)   # raw partial sums: not the tensor's amax
+            ph, route = c.lay.phase_fwd, self._route_phase(c.lay.phase_fwd, True)
+            if route == TILE_HP:
+                ops.conv_up2_phase_fwd_hp(x0, ph.hp, c.b.data, out, self.amax.get(x0), ph.wslot, amax_out=self._sink_slot(out), act=L.ACT_ELU,
                                           addend=out if C1 else None)
-                self.amax.published(out, so)
+                self._sink_done(out)
                 return out
-            phase_fwd = ops.conv_up2_phase_fwd_bf3 if c.wph3 is not None else ops.conv_up2_phase_fwd
-            return phase_fwd(x0, c.wph3 if c.wph3 is not None else self._need32(c.wph), c.b.data, out, act=L.ACT_ELU, addend=out if C1 else None)
+            if route == TILE_BF3:
+                return ops.conv_up2_phase_fwd_bf3(x0, ph.bf3, c.b.data, out, act=L.ACT_ELU, addend=out if C1 else None)
+            return ops.conv_up2_phase_fwd(x0, self._need32(ph.f32), c.b.data, out, act=L.ACT_ELU, addend=out if C1 else None)
         gather = L.GATHER_FWD_REFLECT_UP2 if up2 else L.GATHER_FWD_REFLECT
         d = ops.make_desc(N, H, W, H, W, C0, C1, c.Cout, 3, 1, 1, gather, act=L.ACT_ELU)
-        if x1 is None and not up2:
-            return self._cv(d, x0, c.wp, c.wp3, out, hp=(c.hp_f, c.wslot), bias=c.b.data)
-        if up2 and c.wp3 is not None and ops.conv3x3_bf3_supported(d):      # concat gather inside the split-operand tile kernel
-            if c.hp_f is not None and not ops._bf16x2 and _HP_TILE:
-                return self._cv_hp(d, x0, c.hp_f, c.wslot, out, src1=x1, bias=c.b.data)
-            return ops.conv3x3_bf3(d, x0, c.wp3, out, bias=c.b.data, src1=x1)
-        return ops.conv_igemm(d, x0, x1, self._need32(c.wp), out, bias=c.b.data)
+        return self._cv(d, x0, c.lay.fwd, out, src1=x1, bias=c.b.data)      # (a concat gather only exists in the tile and the fp32 kernels)
 
     # ------------------------------------------------------------------------------------------------
     # forward
@@ -934,20 +863,15 @@ class Engine:
             self.bn0.stats_part = buf("bn.part0", (N * ((h + 7) // 8) * ((w + 15) // 16) * 64 * 3,))
             bo = ops.bn_stats_out(self.bn0.stats_part)
         d0 = ops.make_desc(N, h, w, H, W, 3, 0, 64, 7, 2, 3, L.GATHER_STEM)
-        if self.stem.hp_f is not None and not ops._bf16x2 and ops.conv_stem_hp_supported(d0):
-            ops.conv_stem_hp(d0, image, self.stem.hp_f, z0, self.stem.wslot, bn_out=bo)
+        w0 = self.stem.lay.fwd
+        if w0.hp is not None and not ops._bf16x2 and ops.conv_stem_hp_supported(d0):
+            ops.conv_stem_hp(d0, image, w0.hp, z0, w0.wslot, bn_out=bo)
         else:
-            ops.conv_igemm(d0, image, None, self.stem.wp, z0, bn_out=bo)
+            ops.conv_igemm(d0, image, None, w0.f32, z0, bn_out=bo)
         if bo is not None:
             self.bn0.stats_nblk = bo.nblk
         f0 = self._bn(self.bn0, z0, buf("f0", (N, h, w, 64)), training)
-        hp, wp_ = (h + 1) // 2, (w + 1) // 2
-        pool = buf("pool", (N, hp, wp_, 64))
-        am = buf("pool.argmax", (N, hp, wp_, 64), torch.uint8)
-        so = self.amax.out_slot(pool) if _HP else None
-        ops.maxpool_fwd(f0, pool, am, amax_out=so)
-        if so is not None:
-            self.amax.published(pool, so)
+        pool, hp, wp_ = self._maxpool(f0, N, h, w)
         feats = [f0]
         dims = [(h, w)]
         x, h, w = pool, hp, wp_
@@ -1027,7 +951,7 @@ class Engine:
         for P, c, off in dec.psp.blocks:
             pooled = ops.adaptive_avgpool_fwd(f4, buf("%s.psp.pool%d" % (dec.name, P), (N, P, P, 512)))
             d = ops.make_desc(N, P, P, P, P, 512, 0, 128, 1, 1, 0, L.GATHER_FWD_ZERO)
-            red = ops.conv_igemm(d, pooled, None, self._need32(c.wp), buf("%s.psp.red%d" % (dec.name, P), (N, P, P, 128)))
+            red = ops.conv_igemm(d, pooled, None, self._need32(c.lay.fwd.f32), buf("%s.psp.red%d" % (dec.name, P), (N, P, P, 128)))
             ops.bilinear_ac_fwd(red, cat, off)
             D["psp"].append(pooled)
         return cat
@@ -1041,7 +965,7 @@ class Engine:
             dw = ops.make_desc(N, P, P, P, P, 512, 0, 128, 1, 1, 0, L.GATHER_FWD_ZERO)
             ops.conv_wgrad(dw, pooled, None, dred, c.gw, accumulate=acc)
             dd = ops.make_desc(N, P, P, P, P, 128, 0, 512, 1, 1, 0, L.GATHER_DGRAD_ZERO)
-            dpool = ops.conv_igemm(dd, dred, None, self._need32(c.wpd), buf("g.%s.psp.dpool%d" % (dec.name, P), (N, P, P, 512)))
+            dpool = ops.conv_igemm(dd, dred, None, self._need32(c.lay.dgrad.f32), buf("g.%s.psp.dpool%d" % (dec.name, P), (N, P, P, 512)))
             ops.adaptive_avgpool_bwd(dpool, dF4, accumulate=True)
 
     def _decoder_forward(self, dec, S, outputs, D):
@@ -1049,6 +973,12 @@ class Engine:
         N, feats, dims = S["N"], S["feats"], S["dims"]
         buf = self.buf
         D.update({"y": [], "x": [], "low": []})
+
+        def head(k, x):
+            low = buf("%s.low%d" % (dec.name, k + 1), x.shape[:3] + (2,))
+            ops.head_fwd(x, *self._head_wb(dec.heads[k]), low, dec.sig)
+            ops.head_upsample(low, outputs[k], dec.head_scales[k], dec.c0)
+            D["low"].append(low)
         x = feats[4]
         h, w = dims[4]
         if dec.psp is not None:
@@ -1069,23 +999,14 @@ class Engine:
             D["x"].append(xo)
             x = xo
             if bi >= 1 and (bi - 1) in S.get("scales", _ALL_SCALES):     # heads on block2/3/4 outputs: scales 8, 4, 2
-                scale = dec.head_scales[bi - 1]
-                low = buf("%s.low%d" % (dec.name, bi), (N, h, w, 2))
-                hw_, hb_ = self._head_wb(dec.heads[bi - 1])
-                ops.head_fwd(x, hw_, hb_, low, dec.sig)
-                ops.head_upsample(low, outputs[bi - 1], scale, dec.c0)
-                D["low"].append(low)
+                head(bi - 1, x)
         # outconv4: nearest x2 (virtual) -> ConvBlock(64->32) -> head, scale 1
         yield
         h, w = 2 * h, 2 * w
         y51 = self._conv_dec(dec.o41, x, None, N, h, w, 64, 0, True, buf(dec.name + ".y51", (N, h, w, 32)))
         x5 = self._conv_dec(dec.o42, y51, None, N, h, w, 32, 0, False, buf(dec.name + ".x5", (N, h, w, 32)))
         if 3 in S.get("scales", _ALL_SCALES):
-            low = buf(dec.name + ".low4", (N, h, w, 2))
-            hw_, hb_ = self._head_wb(dec.heads[3])
-            ops.head_fwd(x5, hw_, hb_, low, dec.sig)
-            ops.head_upsample(low, outputs[3], 1, dec.c0)
-            D["low"].append(low)
+            head(3, x5)
         D["y51"], D["x5"] = y51, x5
 
     # ------------------------------------------------------------------------------------------------
@@ -1109,12 +1030,7 @@ class Engine:
             ops.conv_wgrad(d, src0, src1, dz, c.gw, accumulate=acc)
             if c.gb is not None:
                 ops.colsum(dz.view(-1, c.Cout), c.gb, accumulate=acc)
-        if side is None:
-            return launch()
-        if fork:
-            ops.event_wait(side, self._record(ops.current_stream()))
-        with ops.on_stream(side):
-            launch()
+        self._on_side(side, launch, fork)
 
     def _wgrad_up2(self, c, low, skip, dz, N, hl, wl, C0, C1, acc, side=None, fork=True):
         """weight (+bias) gradient of a conv over cat[nearest_x2(low), skip]: upsampled half by output phase, skip half as a
@@ -1133,12 +1049,7 @@ class Engine:
                 ops.conv_wgrad_bf3(d_lo, low, dz, c.gw, 0, accumulate=acc, db=c.gb, amax=am_lo)
                 if d_sk is not None:
                     ops.conv_wgrad_bf3(d_sk, skip, dz, c.gw, C0, accumulate=acc, amax=am_sk)
-            if side is None:
-                return launch_small()
-            if fork:
-                ops.event_wait(side, self._record(ops.current_stream()))
-            with ops.on_stream(side):
-                return launch_small()
+            return self._on_side(side, launch_small, fork)
 
         pbf3 = _WBF3 and _PWBF3
         d_skip = ops.make_desc(N, H, W, H, W, C1, 0, c.Cout, 3, 1, 1, L.GATHER_FWD_REFLECT) if C1 else None
@@ -1162,27 +1073,24 @@ class Engine:
                     ops.conv_wgrad_slice(d, skip, None, dz, c.gw, C0, accumulate=acc)
             if not bias_done:
                 ops.colsum(dz.view(-1, c.Cout), c.gb, accumulate=acc)
-        if side is None:
-            return launch()
-        if fork:
-            ops.event_wait(side, self._record(ops.current_stream()))
-        with ops.on_stream(side):
-            launch()
+        self._on_side(side, launch, fork)
 
     def _dgrad_dec(self, c, dz, N, H, W, out, actsrc=None, addend=None, accum=False):
         epi = (L.EPI_ACTGRAD_ELU if actsrc is not None else 0) | (L.EPI_ACCUM if accum else 0)
         d = ops.make_desc(N, H, W, H, W, c.Cout, 0, c.Cin, 3, 1, 1, L.GATHER_DGRAD_REFLECT, epi=epi)
-        return self._cv(d, dz, c.wpd, c.wpd3, out, hp=(c.hp_d, c.wslot), actsrc=actsrc, addend=addend)
+        return self._cv(d, dz, c.lay.dgrad, out, actsrc=actsrc, addend=addend)
 
     def _dgrad_up2_ext(self, c, dz, N, hl, wl, C0, pfx):
         """gradient wrt the low-res input of an upsample conv on the (hl+2) x (wl+2) extended grid (ops.up2_fold_bwd folds it)"""
         ext = self.buf(pfx + "XV", (N, hl + 2, wl + 2, C0))
-        if c.wdu3 is not None and self._phase_ok(hl + 2, wl + 2):      # split-operand phase kernel (8x16 tiles of the extended grid)
-            if c.hp_du is not None and _HP_TILE:
-                return ops.conv_up2_phase_dgrad_hp(dz, c.hp_du, ext, self.amax.get(dz), c.wslot)
-            return ops.conv_up2_phase_dgrad_bf3(dz, c.wdu3, ext)
+        ph = c.lay.phase_dgrad
+        route = self._route_phase(ph, self._phase_ok(hl + 2, wl + 2))      # split-operand phase kernel (8x16 tiles of the extended grid)
+        if route == TILE_HP:
+            return ops.conv_up2_phase_dgrad_hp(dz, ph.hp, ext, self.amax.get(dz), ph.wslot)
+        if route == TILE_BF3:
+            return ops.conv_up2_phase_dgrad_bf3(dz, ph.bf3, ext)
         d = ops.make_desc(N, hl + 2, wl + 2, 2 * hl, 2 * wl, c.Cout, 0, C0, 4, 2, 3, L.GATHER_FWD_ZERO)
-        return ops.conv_igemm(d, dz, None, self._need32(c.wdu), ext)
+        return ops.conv_igemm(d, dz, None, self._need32(ph.f32), ext)
 
     def stage_streams(self):
         """every stream that may still be writing parameter gradients when `on_stage` fires (None: everything is on the caller's stream)"""
@@ -1230,16 +1138,12 @@ class Engine:
         dnext = None       # gradient wrt this block's output coming from the next block (same layer)
         dnext_part = None  # (partials, blocks) when `dnext` already IS g = dout * (out > 0) and its producer wrote bn2's backward sums
         # (round 5: also with the exact bf16x3 operands -- the sink is a property of the tile kernel's epilogue, not of the operand format)
-        bwd_epi = ops._BN_BWD_EPI and (_HP_TILE or _BF3) and not ops._bf16x2
+        # does this data gradient go to a tile kernel, whose epilogue can emit a BatchNorm's backward sums?
+        bwd_epi = lambda d_, c_: ops._BN_BWD_EPI and self._route(d_, c_.lay.dgrad) in (TILE_HP, TILE_BF3)
 
         def bnb_arm(name, h_, w_, C_, z, rec):
-            """the BatchNorm-backward side output (ops.BnOut) for a tile data gradient at (h_, w_, C_): partial sums per pixel tile (8 x 16 or 6 x 20
-            pixels, bounded by 6 x 16-pixel ones) and channel"""
-            cap = N * ((h_ + 5) // 6) * ((w_ + 15) // 16) * C_ * 2
-            if C_ % 4 == 0 and 256 % (C_ // 4) == 0:              # split-K grids: one pair per block of the reduce launch (fp_splitk_reduce_bnb_launch)
-                rows = 256 // (C_ // 4) * 4
-                cap = max(cap, min(512, (N * h_ * w_ + rows - 1) // rows) * C_ * 2)
-            part = buf(name, (max(cap, 1),))
+            """the BatchNorm-backward side output (ops.BnOut) for a tile data gradient at (h_, w_, C_): a pair of partial sums per tile and channel"""
+            part = buf(name, (self._partials_cap(N, h_, w_, C_, 2),))
             return part, ops.bn_bwd_out(part, z.view(-1, C_), rec.mean, rec.invstd)
         for i in range(nblk - 1, -1, -1):
             blk, B = self.blocks[i], S["blocks"][i]
@@ -1261,32 +1165,41 @@ class Engine:
             dnext_part = None
             self._sink_done(dz2)
             ev_ds = None
+            first_of_layer = (i == 0) or blk.stride == 2
+            dgd = ops.make_desc(N, hin, win, h, w, C, 0, Cin, 3, blk.stride, 1, L.GATHER_DGRAD_ZERO)
+
+            def conv1_dgrad_acc():       # on top of the previous layer's feature gradient (which already holds the decoders' gradients)
+                dgd.epi = L.EPI_ACCUM
+                self._cv(dgd, dz1, blk.c1.lay.dgrad, dF[feat_of_block[i - 1]])
+
+            def downsample(between=None):       # BN backward, weight gradient, [between], data gradient into the previous layer's feature gradient
+                dzd = buf("g.dzd.%d" % i, (N, h, w, C))
+                ops.bn_bwd(g.view(M, C), None, B["zd"].view(M, C), blk.bnd.mean, blk.bnd.invstd, blk.bnd.bn.weight.data,
+                           dzd.view(M, C), blk.bnd.gg, blk.bnd.gb, accumulate=accumulate,
+                           amax_out=self._sink_slot(dzd) if blk.ds.hp_ig else None)
+                if blk.ds.hp_ig:
+                    self._sink_done(dzd)
+                self._wgrad(blk.ds, L.GATHER_FWD_ZERO, B["x"], None, dzd, N, h, w, hin, win, Cin, 0, accumulate, side)
+                if between is not None:
+                    between()
+                d1 = ops.make_desc(N, hin, win, h, w, C, 0, Cin, 1, blk.stride, 0, L.GATHER_DGRAD_ZERO, epi=L.EPI_ACCUM)
+                self._cv(d1, dzd, blk.ds.lay.dgrad, dF[feat_of_block[i - 1]])
             if blk.ds is not None and self.concurrent and _DS_AUX:
-                # downsample branch on the aux stream: BN backward, weight gradient, and its data gradient FIRST into the previous layer's
-                # feature gradient; the main branch's conv1 data gradient accumulates on top after the join (fixed order)
-                tgt = dF[feat_of_block[i - 1]]
+                # on the aux stream, its data gradient FIRST; the main branch's conv1 data gradient accumulates on top after the join (fixed order)
                 ops.event_wait(self.aux, self._record(ops.current_stream()))
                 with ops.on_stream(self.aux):
-                    dzd = buf("g.dzd.%d" % i, (N, h, w, C))
-                    ops.bn_bwd(g.view(M, C), None, B["zd"].view(M, C), blk.bnd.mean, blk.bnd.invstd, blk.bnd.bn.weight.data,
-                               dzd.view(M, C), blk.bnd.gg, blk.bnd.gb, accumulate=accumulate,
-                               amax_out=self._sink_slot(dzd) if blk.ds.hp_ig else None)
-                    if blk.ds.hp_ig:
-                        self._sink_done(dzd)
-                    self._wgrad(blk.ds, L.GATHER_FWD_ZERO, B["x"], None, dzd, N, h, w, hin, win, Cin, 0, accumulate, side)
-                    d1 = ops.make_desc(N, hin, win, h, w, C, 0, Cin, 1, blk.stride, 0, L.GATHER_DGRAD_ZERO, epi=L.EPI_ACCUM)
-                    self._cv(d1, dzd, blk.ds.wpd, blk.ds.wpd3, tgt, hp=(blk.ds.hp_d, blk.ds.wslot))
+                    downsample()
                     ev_ds = self._record(self.aux)
             if not _WGRAD_PAIR_FORK:
                 self._wgrad(blk.c2, L.GATHER_FWD_ZERO, B["a1"], None, dz2, N, h, w, h, w, C, 0, accumulate, side)
             da1 = buf("g.da1", (N, h, w, C))
             dz1 = buf("g.dz1.%d" % i, (N, h, w, C))
             d2 = ops.make_desc(N, h, w, h, w, C, 0, C, 3, 1, 1, L.GATHER_DGRAD_ZERO)
-            if bwd_epi and (blk.c2.hp_d is not None or blk.c2.wpd3 is not None) and ops.conv3x3_bf3_supported(d2):
+            if bwd_epi(d2, blk.c2):
                 # conv2's data gradient applies bn1's ReLU mask itself (da1 = gradient * (a1 > 0)) and emits bn1's backward sums
                 d2.epi = L.EPI_ACTGRAD_RELU
                 part, bo = bnb_arm("bnb.part1", h, w, C, B["z1"], blk.bn1)
-                self._cv(d2, dz2, blk.c2.wpd, blk.c2.wpd3, da1, hp=(blk.c2.hp_d, blk.c2.wslot), actsrc=B["a1"], bn_out=bo)
+                self._cv(d2, dz2, blk.c2.lay.dgrad, da1, actsrc=B["a1"], bn_out=bo)
                 if bo.nblk > 0:
                     ops.bn_bwd_partials(da1.view(M, C), B["z1"].view(M, C), blk.bn1.mean, blk.bn1.invstd, blk.bn1.bn.weight.data,
                                         dz1.view(M, C), blk.bn1.gg, blk.bn1.gb, part, bo.nblk, accumulate=accumulate,
@@ -1295,7 +1208,7 @@ class Engine:
                     ops.bn_bwd(da1.view(M, C), None, B["z1"].view(M, C), blk.bn1.mean, blk.bn1.invstd, blk.bn1.bn.weight.data,
                                dz1.view(M, C), blk.bn1.gg, blk.bn1.gb, accumulate=accumulate, amax_out=self._sink_slot(dz1))
             else:
-                self._cv(d2, dz2, blk.c2.wpd, blk.c2.wpd3, da1, hp=(blk.c2.hp_d, blk.c2.wslot))
+                self._cv(d2, dz2, blk.c2.lay.dgrad, da1)
                 ops.bn_bwd(da1.view(M, C), B["a1"].view(M, C), B["z1"].view(M, C), blk.bn1.mean, blk.bn1.invstd, blk.bn1.bn.weight.data,
                            dz1.view(M, C), blk.bn1.gg, blk.bn1.gb, accumulate=accumulate, amax_out=self._sink_slot(dz1))
             self._sink_done(dz1)
@@ -1306,47 +1219,33 @@ class Engine:
                 self._wgrad(blk.c2, L.GATHER_FWD_ZERO, B["a1"], None, dz2, N, h, w, h, w, C, 0, accumulate, side)
             self._wgrad(blk.c1, L.GATHER_FWD_ZERO, B["x"], None, dz1, N, h, w, hin, win, Cin, 0, accumulate, side,
                         fork=not (_WGRAD_PAIR_FORK and side is not None))
-            first_of_layer = (i == 0) or blk.stride == 2
-            dgd = ops.make_desc(N, hin, win, h, w, C, 0, Cin, 3, blk.stride, 1, L.GATHER_DGRAD_ZERO)
-            if blk.ds is not None and ev_ds is not None:
-                ops.event_wait(ops.current_stream(), ev_ds)
-                dgd.epi = L.EPI_ACCUM
-                self._cv(dgd, dz1, blk.c1.wpd, blk.c1.wpd3, dF[feat_of_block[i - 1]], hp=(blk.c1.hp_d, blk.c1.wslot))
-                dnext = None
-            elif blk.ds is not None:
-                dzd = buf("g.dzd.%d" % i, (N, h, w, C))
-                ops.bn_bwd(g.view(M, C), None, B["zd"].view(M, C), blk.bnd.mean, blk.bnd.invstd, blk.bnd.bn.weight.data,
-                           dzd.view(M, C), blk.bnd.gg, blk.bnd.gb, accumulate=accumulate,
-                           amax_out=self._sink_slot(dzd) if blk.ds.hp_ig else None)
-                if blk.ds.hp_ig:
-                    self._sink_done(dzd)
-                self._wgrad(blk.ds, L.GATHER_FWD_ZERO, B["x"], None, dzd, N, h, w, hin, win, Cin, 0, accumulate, side)
-                tgt = dF[feat_of_block[i - 1]]          # block input is the previous layer's feature (already holds decoder grads)
-                dgd.epi = L.EPI_ACCUM
-                self._cv(dgd, dz1, blk.c1.wpd, blk.c1.wpd3, tgt, hp=(blk.c1.hp_d, blk.c1.wslot))
-                d1 = ops.make_desc(N, hin, win, h, w, C, 0, Cin, 1, blk.stride, 0, L.GATHER_DGRAD_ZERO, epi=L.EPI_ACCUM)
-                self._cv(d1, dzd, blk.ds.wpd, blk.ds.wpd3, tgt, hp=(blk.ds.hp_d, blk.ds.wslot))
+            if blk.ds is not None:
+                if ev_ds is not None:
+                    ops.event_wait(ops.current_stream(), ev_ds)
+                    conv1_dgrad_acc()
+                else:                                   # in line: conv1's data gradient first, the downsample branch's on top
+                    downsample(between=conv1_dgrad_acc)
                 dnext = None
             elif first_of_layer:                        # layer1 block 0: input is the max-pool output
                 dpool = buf("g.dpool", (N, hin, win, Cin))
-                self._cv(dgd, dz1, blk.c1.wpd, blk.c1.wpd3, dpool, hp=(blk.c1.hp_d, blk.c1.wslot), addend=g)
+                self._cv(dgd, dz1, blk.c1.lay.dgrad, dpool, addend=g)
                 ops.maxpool_bwd(dpool, self._bufs["pool.argmax"][:dpool.numel()].view(dpool.shape), dF[0], accumulate=True)
                 dnext = None
             else:
                 dx = buf("g.dx%d" % (i & 1), (N, hin, win, Cin))
-                if bwd_epi and (blk.c1.hp_d is not None or blk.c1.wpd3 is not None) and ops.conv3x3_bf3_supported(dgd):
+                if bwd_epi(dgd, blk.c1):
                     # this block's input is the previous block's output (after its ReLU): conv1's data gradient + the residual gradient,
                     # masked by (input > 0), IS the g of the previous block's bn2 -- stored as such, with that BatchNorm's backward sums
                     Bp, blkp = S["blocks"][i - 1], self.blocks[i - 1]
                     dgd.epi = L.EPI_ACTGRAD_RELU
                     part, bo = bnb_arm("bnb.part2", hin, win, Cin, Bp["z2"], blkp.bn2)
-                    self._cv(dgd, dz1, blk.c1.wpd, blk.c1.wpd3, dx, hp=(blk.c1.hp_d, blk.c1.wslot), addend=g, actsrc=B["x"], bn_out=bo)
+                    self._cv(dgd, dz1, blk.c1.lay.dgrad, dx, addend=g, actsrc=B["x"], bn_out=bo)
                     if bo.nblk > 0:
                         dnext_part = (part, bo.nblk)
                     else:                               # masked, no sums: the regular backward below must not mask again -- it would not
                         dnext_part = None               # change anything (g * (out > 0) is idempotent), so it simply runs as before
                 else:
-                    self._cv(dgd, dz1, blk.c1.wpd, blk.c1.wpd3, dx, hp=(blk.c1.hp_d, blk.c1.wslot), addend=g)
+                    self._cv(dgd, dz1, blk.c1.lay.dgrad, dx, addend=g)
                 dnext = dx
             if self.debug_hook is not None:
                 self.debug_hook(i, dict(dout=dout, g=g, dz2=dz2, da1=da1, dz1=dz1, dnext=dnext, B=B))
@@ -1358,7 +1257,7 @@ class Engine:
         z0 = self._bufs["z0"][:M0 * 64].view(M0, 64)
         dz0 = buf("g.dz0", (N, h0, w0, 64))
         d = ops.make_desc(N, h0, w0, S["H"], S["W"], 3, 0, 64, 7, 2, 3, L.GATHER_STEM)
-        stem_hp = self.stem.hp_f is not None and ops.conv_stem_hp_supported(d)         # fp16-pair weight gradient: dz0's amax out of bn_bwd
+        stem_hp = self.stem.lay.fwd.hp is not None and ops.conv_stem_hp_supported(d)         # fp16-pair weight gradient: dz0's amax out of bn_bwd
         ops.bn_bwd(dF[0].view(M0, 64), feats[0].view(M0, 64), z0, self.bn0.mean, self.bn0.invstd, self.bn0.bn.weight.data,
                    dz0.view(M0, 64), self.bn0.gg, self.bn0.gb, accumulate=accumulate, amax_out=self._sink_slot(dz0) if stem_hp else None)
         if stem_hp:
@@ -1449,10 +1348,19 @@ class Engine:
                 self._ev_dF[k] = self._record(cur)
             elif self._ev_dF[k] is not None:
                 ops.event_wait(cur, self._ev_dF[k])
+        side_h = side if _HEAD_WGRAD_SIDE else None
+
+        def head_bwd(k, x):
+            """head k (scales 8, 4, 2) on x: its weight gradient; -> its gradient wrt x"""
+            dzl = buf(pfx + "dzl%d" % k, x.shape[:3] + (2,))      # (one buffer per scale: the side stream reads it until the end of the backward pass)
+            ops.head_upsample_bwd(gouts[k], D["low"][k], dzl, dec.head_scales[k], dec.c0, dec.sig)
+            self._head_wgrad(dec.heads[k], x, dzl, acc, side_h)
+            XH = buf(pfx + "XH", tuple(x.shape))
+            ops.head_dgrad(dzl, self._head_wb(dec.heads[k])[0], XH)
+            return XH
         # ---- full-resolution tail: head4 <- o42 <- o41 <- up2(x4) ------------------------------------
         x4 = D["x"][3]
         h0, w0 = dims[0]
-        side_h = side if _HEAD_WGRAD_SIDE else None
         dzl = buf(pfx + "dzl3", (N, H, W, 2))         # (one buffer per scale: the side stream reads it until the end of the backward pass)
         ops.head_upsample_bwd(gouts[3], D["low"][3], dzl, dec.head_scales[3], dec.c0, dec.sig)
         hd = dec.heads[3]
@@ -1474,13 +1382,7 @@ class Engine:
             XV = self._dgrad_up2_ext(dec.o41, Bz, N, h0, w0, 64, pfx)
         else:
             XV = self._dgrad_dec(dec.o41, Bz, N, H, W, buf(pfx + "XV", (N, H, W, 64)))
-        # head3 on x4
-        dzl = buf(pfx + "dzl2", (N, h0, w0, 2))
-        ops.head_upsample_bwd(gouts[2], D["low"][2], dzl, dec.head_scales[2], dec.c0, dec.sig)
-        hd = dec.heads[2]
-        self._head_wgrad(hd, x4, dzl, acc, side_h)
-        XH = buf(pfx + "XH", (N, h0, w0, 64))
-        ops.head_dgrad(dzl, self._head_wb(hd)[0], XH)
+        XH = head_bwd(2, x4)
         A = buf(pfx + "dz.post2.3", (N, h0, w0, 64))
         if phase41:
             ops.up2_fold_bwd(XV, A, addend=XH, ylow=x4, amax_out=self._sink_slot(A))
@@ -1517,7 +1419,7 @@ class Engine:
                     order_dF(3 - bi)
                 ds = ops.make_desc(N, hh, ww, hh, ww, cout, 0, cout, 3, 1, 1, L.GATHER_DGRAD_REFLECT,
                                    epi=L.EPI_ACCUM if accum_feat else 0)
-                self._cv(ds, Bz, blk["post1"].wds, blk["post1"].wds3, dF[3 - bi], hp=(blk["post1"].hp_ds, blk["post1"].wslot))
+                self._cv(ds, Bz, blk["post1"].lay.skip_dgrad, dF[3 - bi])
             else:
                 XV = self._dgrad_dec(blk["post1"], Bz, N, hh, ww, buf(pfx + "XV", (N, hh, ww, 2 * cout)))
                 if not first:
@@ -1549,13 +1451,7 @@ class Engine:
             else:
                 XH = None
                 if bi >= 2:                          # heads on block2 / block3 outputs (x2: scale 8, x3: scale 4)
-                    k = bi - 2
-                    dzl = buf(pfx + "dzl%d" % k, (N, hl, wl, 2))
-                    ops.head_upsample_bwd(gouts[k], D["low"][k], dzl, dec.head_scales[k], dec.c0, dec.sig)
-                    hd = dec.heads[k]
-                    self._head_wgrad(hd, xin, dzl, acc, side_h)
-                    XH = buf(pfx + "XH", (N, hl, wl, cin))
-                    ops.head_dgrad(dzl, self._head_wb(hd)[0], XH)
+                    XH = head_bwd(bi - 2, xin)
                 A = self._dgrad_dec(blk["pre1"], Bz, N, hl, wl, buf(pfx + "dz.post2.%d" % (bi - 1), (N, hl, wl, cin)), actsrc=xin, addend=XH)
 
     # ------------------------------------------------------------------------------------------------
