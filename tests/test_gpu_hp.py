@@ -237,7 +237,7 @@ def test_conv3x3_hp_dynamic_range_and_specials():
     assert not bool(torch.isfinite(y[1, 6:9, 8:11]).all()) and bool(torch.isfinite(y[0]).all())
 
 
-@pytest.mark.parametrize("N,H,W,C0,Cout,emits", [
+STATS_TILE_CASES = [
     (12, 48, 160, 64, 64, True),         # encoder layer 1: 8 x 16 tiles, interior
     (12, 24, 80, 128, 128, True),        # layer 2 (small-grid WPF variant, two channel tiles)
     (12, 12, 40, 256, 256, True),        # layer 3: 6 x 20 tiles (120 of 128 MFMA rows valid)
@@ -245,17 +245,35 @@ def test_conv3x3_hp_dynamic_range_and_specials():
     (10, 21, 45, 64, 128, True),         # ragged, two channel tiles
     (12, 6, 20, 512, 512, "reduce"),     # split-K grid: the statistics come out of the reduce launch, one triple per block of the reduce launch
     (12, 6, 20, 256, 512, "reduce"),
-])
-def test_conv3x3_hp_emits_batchnorm_partials(N, H, W, C0, Cout, emits):
+]
+
+
+# both operand formats, as the backward sibling below; the fp16-pair cases keep the ids they have always had
+@pytest.mark.parametrize("N,H,W,C0,Cout,emits,fmt", [
+    pytest.param(*c, fmt, id=("" if fmt == "fp16_pair" else fmt + "-") + "-".join(str(v) for v in c))
+    for fmt in ("fp16_pair", "exact") for c in STATS_TILE_CASES])
+def test_conv3x3_hp_emits_batchnorm_partials(N, H, W, C0, Cout, emits, fmt):
     """fp_aux.bn_part: the forward tile convolution in front of a train-mode BatchNorm writes (count, mean, M2) per pixel tile and
-    channel of what it stores; fp_bn_train_stats_partials turns them into the same coefficients as fp_bn_train_stats on the tensor"""
+    channel of what it stores; fp_bn_train_stats_partials turns them into the same coefficients as fp_bn_train_stats on the tensor.
+    "exact": the same sink behind fp_conv3x3_bf3 (bf16x3 operands; the engine's default since round 5)"""
     ops, L = _ops()
+    hp = fmt == "fp16_pair"
     w = rnd((Cout, C0, 3, 3), 601, -0.1, 0.1)
     x = rnd((N, C0, H, W), 602) * 2.0 + 0.75                      # a mean of the order of the spread, like post-ReLU activations
     d = ops.make_desc(N, H, W, H, W, C0, 0, Cout, 3, 1, 1, L.GATHER_FWD_ZERO)
     y = torch.empty((N, H, W, Cout), device="cuda")
-    wp, sw = pack_hp(w)
+    if hp:
+        wp, sw = pack_hp(w)
+    else:
+        from tests.test_gpu_kernels import pack_bf3
+        wp, sw = pack_bf3(w), None
     xs = nhwc(x)
+
+    def conv(dst, bn_out=None):
+        if hp:
+            ops.conv3x3_hp(d, xs, wp, dst, slot_of(xs), sw, bn_out=bn_out)
+        else:
+            ops.conv3x3_bf3(d, xs, wp, dst, bn_out=bn_out)
     cap = N * ((H + 5) // 6) * ((W + 15) // 16) * Cout * 3
     rows = 256 // (Cout // 4) * 4
     nred = min(512, (N * H * W + rows - 1) // rows)
@@ -263,7 +281,7 @@ def test_conv3x3_hp_emits_batchnorm_partials(N, H, W, C0, Cout, emits):
         cap = max(cap, nred * Cout * 3)
     part = torch.full((cap,), float("nan"), device="cuda")
     cell = ops.bn_stats_out(part)
-    ops.conv3x3_hp(d, xs, wp, y, slot_of(xs), sw, bn_out=cell)
+    conv(y, cell)
     torch.cuda.synchronize()
     expect_tiles = cell.nblk
     if emits == "reduce":
@@ -272,7 +290,7 @@ def test_conv3x3_hp_emits_batchnorm_partials(N, H, W, C0, Cout, emits):
         assert expect_tiles in ((N * ((H + 7) // 8) * ((W + 15) // 16), N * ((H + 5) // 6) * ((W + 19) // 20)) if emits else (0,))
     check(nchw(y), F.conv2d(x.double(), w.double(), None, 1, 1), "hp forward with statistics sink", 2e-6)
     y2 = torch.empty_like(y)                                       # the sink is one-shot: the next launch emits nothing
-    ops.conv3x3_hp(d, xs, wp, y2, slot_of(xs), sw)
+    conv(y2)
     assert torch.equal(y, y2)
     if expect_tiles == 0:
         assert bool(torch.isnan(part).all())
