@@ -31,6 +31,19 @@ class PackJob(C.Structure):
         "Cout", "Cin", "KH", "KW", "kind", "c_begin", "c_count", "block_begin", "block_count")] + [("amax", C.c_void_p)]
 
 
+RESIZE_LANCZOS, RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_BOX = 1, 2, 3, 4        # FP_RESIZE_*: Pillow's Image.Resampling numbers
+
+
+class ResizeTable(C.Structure):
+    """fp_resize_table (include/footprints_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("in_size", "out_size", "ksize", "bounds_off", "kk_off")]
+
+
+class ResizeSample(C.Structure):
+    """fp_resize_sample (include/footprints_hip.h)"""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("table_h", C.c_int32), ("table_v", C.c_int32)]
+
+
 _P, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _DESC = C.POINTER(ConvDesc)
 
@@ -70,6 +83,15 @@ SIGNATURES = {
     "fp_aug_params_bytes": (_I32, []),
     "fp_assemble_images": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "fp_assemble_labels": (C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _D, _D, _D, _P]),
+    "fp_resize_ksize": (_I32, [_I32, _I32, _I32]),
+    "fp_resize_coeffs": (C.c_int, [_I32, _I32, _I32, _P, _P, _I32]),
+    "fp_resize_table_bytes": (_I32, []),
+    "fp_resize_sample_bytes": (_I32, []),
+    "fp_resize_workspace": (_I64, [_I32, _I32, _I32, _I32]),
+    "fp_resize_status_offset": (_I64, [_I32, _I32, _I32, _I32]),
+    "fp_resize_u8": (C.c_int, [_P, _I64, _P, _P, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_filter_depth_mask_workspace": (_I64, [_I32, _I32, _I32]),
+    "fp_filter_depth_mask": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P, _I64, _P]),
     "fp_adaptive_avgpool_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "fp_adaptive_avgpool_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, C.c_int, _P]),
     "fp_bilinear_ac_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),

@@ -6,6 +6,12 @@ matterport_dataset.py:69-97.  At ~650 img/s per GPU the reference's 8 PIL worker
 host only hands over what the file readers produce -- the resized uint8 image and the resized label maps of every sample -- plus a
 36-byte parameter record per sample, and two kernels (csrc/data_path.hip) assemble the whole batch in the reference's schema.
 
+Two more pieces of the reader can run on the device, both opt-in (csrc/reader.hip): with `raw_images=True` a sample's image is the DECODED
+frame at its native size (KITTI frames come in several) and `Image.resize((W, H), LANCZOS)` (footprint_dataset.py:73-80) runs in front of
+the flip and the jitter, in the reference's order and byte for byte Pillow's 8-bit path; with `filter_depth_mask=True` the depth mask
+arrives unfiltered and the connected-components filter (footprint_dataset.py:96-105) runs in front of the label algebra.  The cv2 resizes
+of the label maps (INTER_AREA / INTER_NEAREST on float64, footprint_dataset.py:82-94) stay on the host: no cv2 was at hand to pin them.
+
 Random decisions stay on the host and consume Python's `random` exactly like the reference does (flip draw, colour-aug draw, then
 torchvision 0.4.2's ColorJitter.get_params: four uniforms in the order brightness, contrast, saturation, hue and one shuffle), so a
 seeded run makes the same decisions as the reference pipeline.  Byte arithmetic is bit-exact with Pillow 12 (tests).
@@ -60,13 +66,21 @@ class DeviceBatchAssembler:
 
     samples: list of (image uint8 [H,W,3], {map name: [H,W] array}) as the file readers deliver them (resized, NOT flipped; the depth
     mask already through filter_depth_mask).  map_dtype float64 reproduces the reference's numpy arithmetic bit for bit; float32
-    halves the H2D bytes (inputs rounded once before the same float64 algebra)."""
+    halves the H2D bytes (inputs rounded once before the same float64 algebra).
+
+    raw_images=True: the image of a sample is the decoded frame uint8 [h,w,3] at its native size, any h <= max_src_hw[0] and
+    w <= max_src_hw[1] (they size the staging buffers), and is resized with Pillow's LANCZOS on the device.  filter_depth_mask=True:
+    the depth mask of a sample is the unfiltered one (zeros and ones)."""
 
     def __init__(self, batch_size, height, width, dataset="kitti", map_dtype=np.float64, slots=3, no_depth_mask=False,
                  project_down_baseline=False, moving_objects_method="ours", footprint_threshold=0.75, baseline=0.54,
-                 depth_scaling=0.25e-3, device="cuda", stream=None):
+                 depth_scaling=0.25e-3, device="cuda", stream=None, raw_images=False, max_src_hw=None, filter_depth_mask=False):
         if dataset not in MAP_KEYS:
             raise ValueError("dataset must be 'kitti' or 'matterport'")
+        if raw_images and (max_src_hw is None or min(max_src_hw) <= 0):
+            raise ValueError("raw_images=True needs max_src_hw=(largest source height, largest source width)")
+        self.raw_images, self.filter_mask = bool(raw_images), bool(filter_depth_mask)
+        self.max_src_hw = tuple(int(v) for v in max_src_hw) if raw_images else None
         _lib.load()
         assert _lib.load().fp_aug_params_bytes() == C.sizeof(AugParams)
         self.B, self.H, self.W, self.dataset = batch_size, height, width, dataset
@@ -95,6 +109,7 @@ class DeviceBatchAssembler:
         npx = batch_size * height * width
         tdt = torch.float64 if self.map_dtype == np.float64 else torch.float32
         self.slots = []
+        self.tables = ops.resize_table_set(self.device) if self.raw_images else None
         for _ in range(slots):
             h_img = torch.empty((batch_size, height, width, 3), dtype=torch.uint8).pin_memory()
             h_maps = torch.empty((len(self.keys), batch_size, height, width), dtype=tdt).pin_memory()
@@ -106,6 +121,11 @@ class DeviceBatchAssembler:
                 image=torch.empty((batch_size, 3, height, width), device=self.device),
                 out=torch.empty((len(OUT_KEYS), batch_size, height, width), device=self.device),
                 ready=torch.cuda.Event(), consumed=None, launched=False))
+            if self.raw_images:             # the packed native-size frames and their fp_resize_sample records
+                h_src = torch.empty(batch_size * self.max_src_hw[0] * self.max_src_hw[1] * 3, dtype=torch.uint8).pin_memory()
+                h_rec = torch.empty(batch_size * C.sizeof(_lib.ResizeSample), dtype=torch.uint8).pin_memory()
+                self.slots[-1].update(h_src=h_src, h_rec=h_rec, d_src=torch.empty_like(h_src, device=self.device),
+                                      d_rec=torch.empty_like(h_rec, device=self.device), src_bytes=0)
         self._next = 0
         assert npx > 0
 
@@ -121,8 +141,14 @@ class DeviceBatchAssembler:
         if s["launched"]:
             s["ready"].synchronize()                         # the pinned buffers are free once the slot's last copies have landed
         img_np, maps_np = s["h_img"].numpy(), s["h_maps"].numpy()
+        if self.raw_images:
+            images = [img for img, _ in samples]
+            if any(im.ndim != 3 or im.shape[2] != 3 or im.shape[0] > self.max_src_hw[0] or im.shape[1] > self.max_src_hw[1] for im in images):
+                raise ValueError("raw images must be uint8 [h, w, 3] within max_src_hw = %r" % (self.max_src_hw,))
+            s["src_bytes"] = ops.resize_pack(images, self.H, self.W, self.tables, packed=s["h_src"].numpy(), records=s["h_rec"].numpy())[2]
         for b, (img, maps) in enumerate(samples):
-            img_np[b] = img
+            if not self.raw_images:
+                img_np[b] = img
             for k, key in enumerate(self.keys):
                 maps_np[k, b] = maps[key]
         arr = (AugParams * self.B)(*params)
@@ -136,9 +162,18 @@ class DeviceBatchAssembler:
         if s["consumed"] is not None:
             self.stream.wait_event(s["consumed"])            # the consumer finished reading this slot's outputs
         with ops.on_stream(self.stream):
-            s["d_img"].copy_(s["h_img"], non_blocking=True)
+            if self.raw_images:                 # Image.resize first, like the reference (footprint_dataset.py:77), straight into d_img
+                n = s["src_bytes"]
+                s["d_src"][:n].copy_(s["h_src"][:n], non_blocking=True)
+                s["d_rec"].copy_(s["h_rec"], non_blocking=True)
+                ops.resize_u8_packed(s["d_src"], n, s["d_rec"], self.B, self.H, self.W, 3, self.max_src_hw[0], self.max_src_hw[1], self.tables,
+                                     out=s["d_img"])
+            else:
+                s["d_img"].copy_(s["h_img"], non_blocking=True)
             s["d_maps"].copy_(s["h_maps"], non_blocking=True)
             s["d_par"].copy_(s["h_par"], non_blocking=True)
+            if self.filter_mask:                # filter_depth_mask in place, in front of the label algebra
+                ops.filter_depth_mask(s["d_maps"][2], out=s["d_maps"][2])
             lib = _lib.load()
             st = ops.stream()
             _lib.check(lib.fp_assemble_images(s["d_img"].data_ptr(), s["d_par"].data_ptr(), s["sums"].data_ptr(), s["image"].data_ptr(),
@@ -228,18 +263,20 @@ class DeviceLoader:
 
 
 class SyntheticSampleSource:
-    """`steps` batches of host samples with the shapes / dtypes the file readers deliver (stand-in for the KITTI reader, which is out
-    of scope): a small pool of random samples, cycled."""
+    """`steps` batches of host samples with the shapes / dtypes the file readers deliver (stand-in for the KITTI reader, whose file
+    decoding stays on the host): a small pool of random samples, cycled.  raw_hw: a list of (h, w) -- the images are then decoded frames
+    at these native sizes, taken in turn (for DeviceBatchAssembler(raw_images=True)); the label maps stay at height x width."""
 
-    def __init__(self, batch_size, height, width, steps, seed=10, pool=24):
+    def __init__(self, batch_size, height, width, steps, seed=10, pool=24, raw_hw=None):
         rng = np.random.default_rng(seed)
         self.B, self.steps, self.first, self.stride = batch_size, steps, 0, 1
         self.pool = []
-        for _ in range(pool):
+        for j in range(pool):
             maps = {"visible_ground": rng.random((height, width)), "ground_depth": rng.random((height, width)) * 30 * (rng.random((height, width)) < 0.5),
                     "depth_mask": (rng.random((height, width)) < 0.1).astype(np.float64), "disparity": rng.random((height, width)) * 60,
                     "moving_objects": (rng.random((height, width)) < 0.05).astype(np.float64)}
-            self.pool.append((rng.integers(0, 256, (height, width, 3), dtype=np.uint8), maps))
+            ih, iw = raw_hw[j % len(raw_hw)] if raw_hw else (height, width)
+            self.pool.append((rng.integers(0, 256, (ih, iw, 3), dtype=np.uint8), maps))
         self.dataset = range(steps * batch_size)
 
     def __len__(self):

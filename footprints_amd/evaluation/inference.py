@@ -5,7 +5,9 @@ The reference takes `model(image)['1/1']`, applies the sigmoid to the two mask c
 fp32 to the CPU and lets every `save_result` cast to float16.  Here the network evaluates only the full-resolution heads
 (`inference_scales`), the encoder BatchNorm is folded into the convolutions, and one kernel (`fp_pack_pred_fp16`) applies the
 sigmoid and rounds to float16 on the device, so the D2H copy is half the bytes and `save_result` writes the array as is.
-The dataset / dataloader side (KITTI, Matterport, handheld readers) is outside this build's scope.
+File decoding (KITTI, Matterport, handheld readers) stays on the host; the reader's `Image.resize((W, H), LANCZOS)` + ToTensor
+(datasets/inference_dataset.py:26,48) can run on the device: `InferenceManager(..., device_resize=True, height_width=(H, W))` takes
+`inputs['raw_image']`, the decoded uint8 frames at their native sizes, uploads them once and produces the same input tensor bit for bit.
 """
 import os
 
@@ -17,7 +19,10 @@ from ..model_manager import ModelManager
 
 
 class InferenceManager:
-    def __init__(self, load_path=None, model_manager=None, save_path=None):
+    def __init__(self, load_path=None, model_manager=None, save_path=None, device_resize=False, height_width=None):
+        if device_resize and height_width is None:
+            raise ValueError("device_resize=True needs height_width=(H, W), the network's input size")
+        self.device_resize, self.height_width = bool(device_resize), height_width
         if model_manager is None:
             model_manager = ModelManager(use_cuda=True, is_inference=True)
             if load_path is not None:
@@ -28,9 +33,16 @@ class InferenceManager:
         self.model.inference_scales = ("1/1",)          # "just take max resolution prediction" (inference.py:104)
         self.savepath = save_path
 
+    def input_tensor(self, inputs):
+        """the network's input [B,3,H,W] on the device"""
+        if self.device_resize:
+            return ops.load_images_u8([np.asarray(im, dtype=np.uint8) for im in inputs["raw_image"]], *self.height_width)
+        return inputs["image"].cuda(non_blocking=True)
+
     def test_batch(self, inputs):
-        """inputs['image']: [B,3,H,W] float tensor.  Returns a float16 numpy array [B,4,H,W]: sigmoid(mask logits), depth."""
-        image = inputs["image"].cuda(non_blocking=True)
+        """inputs['image']: [B,3,H,W] float tensor -- or, with device_resize, inputs['raw_image']: list of B decoded uint8 [h,w,3] frames.
+        Returns a float16 numpy array [B,4,H,W]: sigmoid(mask logits), depth."""
+        image = self.input_tensor(inputs)
         with torch.no_grad():
             pred = self.model(image)["1/1"]
             return ops.pack_pred_fp16(pred).cpu().numpy()

@@ -1062,3 +1062,200 @@ def gt_depth_mask(keys, depth, ground_seg, want_projection=False):
     proj = torch.empty((H, W), dtype=torch.float32, device=depth.device) if want_projection else None
     _lib.check(_lib.load().fp_gt_depth_mask(k, d, g, H, W, _chk(mask), _chk(proj) if want_projection else None, stream()), "fp_gt_depth_mask")
     return (mask.view(torch.bool), proj) if want_projection else mask.view(torch.bool)
+
+
+# ---- reader work on the device: Pillow's 8-bit resize and filter_depth_mask (csrc/reader.hip) -----------------------------------------
+RESIZE_FILTERS = {"lanczos": _lib.RESIZE_LANCZOS, "bilinear": _lib.RESIZE_BILINEAR, "bicubic": _lib.RESIZE_BICUBIC, "box": _lib.RESIZE_BOX}
+_resize_host_tables = {}
+
+
+def _resize_filter(f):
+    f = RESIZE_FILTERS.get(f, f) if isinstance(f, str) else int(f)
+    if f not in RESIZE_FILTERS.values():
+        raise ValueError("footprints_amd.ops: resize filter must be one of %s (or Pillow's number of one)" % sorted(RESIZE_FILTERS))
+    return f
+
+
+def resize_tables(in_size, out_size, filter="lanczos"):
+    """Pillow's coefficient tables of one axis, built by the library on the host in double (no GPU needed) and cached per
+    (in, out, filter) -> (bounds int32 [out, 2] = first source index and tap count, kk int32 [out, ksize] in 22-bit fixed point)"""
+    import numpy as np
+    key = (int(in_size), int(out_size), _resize_filter(filter))
+    t = _resize_host_tables.get(key)
+    if t is None:
+        lib = _lib.load()
+        ksize = lib.fp_resize_ksize(*key)
+        if ksize < 0:
+            raise ValueError("footprints_amd.ops.resize_tables: bad sizes %r" % (key,))
+        bounds, kk = np.empty((key[1], 2), np.int32), np.empty((key[1], ksize), np.int32)
+        _lib.check(lib.fp_resize_coeffs(key[0], key[1], key[2], bounds.ctypes.data, kk.ctypes.data, ksize), "fp_resize_coeffs")
+        bounds.setflags(write=False)
+        kk.setflags(write=False)
+        t = _resize_host_tables[key] = (bounds, kk)
+    return t
+
+
+class ResizeTableSet:
+    """The axis tables one device has seen, in one int32 buffer plus one fp_resize_table record each.  `index` is host work (fill time);
+    `device()` uploads when a table was added since the last upload -- once per distinct (in, out, filter) -- on the current stream."""
+
+    def __init__(self, device):
+        import threading
+        self.device = torch.device(device)
+        self.lock = threading.Lock()           # a loader's worker thread asks for indices while the main thread uploads
+        self.keys, self.records, self.coeffs, self.length = {}, [], [], 0
+        self.uploaded, self.d_tables, self.d_coeffs = 0, None, None
+
+    def index(self, in_size, out_size, filter="lanczos"):
+        """index of the (in -> out) table; -1 when the sizes agree (the pass is skipped, as in Pillow)"""
+        if in_size == out_size:
+            return -1
+        key = (int(in_size), int(out_size), _resize_filter(filter))
+        with self.lock:
+            i = self.keys.get(key)
+            if i is None:
+                bounds, kk = resize_tables(*key)
+                i = self.keys[key] = len(self.records)
+                self.records.append(_lib.ResizeTable(key[0], key[1], kk.shape[1], self.length, self.length + bounds.size))
+                self.coeffs += [bounds.reshape(-1), kk.reshape(-1)]
+                self.length += bounds.size + kk.size
+        return i
+
+    def device_buffers(self):
+        """(table records, count, coefficient buffer) on the device"""
+        import numpy as np
+        with self.lock:
+            n = len(self.records)
+            if n != self.uploaded:
+                # queued launches may still read the superseded buffers: let go of them as every replaced device buffer is
+                release(self.d_tables, "resize_tables")
+                release(self.d_coeffs, "resize_coeffs")
+                rec = np.frombuffer(b"".join(bytes(r) for r in self.records), dtype=np.uint8).copy()
+                self.d_tables = torch.from_numpy(rec).to(self.device)
+                self.d_coeffs = torch.from_numpy(np.concatenate(self.coeffs)).to(self.device)
+                self.uploaded = n
+                bump_alloc_generation()
+            return self.d_tables, n, self.d_coeffs
+
+
+_resize_table_sets = {}
+
+
+def resize_table_set(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    s = _resize_table_sets.get(device)
+    if s is None:
+        assert _lib.load().fp_resize_table_bytes() == C.sizeof(_lib.ResizeTable) and _lib.load().fp_resize_sample_bytes() == C.sizeof(_lib.ResizeSample)
+        s = _resize_table_sets[device] = ResizeTableSet(device)
+    return s
+
+
+def resize_pack(images, H, W, tables, filter="lanczos", packed=None, records=None):
+    """host half of a resize: the images (uint8 [h, w, C] or [h, w], all the same C) one after the other in `packed` (a uint8 numpy
+    buffer, allocated when None) and their fp_resize_sample records in `records` (uint8 numpy view, allocated when None)
+    -> (packed, records, bytes used, C, max_h, max_w)"""
+    import numpy as np
+    B = len(images)
+    shapes = [(im.shape[0], im.shape[1], 1 if im.ndim == 2 else im.shape[2]) for im in images]
+    Cn = shapes[0][2]
+    if Cn not in (1, 3) or any(s[2] != Cn for s in shapes) or any(im.dtype != np.uint8 for im in images):
+        raise ValueError("footprints_amd.ops.resize_pack: images must be uint8 [h, w] or [h, w, C] with one C of 1 or 3")
+    total = sum(h * w * c for h, w, c in shapes)
+    if packed is None:
+        packed = np.empty(total, np.uint8)
+    if total > packed.size:
+        raise ValueError("footprints_amd.ops.resize_pack: the batch needs %d source bytes, the buffer holds %d" % (total, packed.size))
+    rec = (_lib.ResizeSample * B)()
+    off = 0
+    for b, (im, (h, w, c)) in enumerate(zip(images, shapes)):
+        packed[off:off + h * w * c] = im.reshape(-1)
+        rec[b] = _lib.ResizeSample(off, h, w, tables.index(w, W, filter), tables.index(h, H, filter))
+        off += h * w * c
+    raw = np.frombuffer(bytes(rec), dtype=np.uint8)
+    if records is None:
+        records = raw.copy()
+    else:
+        records[:raw.size] = raw
+    return packed, records, total, Cn, max(s[0] for s in shapes), max(s[1] for s in shapes)
+
+
+def resize_u8_packed(src, src_bytes, samples, B, H, W, Cn, max_h, max_w, tables, out=None, check=False):
+    """device half: `src` (uint8 device buffer holding the packed images), `samples` (uint8 device buffer holding B fp_resize_sample
+    records) -> uint8 [B, H, W, C] -- the layout fp_assemble_images reads -- on the current launch stream.  The kernels turn down a
+    record that points outside a buffer or names a table that does not fit its sizes and leave that sample unwritten; check=True reads
+    the library's status word afterwards (this WAITS for the stream) and raises ValueError then -- for records the caller built itself;
+    resize_pack's are right by construction."""
+    lib = _lib.load()
+    d_tables, n_tables, d_coeffs = tables.device_buffers()
+    if out is None:
+        out = torch.empty((B, H, W, Cn), dtype=torch.uint8, device=src.device)
+    if out.numel() != B * H * W * Cn or out.dtype != torch.uint8 or src.dtype != torch.uint8 or src.numel() < src_bytes:
+        raise RuntimeError("footprints_amd.ops.resize_u8_packed: out must be uint8 [B, H, W, C] and src hold src_bytes bytes")
+    if samples.numel() * samples.element_size() < B * C.sizeof(_lib.ResizeSample):
+        raise RuntimeError("footprints_amd.ops.resize_u8_packed: fewer than B sample records")
+    need = lib.fp_resize_workspace(B, max_h, W, Cn)
+    if need < 0:
+        raise RuntimeError("footprints_amd.ops.resize_u8_packed: bad sizes")
+    ws = workspace(need, src.device, "resize")
+    _lib.check(lib.fp_resize_u8(_chk(src, "src"), int(src_bytes), _chk(samples, "samples"), _chk(d_tables) if n_tables else None, n_tables,
+                                _chk(d_coeffs) if n_tables else None, d_coeffs.numel() if n_tables else 0, _chk(out, "out"), B, H, W, Cn,
+                                max_h, max_w, ws.data_ptr(), ws.numel(), stream()), "fp_resize_u8")
+    if check:
+        off = lib.fp_resize_status_offset(B, max_h, W, Cn)
+        if int(ws[off:off + 4].view(torch.int32).item()) != 0:
+            raise ValueError("footprints_amd.ops.resize_u8_packed: a sample or table record was turned down on the device; its output is unwritten")
+    return out
+
+
+def resize_u8(images, H, W, filter="lanczos", device="cuda"):
+    """PIL.Image.resize((W, H), filter) of a batch of uint8 images of any (mixed) sizes, byte for byte, in one library call:
+    images = list of numpy uint8 [h, w, 3], [h, w, 1] or [h, w] -> uint8 device tensor [B, H, W, C]"""
+    tables = resize_table_set(device)
+    packed, records, total, Cn, max_h, max_w = resize_pack(images, H, W, tables, filter)
+    src = torch.from_numpy(packed).to(tables.device)
+    rec = torch.from_numpy(records).to(tables.device)
+    return resize_u8_packed(src, total, rec, len(images), H, W, Cn, max_h, max_w, tables)
+
+
+def filter_depth_mask_workspace_bytes(B, H, W):
+    n = _lib.load().fp_filter_depth_mask_workspace(B, H, W)
+    if n < 0:
+        raise RuntimeError("footprints_amd.ops.filter_depth_mask: B x H x W = %d x %d x %d is too large" % (B, H, W))
+    return n
+
+
+def filter_depth_mask(mask, out=None):
+    """the reference's filter_depth_mask on the device: mask [B, H, W] or [H, W], float32 or float64 holding 0 / 1 -> same shape and type,
+    1 on the 8-connected components of ones smaller than W * H / 100 pixels.  `out` may be `mask` (in place)."""
+    if mask.dtype not in (torch.float32, torch.float64) or mask.dim() not in (2, 3):
+        raise RuntimeError("footprints_amd.ops.filter_depth_mask: mask must be float32 or float64 [B, H, W] or [H, W]")
+    H, W = mask.shape[-2:]
+    B = mask.numel() // (H * W)
+    out = torch.empty_like(mask) if out is None else out
+    if out.shape != mask.shape or out.dtype != mask.dtype:
+        raise RuntimeError("footprints_amd.ops.filter_depth_mask: out must match the mask")
+    ws = workspace(filter_depth_mask_workspace_bytes(B, H, W), mask.device, "ccl")
+    _lib.check(_lib.load().fp_filter_depth_mask(_chk(mask, "mask"), int(mask.dtype == torch.float64), _chk(out, "out"), B, H, W, ws.data_ptr(),
+                                                ws.numel(), stream()), "fp_filter_depth_mask")
+    return out
+
+
+def to_tensor_u8(images_hwc):
+    """ToTensor on the device: uint8 [B, H, W, 3] -> float32 [B, 3, H, W] in [0, 1] (fp_assemble_images without flip or jitter)"""
+    B, H, W, Cn = images_hwc.shape
+    if Cn != 3 or images_hwc.dtype != torch.uint8:
+        raise RuntimeError("footprints_amd.ops.to_tensor_u8: images must be uint8 [B, H, W, 3]")
+    dev = images_hwc.device
+    params = torch.zeros(B * _lib.load().fp_aug_params_bytes(), dtype=torch.uint8, device=dev)        # flip = 0, n_ops = 0
+    sums = torch.empty(B, dtype=torch.int64, device=dev)
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().fp_assemble_images(_chk(images_hwc, "images"), _chk(params), _chk(sums), _chk(out), B, H, W, stream()), "fp_assemble_images")
+    return out
+
+
+def load_images_u8(images, H, W, filter="lanczos", device="cuda"):
+    """Resize((H, W)) + ToTensor of decoded RGB frames (numpy uint8 [h, w, 3], any sizes) on the device: one upload of the raw bytes
+    -> float32 [B, 3, H, W], bit-equal to PIL's resize followed by a division by 255 in float32"""
+    return to_tensor_u8(resize_u8(images, H, W, filter, device))

@@ -24,16 +24,22 @@ MODEL_HEIGHT_WIDTH = {"kitti": (192, 640), "matterport": (512, 640), "handheld":
 IMAGE_EXTENSIONS = {".jpg", ".jpeg", ".png"}
 
 
-def preprocess(pil_image, height_width):
-    """Resize((H,W), ANTIALIAS) + ToTensor + [None] (predict_simple.py:51-60) -> float32 [1,3,H,W] in [0,1]."""
+def preprocess(pil_image, height_width, device_resize=False):
+    """Resize((H,W), ANTIALIAS) + ToTensor + [None] (predict_simple.py:51-60) -> float32 [1,3,H,W] in [0,1].
+    device_resize=True: the decoded frame is uploaded once and both steps run on the GPU (csrc/reader.hip: Pillow's LANCZOS byte for
+    byte, then the division by 255); the result is a device tensor bit-equal to the host path's."""
     h, w = height_width
+    if device_resize:
+        from . import ops
+        return ops.load_images_u8([np.asarray(pil_image, dtype=np.uint8)], h, w)
     resized = pil_image.resize((w, h), Image.LANCZOS)
     arr = np.asarray(resized, dtype=np.uint8).astype(np.float32) / 255.0
     return torch.from_numpy(arr).permute(2, 0, 1)[None].contiguous()
 
 
 class InferenceManager:
-    def __init__(self, model_name, save_dir, use_cuda=True, save_visualisations=True, weights_path=None, model_manager=None):
+    def __init__(self, model_name, save_dir, use_cuda=True, save_visualisations=True, weights_path=None, model_manager=None,
+                 device_resize=False):
         if not use_cuda or not torch.cuda.is_available():
             raise RuntimeError("footprints_amd.predict_simple needs a MI355X: the package has no CPU compute path "
                                "(--no_cuda is accepted for CLI compatibility only)")
@@ -45,6 +51,7 @@ class InferenceManager:
         self.model_manager = model_manager
         self.model_manager.model.eval()
         self.model_manager.model.inference_scales = ("1/1",)      # only the full-resolution prediction is consumed below
+        self.device_resize = bool(device_resize)
         self.save_dir = save_dir
         os.makedirs(os.path.join(save_dir, "outputs"), exist_ok=True)
         self.save_visualisations = save_visualisations
@@ -52,7 +59,7 @@ class InferenceManager:
             os.makedirs(os.path.join(save_dir, "visualisations"), exist_ok=True)
 
     def predict_array(self, pil_image):
-        x = preprocess(pil_image, self.height_width).cuda()
+        x = preprocess(pil_image, self.height_width, self.device_resize).cuda()
         with torch.no_grad():
             pred = self.model_manager.model(x)
         return pred["1/1"].cpu().numpy().squeeze(0)          # [4,H,W]
@@ -120,13 +127,15 @@ def parse_args(argv=None):
     ap.add_argument("--save_dir", type=str, default="predictions", help="output root (outputs/ and visualisations/ below it)")
     ap.add_argument("--weights", type=str, default=None,
                     help="folder holding model.pth (default: %s/<model>; this build cannot download)" % MODEL_DIR)
+    ap.add_argument("--device_resize", action="store_true", help="resize the decoded image on the GPU (same bytes as PIL's LANCZOS)")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
     manager = InferenceManager(model_name=args.model, use_cuda=torch.cuda.is_available() and not args.no_cuda,
-                               save_visualisations=not args.no_save_vis, save_dir=args.save_dir, weights_path=args.weights)
+                               save_visualisations=not args.no_save_vis, save_dir=args.save_dir, weights_path=args.weights,
+                               device_resize=args.device_resize)
     manager.predict(image_path=args.image)
 
 

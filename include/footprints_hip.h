@@ -487,6 +487,52 @@ int fp_assemble_labels(const void* visible_ground, const void* ground_depth, con
                        int32_t no_depth_mask, int32_t project_down_baseline, int32_t use_moving, double threshold, double fxb,
                        double depth_scaling, fp_stream_t stream);
 
+/* ---- device-side reader work: Pillow's 8-bit Image.resize and filter_depth_mask (footprint_dataset.py:73-80, :96-105; csrc/reader.hip) ---- */
+/* Resample filters, numbered like Pillow's Image.Resampling.  NEAREST (0) and the mode-"F" paths are not provided. */
+#define FP_RESIZE_LANCZOS 1
+#define FP_RESIZE_BILINEAR 2
+#define FP_RESIZE_BICUBIC 3
+#define FP_RESIZE_BOX 4
+/* HOST functions (no GPU needed): Resample.c's coefficient tables of one axis.  ksize = 2 * ceil(support * max(in / out, 1)) + 1 (-1 on bad
+ * arguments); bounds int32 [out][2] = first source index and tap count, kk int32 [out][ksize] = the taps in 22-bit fixed point, rows padded
+ * with zeros.  Built in double exactly as Pillow builds them. */
+int32_t fp_resize_ksize(int32_t in_size, int32_t out_size, int32_t filter);
+int fp_resize_coeffs(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* kk, int32_t ksize);
+/* one axis table inside the int32 coefficient buffer on the device; fp_resize_table_bytes() == sizeof(fp_resize_table) */
+typedef struct fp_resize_table {
+  int32_t in_size, out_size, ksize;
+  int32_t bounds_off; /* element offsets into the coefficient buffer */
+  int32_t kk_off;
+} fp_resize_table;
+/* one source image of the batch; fp_resize_sample_bytes() == sizeof(fp_resize_sample) */
+typedef struct fp_resize_sample {
+  int64_t offset;  /* of its first byte in the packed source buffer; the image is uint8 [h][w][C], dense */
+  int32_t h, w;
+  int32_t table_h; /* index of its (w -> W) table; -1 = w == W, no horizontal pass */
+  int32_t table_v; /* index of its (h -> H) table; -1 = h == H, no vertical pass */
+} fp_resize_sample;
+int32_t fp_resize_table_bytes(void);
+int32_t fp_resize_sample_bytes(void);
+/* bytes of the workspace: the uint8 intermediate between the horizontal and the vertical pass (B * max_h * W * C) and, at
+ * fp_resize_status_offset, one int32 status word (-1 on bad arguments) */
+int64_t fp_resize_workspace(int32_t B, int32_t max_h, int32_t W, int32_t C);
+int64_t fp_resize_status_offset(int32_t B, int32_t max_h, int32_t W, int32_t C);
+/* B source images of different sizes (all h <= max_h, w <= max_w; C = 1 or 3), packed in `src` (4-byte aligned, src_bytes long) and
+ * described by `samples` (device, B records), -> out uint8 [B][H][W][C], byte for byte what PIL.Image.resize((W, H), filter) gives:
+ * horizontal pass into the uint8 workspace, then the vertical pass, a pass whose sizes agree skipped, int32 arithmetic throughout.
+ * tables: n_tables device records over `coeffs` (device int32, coeffs_len elements).  A record that points outside a buffer, or whose
+ * table does not fit its sizes, leaves that sample's output unwritten and sets the workspace's status word to 1 (every call clears it
+ * first; read it after the stream has finished).  max_w * C <= 65528 (a source row is staged in LDS). */
+int fp_resize_u8(const uint8_t* src, int64_t src_bytes, const void* samples, const void* tables, int32_t n_tables, const int32_t* coeffs,
+                 int64_t coeffs_len, uint8_t* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t max_h, int32_t max_w, void* workspace,
+                 int64_t workspace_bytes, fp_stream_t stream);
+/* filter_depth_mask: mask [B][H][W] (float32, or float64 when is_double; values 0 / 1) -> out, same type: 1 on every 8-connected component
+ * of ones with fewer than W * H / 100 pixels (compared in double, strictly), 0 elsewhere.  out may be the mask itself.  Integer atomics
+ * only: the result does not depend on scheduling.  workspace >= fp_filter_depth_mask_workspace(B, H, W) bytes (-1: too large). */
+int64_t fp_filter_depth_mask_workspace(int32_t B, int32_t H, int32_t W);
+int fp_filter_depth_mask(const void* mask, int32_t is_double, void* out, int32_t B, int32_t H, int32_t W, void* workspace,
+                         int64_t workspace_bytes, fp_stream_t stream);
+
 /* ---- pyramid pooling of the ground-segmentation network (footprints/preprocessing/segmentation/network.py:174-207) ---- */
 /* nn.AdaptiveAvgPool2d(P) (network.py:180,188): y[N][P][P][C] = window means of x[N][H][W][C]; windows floor(i*H/P) .. ceil((i+1)*H/P) */
 int fp_adaptive_avgpool_fwd(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t P, fp_stream_t stream);
