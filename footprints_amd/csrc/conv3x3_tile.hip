@@ -16,7 +16,7 @@
 // v_mfma_f32_32x32x2_f32 (same k permutation as the B fragment, so the dot product is unchanged).  Accumulation order
 // per output element: 16-channel chunks outer, taps inner (conv_igemm.hip: taps outer) -- both are plain fp32 fmaf
 // chains, equal to round-off but not bitwise.
-#include "fp_common.h"
+#include "conv_host.h"
 
 namespace {
 

@@ -14,15 +14,7 @@
 //   * weights are packed [tap][chunk][plane][n][16] bf16 (pack.hip, FP_PACK_*_BF3): a wave's B fragment of one plane is 1 KB contiguous.
 #include <type_traits>
 
-#include "fp_common.h"
-
-int fp_splitk_reduce_launch(const float* part, int SK, int64_t M, int Nout, const float* bias, const float* addend, const float* addend_mask,
-                            const float* actsrc, float* y, int act, unsigned epi, hipStream_t stream, unsigned* amax_out = nullptr);
-int fp_splitk_reduce_bnb_launch(const float* part, int SK, int64_t M, int Nout, const float* bias, const float* addend, const float* addend_mask,
-                                const float* actsrc, float* y, int act, unsigned epi, hipStream_t stream, unsigned* amax_out, const float* z,
-                                const float* mean, const float* invstd, float* bpart, int64_t cap_floats, int* rc_out);
-int fp_splitk_reduce_stats_launch(const float* part, int SK, int64_t M, int Nout, float* y, hipStream_t stream, unsigned* amax_out, float* stats,
-                                  int64_t cap_floats, int* rc_out);
+#include "conv_host.h"
 
 // waves per SIMD requested from the register allocator for the fp16-pair variants: 4 = 128 VGPRs (34 KB of LDS per workgroup allow four
 // workgroups per CU; the reflection-fold variants spill 3-4 registers).  Training step 15.16 / 15.24 vs 15.30 / 15.40 ms with 1 (= 160
@@ -58,7 +50,7 @@ struct Tile3Args {
   int act;
   unsigned epi;
   int tilesX, tilesY, tilesN, nwg;
-  int SK, chunksPerSplit;   // split-K over 16-channel chunks for small grids: raw partials [SK][N*OH*OW][Nout] -> fp_splitk_reduce_launch
+  int SK, chunksPerSplit;   // split-K over 16-channel chunks for small grids: raw partials [SK][N*OH*OW][Nout] -> fp_splitk_finish
   int wmajor;               // workgroup ids enumerate pixel tiles fastest, (channel tile, split) slowest
   float* part;
   // fp16-pair mode (HP): amax slots of the source tensor(s) and of the weights; optional slot receiving max |y| of this launch
@@ -888,57 +880,48 @@ extern "C" int64_t fp_conv3x3_bf3_workspace(const fp_conv_desc* d) {
 namespace {
 struct HpSlots { const unsigned* a; const unsigned* a1; const unsigned* w; unsigned* out; };
 
-int run_tile3(const char* who, const fp_conv_desc* d, const float* src, const float* src1, const void* wpacked, const float* bias,
-              const float* addend, const float* addend_mask, const float* actsrc, float* y, void* workspace, int64_t workspace_bytes,
-              const HpSlots* hp, const fp_aux* aux, hipStream_t stream) {
+// `e`: the epilogue operands with the descriptor's flags (fp_conv_epilogue_of)
+int run_tile3(const char* who, const fp_conv_desc* d, const float* src, const float* src1, const void* wpacked, FpConvEpilogue e, void* workspace,
+              int64_t workspace_bytes, const HpSlots* hp, const fp_aux* aux, hipStream_t stream) {
   const FpBnSink bn_sink = fp_bn_sink_of(aux);       // (zeroes *bn_nblk_out: an argument error below reports "nothing emitted")
-  FP_REQUIRE(d && src && wpacked && y, "fp_conv3x3_bf3 / fp_conv3x3_hp: null pointer");
+  FP_REQUIRE(d && src && wpacked && e.y, "%s: null pointer", who);
   const Plan3 p = plan3(d);
-  FP_REQUIRE(p.ok, "fp_conv3x3_bf3 / fp_conv3x3_hp: shape not supported (see fp_conv3x3_bf3_supported)");
-  FP_REQUIRE(!(d->epi & FP_EPI_BIAS) || bias, "fp_conv3x3_bf3 / fp_conv3x3_hp: bias missing");
-  FP_REQUIRE(!(d->epi & FP_EPI_ADDEND) || addend, "fp_conv3x3_bf3 / fp_conv3x3_hp: addend missing");
-  FP_REQUIRE(!(d->epi & FP_EPI_ADDEND_MASK) || addend_mask, "fp_conv3x3_bf3 / fp_conv3x3_hp: addend_mask missing");
-  FP_REQUIRE(!(d->epi & (FP_EPI_ACTGRAD_ELU | FP_EPI_ACTGRAD_RELU)) || actsrc, "fp_conv3x3_bf3 / fp_conv3x3_hp: actsrc missing");
-  FP_REQUIRE(p.SK <= 1 || (workspace && workspace_bytes >= fp_conv3x3_bf3_workspace(d)), "fp_conv3x3_bf3 / fp_conv3x3_hp: workspace too small");
-  FP_REQUIRE((int64_t)d->N * d->OH * d->OW * d->Nout < ((int64_t)1 << 29), "fp_conv3x3_bf3 / fp_conv3x3_hp: output larger than 2^29 elements");
+  FP_REQUIRE(p.ok, "%s: shape not supported (see fp_conv3x3_bf3_supported)", who);
+  if (const int rc = fp_conv_check_epilogue(who, d, e)) return rc;
+  FP_REQUIRE(p.SK <= 1 || (workspace && workspace_bytes >= fp_conv3x3_bf3_workspace(d)), "%s: workspace too small", who);
+  FP_REQUIRE((int64_t)d->N * d->OH * d->OW * d->Nout < ((int64_t)1 << 29), "%s: output larger than 2^29 elements", who);
   // operands are addressed with 32-bit byte offsets (raw buffer loads; bit 31 = "out of range, reads zero")
-  FP_REQUIRE((int64_t)d->N * d->IH * d->IW * (d->C0 + d->C1) * 4 < ((int64_t)1 << 31), "fp_conv3x3_bf3 / fp_conv3x3_hp: input larger than 2^31 bytes");
+  FP_REQUIRE((int64_t)d->N * d->IH * d->IW * (d->C0 + d->C1) * 4 < ((int64_t)1 << 31), "%s: input larger than 2^31 bytes", who);
+  e.epi &= ~(unsigned)FP_EPI_BF16X2;                 // that bit selects the operand format; it is no option of the epilogue
   Tile3Args a;
   a.bn_part = nullptr;
   a.bnb_part = nullptr; a.bnb_z = a.bnb_mean = a.bnb_invstd = nullptr;
   const bool up2 = d->gather == FP_GATHER_FWD_REFLECT_UP2;
-  FP_REQUIRE(!up2 || d->C1 == 0 || src1, "fp_conv3x3_bf3 / fp_conv3x3_hp: the concat gather needs the skip tensor (src1)");
+  FP_REQUIRE(!up2 || d->C1 == 0 || src1, "%s: the concat gather needs the skip tensor (src1)", who);
   a.src_lo = up2 ? src : nullptr; a.Clo = up2 ? d->C0 : 0;
-  a.src = up2 ? (d->C1 ? src1 : src) : src; a.w = (const unsigned short*)wpacked; a.bias = bias; a.addend = addend; a.addend_mask = addend_mask; a.actsrc = actsrc;
-  a.y = y;
+  a.src = up2 ? (d->C1 ? src1 : src) : src; a.w = (const unsigned short*)wpacked; a.bias = e.bias; a.addend = e.addend; a.addend_mask = e.addend_mask;
+  a.actsrc = e.actsrc; a.y = e.y;
   a.N = d->N; a.OH = d->OH; a.OW = d->OW; a.IH = d->IH; a.IW = d->IW; a.C = d->C0 + d->C1; a.Nout = d->Nout;
   a.KC16 = (d->C0 + d->C1 + 15) / 16;
   const bool flip = d->gather == FP_GATHER_DGRAD_ZERO || d->gather == FP_GATHER_DGRAD_REFLECT;
   const bool fold = d->gather == FP_GATHER_DGRAD_REFLECT;
   a.mode = (d->gather == FP_GATHER_FWD_REFLECT || up2) ? 1 : 0;
-  a.act = d->act; a.epi = d->epi & ~FP_EPI_BF16X2;
+  a.act = e.act; a.epi = e.epi;
   a.tilesX = p.tilesX; a.tilesY = p.tilesY; a.tilesN = p.tilesN; a.SK = p.SK; a.chunksPerSplit = p.chunksPerSplit;
   a.part = (float*)workspace;
   a.amax_a = hp ? hp->a : nullptr; a.amax_a1 = hp && up2 && d->C1 ? hp->a1 : nullptr; a.amax_w = hp ? hp->w : nullptr;
   a.amax_out = hp ? hp->out : nullptr;
-  {
-    // BatchNorm-statistics sink (fp_aux.bn_part): only the plain forward form on an unsplit grid emits -- its stored value is the
-    // accumulator itself -- everything else reports 0 blocks and the caller runs fp_bn_train_stats as before
+  // BatchNorm side output (fp_aux.bn_*; the rule: fp_common.h).  This kernel's own condition: it computes the forward statistics only in
+  // its forward-gather instantiations -- a data gradient with the forward form armed emits nothing, on either grid.
+  const bool sink_here = bn_sink.z || !flip;
+  if (p.SK <= 1 && sink_here) {                      // an unsplit grid emits from the kernel's epilogue, one block of partials per pixel tile
     const int64_t blocks = (int64_t)d->N * p.tilesY * p.tilesX;
-    bool emit;
-    if (bn_sink.z) {       // backward form (fp_aux.bnb_*): a data gradient on an unsplit grid that overwrites its output
-      emit = bn_sink.part && p.SK <= 1 && flip && !fold && !(d->epi & FP_EPI_ACCUM) && d->act == 0 && blocks * d->Nout * 2 <= bn_sink.cap_floats;
-      if (emit) { a.bnb_part = bn_sink.part; a.bnb_z = bn_sink.z; a.bnb_mean = bn_sink.mean; a.bnb_invstd = bn_sink.invstd; }
-    } else {
-      emit = bn_sink.part && p.SK <= 1 && !flip && (d->epi & ~(unsigned)FP_EPI_BF16X2) == 0 && d->act == 0 &&
-             blocks * d->Nout * 3 <= bn_sink.cap_floats;
-      if (emit) a.bn_part = bn_sink.part;
+    if (fp_bn_sink_bwd_ok(bn_sink, d->gather, e.epi, e.act) && fp_bn_sink_claim(bn_sink, blocks, d->Nout)) {
+      a.bnb_part = bn_sink.part; a.bnb_z = bn_sink.z; a.bnb_mean = bn_sink.mean; a.bnb_invstd = bn_sink.invstd;
+    } else if (fp_bn_sink_fwd_ok(bn_sink, e.epi, e.act) && fp_bn_sink_claim(bn_sink, blocks, d->Nout)) {
+      a.bn_part = bn_sink.part;
     }
-    if (bn_sink.nblk_out) *bn_sink.nblk_out = emit ? (int32_t)blocks : 0;
   }
-  // a split forward grid with the statistics sink armed: its reduce launch writes the statistics (fp_splitk_reduce_stats_launch below)
-  const bool bnb_in_reduce = bn_sink.part && bn_sink.z && p.SK > 1 && flip && !fold && !(d->epi & FP_EPI_ACCUM) && d->act == 0;
-  const bool stats_in_reduce = bn_sink.part && !bn_sink.z && p.SK > 1 && !flip && (d->epi & ~(unsigned)FP_EPI_BF16X2) == 0 && d->act == 0;
   const int planes = hp ? 4 : 6;                    // bytes of packed weight per element
   a.wmajor = (int64_t)9 * (d->C0 + d->C1) * d->Nout * planes > ((int64_t)4 << 20);
 #if FP_TILE_T16
@@ -989,37 +972,18 @@ int run_tile3(const char* who, const fp_conv_desc* d, const float* src, const fl
     rc = p.th == 8 ? FP_L3X(8, 16, 3, false) : FP_L3X(6, 20, 3, false);
   }
 #undef FP_L3X
-  (void)who;
   if (rc || p.SK <= 1) return rc;
-  if (bnb_in_reduce) {
-    int rc2 = 0;
-    const int nb = fp_splitk_reduce_bnb_launch(a.part, p.SK, (int64_t)d->N * d->OH * d->OW, d->Nout, bias, addend, addend_mask, actsrc, y, d->act,
-                                               d->epi & ~FP_EPI_BF16X2, stream, hp ? hp->out : nullptr, bn_sink.z, bn_sink.mean, bn_sink.invstd,
-                                               bn_sink.part, bn_sink.cap_floats, &rc2);
-    if (nb > 0) {
-      if (bn_sink.nblk_out) *bn_sink.nblk_out = nb;
-      return rc2;
-    }
-  }
-  if (stats_in_reduce) {
-    int rc2 = 0;
-    const int nb = fp_splitk_reduce_stats_launch(a.part, p.SK, (int64_t)d->N * d->OH * d->OW, d->Nout, y, stream, hp ? hp->out : nullptr, bn_sink.part,
-                                                 bn_sink.cap_floats, &rc2);
-    if (nb > 0) {
-      if (bn_sink.nblk_out) *bn_sink.nblk_out = nb;
-      return rc2;
-    }
-  }
-  return fp_splitk_reduce_launch(a.part, p.SK, (int64_t)d->N * d->OH * d->OW, d->Nout, bias, addend, addend_mask, actsrc, y, d->act,
-                                 d->epi & ~FP_EPI_BF16X2, stream, hp ? hp->out : nullptr);      // split-K launches publish max |y| here
+  // a split grid stores raw partials: epilogue, max |y| and the BatchNorm partials come out of its reduce launch
+  return fp_splitk_finish(who, a.part, p.SK, (int64_t)d->N * d->OH * d->OW, d->Nout, e, d->gather, hp ? hp->out : nullptr,
+                          sink_here ? &bn_sink : nullptr, stream);
 }
 }  // namespace
 
 extern "C" int fp_conv3x3_bf3(const fp_conv_desc* d, const float* src, const float* src1, const void* wpacked_bf3, const float* bias,
                               const float* addend, const float* addend_mask, const float* actsrc, float* y, void* workspace,
                               int64_t workspace_bytes, const fp_aux* aux, fp_stream_t stream_) {
-  return run_tile3("fp_conv3x3_bf3", d, src, src1, wpacked_bf3, bias, addend, addend_mask, actsrc, y, workspace, workspace_bytes, nullptr,
-                   aux, (hipStream_t)stream_);
+  return run_tile3("fp_conv3x3_bf3", d, src, src1, wpacked_bf3, fp_conv_epilogue_of(d, bias, addend, addend_mask, actsrc, y), workspace,
+                   workspace_bytes, nullptr, aux, (hipStream_t)stream_);
 }
 
 // Same operation with fp16-pair operands (fp_common.h): weights from fp_pack_conv_weight_hp / FP_PACK_{FWD,DGRAD}_HP jobs with the
@@ -1032,6 +996,6 @@ extern "C" int fp_conv3x3_hp(const fp_conv_desc* d, const float* src, const floa
   FP_REQUIRE(amax_src && amax_w, "fp_conv3x3_hp: amax slots missing");
   FP_REQUIRE(!(d && d->gather == FP_GATHER_FWD_REFLECT_UP2 && d->C1) || amax_src1, "fp_conv3x3_hp: the skip tensor's amax slot is missing");
   const HpSlots hp = {amax_src, amax_src1, amax_w, amax_out};
-  return run_tile3("fp_conv3x3_hp", d, src, src1, wpacked_hp, bias, addend, addend_mask, actsrc, y, workspace, workspace_bytes, &hp,
-                   aux, (hipStream_t)stream_);
+  return run_tile3("fp_conv3x3_hp", d, src, src1, wpacked_hp, fp_conv_epilogue_of(d, bias, addend, addend_mask, actsrc, y), workspace,
+                   workspace_bytes, &hp, aux, (hipStream_t)stream_);
 }

@@ -19,14 +19,7 @@
 // buffers and a single barrier per K-step.
 #include <stdlib.h>
 
-#include "fp_common.h"
-
-int fp_stem_tile_dispatch(const fp_conv_desc* d, const float* img, const float* wpacked, const float* bias, float* y, hipStream_t stream,
-                          const FpBnSink& sink);
-int fp_splitk_reduce_stats_launch(const float* part, int SK, int64_t M, int Nout, float* y, hipStream_t stream, unsigned* amax_out,
-                                  float* stats, int64_t cap_floats, int* rc_out);
-int fp_conv3x3_tile_dispatch(const fp_conv_desc* d, const float* src0, const float* src1, const float* wpacked, const float* bias,
-                             const float* addend, const float* addend_mask, const float* actsrc, float* y, hipStream_t stream);
+#include "conv_host.h"
 
 namespace {
 
@@ -521,19 +514,35 @@ __global__ void __launch_bounds__(256) igemm_hp_kernel(const IgemmArgs a) {
   igemm_store_tile<1, TN>(a, acc, m0, n0, wave, 0, idx, h, split, ldexpf(1.f, kunscale));
 }
 
+// sum_s part[s][o] of one element (V = float) or of four consecutive channels (V = float4) in THE fixed order of every split-K reduce: four
+// strided running sums over s, s + 1, s + 2, s + 3 (four loads in flight), the tail into the first, then (p0 + p1) + (p2 + p3)
+__device__ __forceinline__ void splitk_add(float& p, float a) { p += a; }
+__device__ __forceinline__ void splitk_add(float4& p, const float4& a) { p.x += a.x; p.y += a.y; p.z += a.z; p.w += a.w; }
+__device__ __forceinline__ float splitk_fold(float p0, float p1, float p2, float p3) { return (p0 + p1) + (p2 + p3); }
+__device__ __forceinline__ float4 splitk_fold(const float4& p0, const float4& p1, const float4& p2, const float4& p3) {
+  return make_float4((p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y), (p0.z + p1.z) + (p2.z + p3.z), (p0.w + p1.w) + (p2.w + p3.w));
+}
+template <typename V>
+__device__ __forceinline__ V splitk_sum(const float* part, int SK, size_t total, size_t o) {
+  V p0 = {}, p1 = p0, p2 = p0, p3 = p0;
+  int s = 0;
+  for (; s + 4 <= SK; s += 4) {
+    const float* q = part + (size_t)s * total + o;
+    const V a0 = *reinterpret_cast<const V*>(q), a1 = *reinterpret_cast<const V*>(q + total), a2 = *reinterpret_cast<const V*>(q + 2 * total),
+            a3 = *reinterpret_cast<const V*>(q + 3 * total);
+    splitk_add(p0, a0); splitk_add(p1, a1); splitk_add(p2, a2); splitk_add(p3, a3);
+  }
+  for (; s < SK; ++s) splitk_add(p0, *reinterpret_cast<const V*>(part + (size_t)s * total + o));
+  return splitk_fold(p0, p1, p2, p3);
+}
+
 // y = epilogue(sum_s part[s]) -- fixed summation order
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(const IgemmArgs a) {
   const size_t total = (size_t)a.M * a.Nout;
   float ymax = 0.f;
   for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256) {
-    float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;              // four loads in flight, fixed combination order
-    int s = 0;
-    for (; s + 4 <= a.SK; s += 4) {
-      const float* q = a.part + (size_t)s * total + o;
-      p0 += q[0]; p1 += q[total]; p2 += q[2 * total]; p3 += q[3 * total];
-    }
-    for (; s < a.SK; ++s) p0 += a.part[(size_t)s * total + o];
-    const float v = igemm_epilogue(a, o, (int)(o % a.Nout), (p0 + p1) + (p2 + p3));
+    const float p = splitk_sum<float>(a.part, a.SK, total, o);
+    const float v = igemm_epilogue(a, o, (int)(o % a.Nout), p);
     a.y[o] = v;
     ymax = fmaxf(ymax, fabsf(v));
   }
@@ -554,23 +563,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_stats_kernel(const float* _
   float cnt = 0.f, ymax = 0.f;
   for (int m = blockIdx.x * R + rr; m < M; m += gridDim.x * R) {
     const size_t o = (size_t)m * Nout + cq * 4;
-    float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0, p3 = p0;      // four loads in flight, fixed combination order (as above)
-    int s = 0;
-    for (; s + 4 <= SK; s += 4) {
-      const float* q = part + (size_t)s * total + o;
-      const float4 a0 = *reinterpret_cast<const float4*>(q), a1 = *reinterpret_cast<const float4*>(q + total),
-                   a2 = *reinterpret_cast<const float4*>(q + 2 * total), a3 = *reinterpret_cast<const float4*>(q + 3 * total);
-      p0.x += a0.x; p0.y += a0.y; p0.z += a0.z; p0.w += a0.w;
-      p1.x += a1.x; p1.y += a1.y; p1.z += a1.z; p1.w += a1.w;
-      p2.x += a2.x; p2.y += a2.y; p2.z += a2.z; p2.w += a2.w;
-      p3.x += a3.x; p3.y += a3.y; p3.z += a3.z; p3.w += a3.w;
-    }
-    for (; s < SK; ++s) {
-      const float4 a0 = *reinterpret_cast<const float4*>(part + (size_t)s * total + o);
-      p0.x += a0.x; p0.y += a0.y; p0.z += a0.z; p0.w += a0.w;
-    }
-    const float4 v = make_float4((p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y), (p0.z + p1.z) + (p2.z + p3.z),
-                                 (p0.w + p1.w) + (p2.w + p3.w));
+    const float4 v = splitk_sum<float4>(part, SK, total, o);
     *reinterpret_cast<float4*>(y + o) = v;
     ymax = fp_amax4(ymax, v);
     cnt += 1.f;
@@ -613,27 +606,13 @@ __global__ void __launch_bounds__(256) splitk_reduce_bnb_kernel(const IgemmArgs 
   float ymax = 0.f;
   for (int m = blockIdx.x * R + rr; m < a.M; m += gridDim.x * R) {
     const size_t o = (size_t)m * a.Nout + cq * 4;
-    float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0, p3 = p0;
-    int s = 0;
-    for (; s + 4 <= a.SK; s += 4) {
-      const float* q = a.part + (size_t)s * total + o;
-      const float4 a0 = *reinterpret_cast<const float4*>(q), a1 = *reinterpret_cast<const float4*>(q + total),
-                   a2 = *reinterpret_cast<const float4*>(q + 2 * total), a3 = *reinterpret_cast<const float4*>(q + 3 * total);
-      p0.x += a0.x; p0.y += a0.y; p0.z += a0.z; p0.w += a0.w;
-      p1.x += a1.x; p1.y += a1.y; p1.z += a1.z; p1.w += a1.w;
-      p2.x += a2.x; p2.y += a2.y; p2.z += a2.z; p2.w += a2.w;
-      p3.x += a3.x; p3.y += a3.y; p3.z += a3.z; p3.w += a3.w;
-    }
-    for (; s < a.SK; ++s) {
-      const float4 a0 = *reinterpret_cast<const float4*>(a.part + (size_t)s * total + o);
-      p0.x += a0.x; p0.y += a0.y; p0.z += a0.z; p0.w += a0.w;
-    }
+    const float4 p = splitk_sum<float4>(a.part, a.SK, total, o);
     const float4 zv = *reinterpret_cast<const float4*>(z + o);
     float4 g;
-    g.x = igemm_epilogue(a, o + 0, cq * 4 + 0, (p0.x + p1.x) + (p2.x + p3.x));
-    g.y = igemm_epilogue(a, o + 1, cq * 4 + 1, (p0.y + p1.y) + (p2.y + p3.y));
-    g.z = igemm_epilogue(a, o + 2, cq * 4 + 2, (p0.z + p1.z) + (p2.z + p3.z));
-    g.w = igemm_epilogue(a, o + 3, cq * 4 + 3, (p0.w + p1.w) + (p2.w + p3.w));
+    g.x = igemm_epilogue(a, o + 0, cq * 4 + 0, p.x);
+    g.y = igemm_epilogue(a, o + 1, cq * 4 + 1, p.y);
+    g.z = igemm_epilogue(a, o + 2, cq * 4 + 2, p.z);
+    g.w = igemm_epilogue(a, o + 3, cq * 4 + 3, p.w);
     *reinterpret_cast<float4*>(a.y + o) = g;
     ymax = fp_amax4(ymax, g);
     s1[0] += g.x; s2[0] += g.x * ((zv.x - mu.x) * is.x);
@@ -675,8 +654,8 @@ int pick_splitk(int64_t tiles, int steps, int64_t MN, int64_t ws_floats) {
   return sk < 2 ? 1 : (int)sk;
 }
 
-template <int BM, int BN, int WM, int WN, bool STEM>
-int launch(IgemmArgs& a, hipStream_t stream, int64_t ws_floats) {
+// the grid of a flattened kernel with BM x BN tiles: row tiles, channel tiles, the split of the (tap, 16-channel) steps, workgroups
+void plan_grid(IgemmArgs& a, int BM, int BN, int64_t ws_floats) {
   int tilesM = (int)fp_ceil_div(a.M, BM);
   if (a.pm) {                       // four parity classes, each padded to whole BM-row tiles; never split
     a.McP = (int)fp_ceil_div(a.Mc, BM) * BM;
@@ -689,100 +668,84 @@ int launch(IgemmArgs& a, hipStream_t stream, int64_t ws_floats) {
   a.stepsPerSplit = (int)fp_ceil_div(steps, sk);
   a.SK = (int)fp_ceil_div(steps, a.stepsPerSplit);
   a.nwg = tilesM * a.tilesN * a.SK;
+}
+
+// behind the kernel's launch: the finish of a split grid, or the status of the launch
+int finish_grid(const char* who, const IgemmArgs& a, const FpBnSink* sink, hipStream_t stream) {
+  if (a.SK <= 1) return fp_check_launch(who);
+  return fp_splitk_finish(who, a.part, a.SK, a.M, a.Nout, FpConvEpilogue{a.bias, a.addend, a.addend_mask, a.actsrc, a.y, a.act, a.epi}, a.g.gather,
+                          a.amax_out, sink, stream);
+}
+
+template <int BM, int BN, int WM, int WN, bool STEM>
+int launch(IgemmArgs& a, hipStream_t stream, int64_t ws_floats) {
+  plan_grid(a, BM, BN, ws_floats);
   fp_launch((igemm_kernel<BM, BN, WM, WN, STEM>), dim3(a.nwg), dim3(256), 0, stream, a);
-  if (a.SK > 1) {
-    int64_t g = fp_ceil_div((int64_t)a.M * a.Nout, 256);
-    if (g > 4096) g = 4096;
-    fp_launch(splitk_reduce_kernel, dim3((int)g), dim3(256), 0, stream, a);
-  }
-  return fp_check_launch("fp_conv_igemm");
+  return finish_grid("fp_conv_igemm", a, nullptr, stream);       // fp32 operands: the reduce launch never emits BatchNorm partials
 }
 
 template <int TN, int NP = 2>
-int launch_hp(IgemmArgs& a, hipStream_t stream, int64_t ws_floats, const FpBnSink& sink) {
-  constexpr int BM = 128, BN = 32 * TN;
-  int tilesM = (int)fp_ceil_div(a.M, BM);
-  if (a.pm) {
-    a.McP = (int)fp_ceil_div(a.Mc, BM) * BM;
-    tilesM = 4 * (a.McP / BM);
-    ws_floats = 0;
-  }
-  a.tilesN = (int)fp_ceil_div(a.Nout, BN);
-  const int steps = a.T * a.KC16;
-  const int sk = pick_splitk((int64_t)tilesM * a.tilesN, steps, (int64_t)a.M * a.Nout, ws_floats);
-  a.stepsPerSplit = (int)fp_ceil_div(steps, sk);
-  a.SK = (int)fp_ceil_div(steps, a.stepsPerSplit);
-  a.nwg = tilesM * a.tilesN * a.SK;
+int launch_hp(const char* who, IgemmArgs& a, hipStream_t stream, int64_t ws_floats, const FpBnSink& sink) {
+  plan_grid(a, 128, 32 * TN, ws_floats);
   fp_launch((igemm_hp_kernel<TN, NP>), dim3(a.nwg), dim3(256), 0, stream, a);
-  if (a.SK > 1 && sink.part && !sink.z && a.epi == 0 && a.act == FP_ACT_NONE && !a.pm) {
-    // a strided / 1 x 1 forward convolution in front of a train-mode BatchNorm: the statistics out of the reduce launch (fp_aux.bn_part)
-    int rc2 = 0;
-    const int nb = fp_splitk_reduce_stats_launch(a.part, a.SK, a.M, a.Nout, a.y, stream, a.amax_out, sink.part, sink.cap_floats, &rc2);
-    if (nb > 0) {
-      if (sink.nblk_out) *sink.nblk_out = nb;
-      return rc2 ? rc2 : fp_check_launch("fp_conv_igemm_hp");
-    }
-  }
-  if (a.SK > 1) {
-    int64_t g = fp_ceil_div((int64_t)a.M * a.Nout, 256);
-    if (g > 4096) g = 4096;
-    fp_launch(splitk_reduce_kernel, dim3((int)g), dim3(256), 0, stream, a);
-  }
-  return fp_check_launch("fp_conv_igemm_hp");
+  // a strided / 1 x 1 convolution in front of a train-mode BatchNorm: the statistics out of the reduce launch.  This family's own
+  // conditions: no parity-major rows (an unsplit grid anyway), and the forward form only -- nothing arms the backward one here
+  return finish_grid(who, a, !a.pm && !sink.z ? &sink : nullptr, stream);
 }
 
 // worst-case split-K workspace: the launcher never uses more than 24 partial copies of the output
 constexpr int64_t MAX_SK = 24;
 
+// what fp_conv_igemm and the split-operand entry points fill alike: operands, geometry, K-steps and the parity-major rule.  Returns the
+// floats of split-K workspace the launch may use.
+int64_t igemm_fill(IgemmArgs& a, const fp_conv_desc* d, const float* src0, const float* src1, const FpConvEpilogue& e, void* workspace,
+                   int64_t workspace_bytes) {
+  const bool stem = d->gather == FP_GATHER_STEM;
+  const int64_t M64 = (int64_t)d->N * d->OH * d->OW;
+  a = IgemmArgs{};
+  a.src0 = src0; a.src1 = src1;
+  a.bias = e.bias; a.addend = e.addend; a.addend_mask = e.addend_mask; a.actsrc = e.actsrc; a.y = e.y; a.act = e.act; a.epi = e.epi;
+  a.g = FpGeom{d->N, d->OH, d->OW, d->IH, d->IW, d->C0, d->C1, d->KH, d->KW, d->stride, d->pad, d->gather};
+  a.Nout = d->Nout;
+  a.M = (int)M64;
+  a.T = stem ? 1 : d->KH * d->KW;
+  a.KC16 = stem ? 10 : (d->C0 + d->C1 + 15) / 16;
+  a.part = (float*)workspace;
+  a.SK = 1;
+  // 3x3 stride-2 data gradient on even dims: parity-major rows, only the taps a pixel class receives (see IgemmArgs)
+  static const bool no_pm = fp_env_flag("FP_NO_PM");
+  a.pm = !no_pm && d->gather == FP_GATHER_DGRAD_ZERO && d->stride == 2 && d->KH == 3 && d->KW == 3 && d->OH % 2 == 0 && d->OW % 2 == 0 &&
+         d->IH * 2 == d->OH && d->IW * 2 == d->OW;
+  a.Mc = a.pm ? d->N * (d->OH / 2) * (d->OW / 2) : 0;
+  a.McP = a.Mc;
+  const int64_t ws = workspace ? workspace_bytes / (int64_t)sizeof(float) : 0;
+  return ws > MAX_SK * M64 * d->Nout ? MAX_SK * M64 * d->Nout : ws;
+}
+
 }  // namespace
 
-// y = epilogue(sum over `SK` raw partial copies [SK][M][Nout]) in a fixed order -- shared with conv3x3_tile_bf3.hip
-int fp_splitk_reduce_launch(const float* part, int SK, int64_t M, int Nout, const float* bias, const float* addend, const float* addend_mask,
-                            const float* actsrc, float* y, int act, unsigned epi, hipStream_t stream, unsigned* amax_out) {
+int fp_splitk_finish(const char* who, const float* part, int SK, int64_t M, int Nout, const FpConvEpilogue& e, int gather, unsigned* amax_out,
+                     const FpBnSink* sink, hipStream_t stream) {
   IgemmArgs a = {};
-  a.amax_out = amax_out;
-  a.part = const_cast<float*>(part); a.SK = SK; a.M = (int)M; a.Nout = Nout;
-  a.bias = bias; a.addend = addend; a.addend_mask = addend_mask; a.actsrc = actsrc; a.y = y; a.act = act; a.epi = epi;
+  a.part = const_cast<float*>(part); a.SK = SK; a.M = (int)M; a.Nout = Nout; a.amax_out = amax_out;
+  a.bias = e.bias; a.addend = e.addend; a.addend_mask = e.addend_mask; a.actsrc = e.actsrc; a.y = e.y; a.act = e.act; a.epi = e.epi;
+  const bool bwd = sink && fp_bn_sink_bwd_ok(*sink, gather, e.epi, e.act), fwd = sink && fp_bn_sink_fwd_ok(*sink, e.epi, e.act);
+  // the emitting kernels: a thread owns four channels, the 256 / (Nout / 4) row groups of a block walk the rows
+  const int C4 = Nout / 4;
+  if ((bwd || fwd) && Nout % 4 == 0 && C4 >= 1 && C4 <= 256 && 256 % C4 == 0 && M < ((int64_t)1 << 31)) {
+    const int R = 256 / C4;
+    int64_t blocks = fp_ceil_div(M, (int64_t)R * 4);           // four rows per thread, as fp_bn_train_stats on these small tensors (one row per thread: four
+    if (blocks > 512) blocks = 512;                            // times the partial triples for the final stage, measured +0.05 ms per step)
+    if (fp_bn_sink_claim(*sink, blocks, Nout)) {
+      if (bwd) fp_launch(splitk_reduce_bnb_kernel, dim3((int)blocks), dim3(256), 0, stream, a, sink->z, sink->mean, sink->invstd, sink->part);
+      else fp_launch(splitk_reduce_stats_kernel, dim3((int)blocks), dim3(256), 0, stream, part, SK, (int)M, Nout, e.y, sink->part, amax_out);
+      return fp_check_launch(who);
+    }
+  }
   int64_t g = fp_ceil_div(M * Nout, 256);
   if (g > 4096) g = 4096;
   fp_launch(splitk_reduce_kernel, dim3((int)g), dim3(256), 0, stream, a);
-  return fp_check_launch("splitk_reduce");
-}
-
-// ... with BatchNorm statistics of y (splitk_reduce_stats_kernel); returns the number of partial blocks written to `stats` (capacity
-// `cap_floats`), 0 = shape not handled / capacity too small: the caller then uses fp_splitk_reduce_launch
-int fp_splitk_reduce_stats_launch(const float* part, int SK, int64_t M, int Nout, float* y, hipStream_t stream, unsigned* amax_out,
-                                  float* stats, int64_t cap_floats, int* rc_out) {
-  *rc_out = 0;
-  const int C4 = Nout / 4;
-  if (Nout % 4 || C4 < 1 || C4 > 256 || 256 % C4 || M >= ((int64_t)1 << 31)) return 0;
-  const int R = 256 / C4;
-  int64_t blocks = fp_ceil_div(M, (int64_t)R * 4);           // four rows per thread, as fp_bn_train_stats on these small tensors (one row per thread: four
-  if (blocks > 512) blocks = 512;                            // times the partial triples for the final stage, measured +0.05 ms per step)
-  if (blocks * Nout * 3 > cap_floats) return 0;
-  fp_launch(splitk_reduce_stats_kernel, dim3((int)blocks), dim3(256), 0, stream, part, SK, (int)M, Nout, y, stats, amax_out);
-  *rc_out = fp_check_launch("splitk_reduce(stats)");
-  return (int)blocks;
-}
-
-// ... with the BatchNorm-backward sums of y (splitk_reduce_bnb_kernel); returns the number of partial blocks written, 0 = not handled
-int fp_splitk_reduce_bnb_launch(const float* part, int SK, int64_t M, int Nout, const float* bias, const float* addend, const float* addend_mask,
-                                const float* actsrc, float* y, int act, unsigned epi, hipStream_t stream, unsigned* amax_out, const float* z,
-                                const float* mean, const float* invstd, float* bpart, int64_t cap_floats, int* rc_out) {
-  *rc_out = 0;
-  const int C4 = Nout / 4;
-  if (Nout % 4 || C4 < 1 || C4 > 256 || 256 % C4 || M >= ((int64_t)1 << 31)) return 0;
-  const int R = 256 / C4;
-  int64_t blocks = fp_ceil_div(M, (int64_t)R * 4);
-  if (blocks > 512) blocks = 512;
-  if (blocks * Nout * 2 > cap_floats) return 0;
-  IgemmArgs a = {};
-  a.amax_out = amax_out;
-  a.part = const_cast<float*>(part); a.SK = SK; a.M = (int)M; a.Nout = Nout;
-  a.bias = bias; a.addend = addend; a.addend_mask = addend_mask; a.actsrc = actsrc; a.y = y; a.act = act; a.epi = epi;
-  fp_launch(splitk_reduce_bnb_kernel, dim3((int)blocks), dim3(256), 0, stream, a, z, mean, invstd, bpart);
-  *rc_out = fp_check_launch("splitk_reduce(bn backward)");
-  return (int)blocks;
+  return fp_check_launch(who);
 }
 
 extern "C" int64_t fp_conv_igemm_workspace(const fp_conv_desc* d) {
@@ -813,12 +776,10 @@ extern "C" int fp_conv_igemm(const fp_conv_desc* d, const float* src0, const flo
     if (d->gather == FP_GATHER_FWD_REFLECT_UP2) FP_REQUIRE(d->IH % 2 == 0 && d->IW % 2 == 0, "fp_conv_igemm: UP2 needs even dims");
     FP_REQUIRE(d->C1 == 0 || (d->gather == FP_GATHER_FWD_REFLECT_UP2 && src1), "fp_conv_igemm: C1 only with UP2 concat");
   }
-  FP_REQUIRE(!(d->epi & FP_EPI_BIAS) || bias, "fp_conv_igemm: bias flag without pointer");
-  FP_REQUIRE(!(d->epi & FP_EPI_ADDEND) || addend, "fp_conv_igemm: addend flag without pointer");
-  FP_REQUIRE(!(d->epi & FP_EPI_ADDEND_MASK) || addend_mask, "fp_conv_igemm: addend_mask flag without pointer");
-  FP_REQUIRE(!(d->epi & (FP_EPI_ACTGRAD_ELU | FP_EPI_ACTGRAD_RELU)) || actsrc, "fp_conv_igemm: actgrad flag without pointer");
-  const int64_t M64 = (int64_t)d->N * d->OH * d->OW;
-  FP_REQUIRE(M64 * (int64_t)(d->Nout > d->C0 + d->C1 ? d->Nout : d->C0 + d->C1) < (int64_t)1 << 40 && M64 < (int64_t)1 << 31,
+  const FpConvEpilogue e = fp_conv_epilogue_of(d, bias, addend, addend_mask, actsrc, y);
+  if (const int rc = fp_conv_check_epilogue("fp_conv_igemm", d, e)) return rc;
+  const int64_t M = (int64_t)d->N * d->OH * d->OW;
+  FP_REQUIRE(M * (int64_t)(d->Nout > d->C0 + d->C1 ? d->Nout : d->C0 + d->C1) < (int64_t)1 << 40 && M < (int64_t)1 << 31,
              "fp_conv_igemm: problem too large");
 
   if (stem) {    // patch-in-LDS kernel (stem_tile.hip); shapes / epilogues it does not take stay on the flattened path
@@ -833,27 +794,10 @@ extern "C" int fp_conv_igemm(const fp_conv_desc* d, const float* src0, const flo
     }
   }
   IgemmArgs a;
-  a.amax_out = nullptr;
-  a.src0 = src0; a.src1 = src1; a.w = wpacked; a.bias = bias; a.addend = addend; a.addend_mask = addend_mask;
-  a.actsrc = actsrc; a.y = y;
-  a.g = FpGeom{d->N, d->OH, d->OW, d->IH, d->IW, d->C0, d->C1, d->KH, d->KW, d->stride, d->pad, d->gather};
-  a.Nout = d->Nout; a.act = d->act; a.epi = d->epi;
-  a.M = (int)M64;
-  a.T = stem ? 1 : d->KH * d->KW;
-  a.KC16 = stem ? 10 : (d->C0 + d->C1 + 15) / 16;
-  a.part = (float*)workspace;
-  a.SK = 1;
-  // 3x3 stride-2 data gradient on even dims: parity-major rows, only the taps a pixel class receives (see IgemmArgs)
-  static const bool no_pm = getenv("FP_NO_PM") && atoi(getenv("FP_NO_PM"));
-  a.pm = !no_pm && d->gather == FP_GATHER_DGRAD_ZERO && d->stride == 2 && d->KH == 3 && d->KW == 3 && d->OH % 2 == 0 && d->OW % 2 == 0 &&
-         d->IH * 2 == d->OH && d->IW * 2 == d->OW;
-  a.Mc = a.pm ? d->N * (d->OH / 2) * (d->OW / 2) : 0;
-  a.McP = a.Mc;
-  int64_t ws = workspace ? workspace_bytes / (int64_t)sizeof(float) : 0;
-  if (ws > MAX_SK * M64 * d->Nout) ws = MAX_SK * M64 * d->Nout;
+  const int64_t ws = igemm_fill(a, d, src0, src1, e, workspace, workspace_bytes);
+  a.w = wpacked;
 
   if (stem) return launch<128, 64, 2, 2, true>(a, stream, 0);
-  const int64_t M = a.M;
   if (d->Nout <= 32) {
     if (fp_ceil_div(M, 256) >= 512) return launch<256, 32, 4, 1, false>(a, stream, ws);
     return launch<128, 32, 4, 1, false>(a, stream, ws);
@@ -875,53 +819,35 @@ extern "C" int fp_conv_igemm_hp_supported(const fp_conv_desc* d) {
   return 1;
 }
 
-static int igemm_split_operands(const char* who, const fp_conv_desc* d, const float* src, const void* wpacked, const float* bias, const float* addend,
-                                const float* addend_mask, const float* actsrc, float* y, void* workspace, int64_t workspace_bytes,
-                                const uint32_t* amax_src, const uint32_t* amax_w, bool exact, const fp_aux* aux, fp_stream_t stream_) {
+static int igemm_split_operands(const char* who, const fp_conv_desc* d, const float* src, const void* wpacked, const FpConvEpilogue& e,
+                                void* workspace, int64_t workspace_bytes, const uint32_t* amax_src, const uint32_t* amax_w, bool exact,
+                                const fp_aux* aux, fp_stream_t stream_) {
   const FpBnSink bn_sink = fp_bn_sink_of(aux);    // only a split grid's reduce launch can emit (launch_hp)
   hipStream_t stream = (hipStream_t)stream_;
-  (void)who;
-  FP_REQUIRE(d && src && wpacked && y && (exact || (amax_src && amax_w)), "fp_conv_igemm_hp / _bf3: null pointer");
-  FP_REQUIRE(fp_conv_igemm_hp_supported(d), "fp_conv_igemm_hp / _bf3: shape / gather not supported (see fp_conv_igemm_hp_supported)");
-  FP_REQUIRE(!(d->epi & FP_EPI_BIAS) || bias, "fp_conv_igemm_hp / _bf3: bias flag without pointer");
-  FP_REQUIRE(!(d->epi & FP_EPI_ADDEND) || addend, "fp_conv_igemm_hp / _bf3: addend flag without pointer");
-  FP_REQUIRE(!(d->epi & FP_EPI_ADDEND_MASK) || addend_mask, "fp_conv_igemm_hp / _bf3: addend_mask flag without pointer");
-  FP_REQUIRE(!(d->epi & (FP_EPI_ACTGRAD_ELU | FP_EPI_ACTGRAD_RELU)) || actsrc, "fp_conv_igemm_hp / _bf3: actgrad flag without pointer");
-  const int64_t M64 = (int64_t)d->N * d->OH * d->OW;
-  FP_REQUIRE(M64 > 0 && M64 < (int64_t)1 << 31 && M64 * d->Nout < (int64_t)1 << 40, "fp_conv_igemm_hp / _bf3: problem too large / empty");
-  IgemmArgs a = {};
-  a.src0 = src; a.w_hp = (const unsigned short*)wpacked; a.bias = bias; a.addend = addend; a.addend_mask = addend_mask; a.actsrc = actsrc; a.y = y;
-  a.amax_a = amax_src; a.amax_w = amax_w; a.amax_out = nullptr;
-  a.g = FpGeom{d->N, d->OH, d->OW, d->IH, d->IW, d->C0, 0, d->KH, d->KW, d->stride, d->pad, d->gather};
-  a.Nout = d->Nout; a.act = d->act; a.epi = d->epi;
-  a.M = (int)M64;
-  a.T = d->KH * d->KW;
-  a.KC16 = (d->C0 + 15) / 16;
-  a.part = (float*)workspace;
-  a.SK = 1;
-  static const bool no_pm = getenv("FP_NO_PM") && atoi(getenv("FP_NO_PM"));
-  a.pm = !no_pm && d->gather == FP_GATHER_DGRAD_ZERO && d->stride == 2 && d->KH == 3 && d->KW == 3 && d->OH % 2 == 0 && d->OW % 2 == 0 &&
-         d->IH * 2 == d->OH && d->IW * 2 == d->OW;
-  a.Mc = a.pm ? d->N * (d->OH / 2) * (d->OW / 2) : 0;
-  a.McP = a.Mc;
-  int64_t ws = workspace ? workspace_bytes / (int64_t)sizeof(float) : 0;
-  if (ws > MAX_SK * M64 * d->Nout) ws = MAX_SK * M64 * d->Nout;
+  FP_REQUIRE(d && src && wpacked && e.y && (exact || (amax_src && amax_w)), "%s: null pointer", who);
+  FP_REQUIRE(fp_conv_igemm_hp_supported(d), "%s: shape / gather not supported (see fp_conv_igemm_hp_supported)", who);
+  if (const int rc = fp_conv_check_epilogue(who, d, e)) return rc;
+  const int64_t M = (int64_t)d->N * d->OH * d->OW;
+  FP_REQUIRE(M > 0 && M < (int64_t)1 << 31 && M * d->Nout < (int64_t)1 << 40, "%s: problem too large / empty", who);
+  IgemmArgs a;
+  const int64_t ws = igemm_fill(a, d, src, nullptr, e, workspace, workspace_bytes);
+  a.w_hp = (const unsigned short*)wpacked; a.amax_a = amax_src; a.amax_w = amax_w;
   // wave tile 32 rows x 32 TN columns: wider tiles re-read the A rows less often, narrower ones fill the chip on small grids
   if (exact) {                                    // three planes of weights in flight per K-step: two column blocks per wave at most
-    if (d->Nout <= 32) return launch_hp<1, 3>(a, stream, ws, bn_sink);
-    return launch_hp<2, 3>(a, stream, ws, bn_sink);
+    if (d->Nout <= 32) return launch_hp<1, 3>(who, a, stream, ws, bn_sink);
+    return launch_hp<2, 3>(who, a, stream, ws, bn_sink);
   }
-  if (d->Nout <= 32) return launch_hp<1>(a, stream, ws, bn_sink);
-  const int64_t t128 = fp_ceil_div(M64, 128);
-  if (d->Nout % 128 == 0 && t128 * (d->Nout / 128) >= 512) return launch_hp<4>(a, stream, ws, bn_sink);
-  return launch_hp<2>(a, stream, ws, bn_sink);
+  if (d->Nout <= 32) return launch_hp<1>(who, a, stream, ws, bn_sink);
+  const int64_t t128 = fp_ceil_div(M, 128);
+  if (d->Nout % 128 == 0 && t128 * (d->Nout / 128) >= 512) return launch_hp<4>(who, a, stream, ws, bn_sink);
+  return launch_hp<2>(who, a, stream, ws, bn_sink);
 }
 
 extern "C" int fp_conv_igemm_hp(const fp_conv_desc* d, const float* src, const void* wpacked_hp, const float* bias, const float* addend,
                                 const float* addend_mask, const float* actsrc, float* y, void* workspace, int64_t workspace_bytes,
                                 const uint32_t* amax_src, const uint32_t* amax_w, const fp_aux* aux, fp_stream_t stream_) {
-  return igemm_split_operands("fp_conv_igemm_hp", d, src, wpacked_hp, bias, addend, addend_mask, actsrc, y, workspace, workspace_bytes, amax_src,
-                              amax_w, false, aux, stream_);
+  return igemm_split_operands("fp_conv_igemm_hp", d, src, wpacked_hp, fp_conv_epilogue_of(d, bias, addend, addend_mask, actsrc, y), workspace,
+                              workspace_bytes, amax_src, amax_w, false, aux, stream_);
 }
 
 // The same operation with EXACTLY split bf16x3 operands (round 5; the default operand format's path for the encoder's stride-2 3x3 and 1x1
@@ -930,6 +856,6 @@ extern "C" int fp_conv_igemm_hp(const fp_conv_desc* d, const float* src, const v
 extern "C" int fp_conv_igemm_bf3(const fp_conv_desc* d, const float* src, const void* wpacked_bf3, const float* bias, const float* addend,
                                  const float* addend_mask, const float* actsrc, float* y, void* workspace, int64_t workspace_bytes,
                                  const fp_aux* aux, fp_stream_t stream_) {
-  return igemm_split_operands("fp_conv_igemm_bf3", d, src, wpacked_bf3, bias, addend, addend_mask, actsrc, y, workspace, workspace_bytes, nullptr,
-                              nullptr, true, aux, stream_);
+  return igemm_split_operands("fp_conv_igemm_bf3", d, src, wpacked_bf3, fp_conv_epilogue_of(d, bias, addend, addend_mask, actsrc, y), workspace,
+                              workspace_bytes, nullptr, nullptr, true, aux, stream_);
 }

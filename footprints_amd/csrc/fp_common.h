@@ -302,14 +302,28 @@ struct FpBnSink {
   const float* mean;
   const float* invstd;
 };
-// round 6: side outputs arrive as an explicit `const fp_aux*` argument (include/footprints_hip.h); these two read it (null = none)
+// round 6: side outputs arrive as an explicit `const fp_aux*` argument (include/footprints_hip.h); these two read it (null = none).
+// An entry point calls this FIRST, before it validates anything: *bn_nblk_out is zeroed here, so a call that fails on its arguments, or
+// a launch that cannot emit, reports "nothing emitted" and the caller runs the BatchNorm's own reduction pass.
 static inline FpBnSink fp_bn_sink_of(const fp_aux* aux) {
-  if (!aux || !aux->bn_part) {
-    if (aux && aux->bn_nblk_out) *aux->bn_nblk_out = 0;
-    return FpBnSink{nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-  }
-  if (aux->bn_nblk_out) *aux->bn_nblk_out = 0;
+  if (aux && aux->bn_nblk_out) *aux->bn_nblk_out = 0;
+  if (!aux || !aux->bn_part) return FpBnSink{nullptr, 0, nullptr, nullptr, nullptr, nullptr};
   return FpBnSink{aux->bn_part, aux->bn_capacity_floats, aux->bn_nblk_out, aux->bnb_z, aux->bnb_mean, aux->bnb_invstd};
+}
+// ---- when a launch may emit into the sink: the rule of every convolution (a condition only one kernel has stays at its site).
+// Forward form, (count, mean, M2) of the output: the stored value is the bare accumulator -- no epilogue flag, no activation.
+static inline bool fp_bn_sink_fwd_ok(const FpBnSink& s, unsigned epi, int act) { return s.part && !s.z && epi == 0 && act == FP_ACT_NONE; }
+// Backward form, (sum g, sum g * xhat) of the output g: a data gradient without the reflection fold that overwrites its output (no
+// FP_EPI_ACCUM) and has no activation.
+static inline bool fp_bn_sink_bwd_ok(const FpBnSink& s, int gather, unsigned epi, int act) {
+  return s.part && s.z && gather == FP_GATHER_DGRAD_ZERO && !(epi & FP_EPI_ACCUM) && act == FP_ACT_NONE;
+}
+// the claim of a launch that emits `blocks` blocks of Nout x {3 forward, 2 backward} floats: false when the capacity does not suffice,
+// else *nblk_out = blocks
+static inline bool fp_bn_sink_claim(const FpBnSink& s, int64_t blocks, int Nout) {
+  if (blocks * Nout * (s.z ? 2 : 3) > s.cap_floats) return false;
+  if (s.nblk_out) *s.nblk_out = (int32_t)blocks;
+  return true;
 }
 static inline unsigned* fp_amax_out_of(const fp_aux* aux) { return aux ? aux->amax_out : nullptr; }
 __device__ __forceinline__ float fp_wave_max(float v);

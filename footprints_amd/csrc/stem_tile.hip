@@ -8,7 +8,7 @@
 // zero beyond 147).  Same arithmetic per element as the flattened kernel (fp32 products, fp32 MFMA accumulation, k ascending).
 #include <stdlib.h>
 
-#include "fp_common.h"
+#include "conv_host.h"
 
 namespace {
 
@@ -576,12 +576,10 @@ int fp_stem_tile_dispatch(const fp_conv_desc* d, const float* img, const float* 
   a.N = d->N; a.IH = d->IH; a.IW = d->IW; a.OH = d->OH; a.OW = d->OW; a.act = d->act;
   a.tilesX = (int)fp_ceil_div(d->OW, TW); a.tilesY = (int)fp_ceil_div(d->OH, TH);
   a.bn_part = nullptr;
-  // statistics sink (fp_aux.bn_part, forward form): the stored value is the accumulator itself only without bias / activation
+  // statistics sink (fp_aux.bn_part, forward form; the rule: fp_common.h).  The stem's epilogue is bias-only (tested above), so "no
+  // epilogue flag" says "no bias" here.
   const int64_t ntiles = (int64_t)d->N * a.tilesX * a.tilesY;
-  if (sink.part && !sink.z && !a.bias && d->act == FP_ACT_NONE && ntiles * 64 * 3 <= sink.cap_floats) {
-    a.bn_part = sink.part;
-    if (sink.nblk_out) *sink.nblk_out = (int32_t)ntiles;
-  }
+  if (fp_bn_sink_fwd_ok(sink, d->epi, d->act) && fp_bn_sink_claim(sink, ntiles, 64)) a.bn_part = sink.part;
   fp_launch(stem_tile_kernel, dim3(d->N * a.tilesX * a.tilesY), dim3(256), 0, stream, a);
   return fp_check_launch("fp_conv_igemm(stem)");
 }
@@ -603,11 +601,8 @@ extern "C" int fp_conv_stem_hp(const fp_conv_desc* d, const float* img, const vo
   a.tilesX = (int)fp_ceil_div(d->OW, TW); a.tilesY = (int)fp_ceil_div(d->OH, TH);
   a.bn_part = nullptr;
   const int64_t ntiles = (int64_t)d->N * a.tilesX * a.tilesY;
-  if (sink.nblk_out) *sink.nblk_out = 0;
-  if (sink.part && !sink.z && !a.bias && d->act == FP_ACT_NONE && ntiles * 64 * 3 <= sink.cap_floats) {
-    a.bn_part = sink.part;
-    if (sink.nblk_out) *sink.nblk_out = (int32_t)ntiles;
-  }
+  // as in fp_stem_tile_dispatch: a bias-only epilogue (fp_conv_stem_hp_supported), so the forward rule says "no bias, no activation"
+  if (fp_bn_sink_fwd_ok(sink, d->epi, d->act) && fp_bn_sink_claim(sink, ntiles, 64)) a.bn_part = sink.part;
   static const int wgs = getenv("FP_STEM_HP_WGS") ? atoi(getenv("FP_STEM_HP_WGS")) : 512;          // persistent: two workgroups per CU (194 VGPRs)
   const int64_t budget = wgs > 0 ? wgs : 512;        // (an unusable value of the experiment knob falls back to the default)
   fp_launch(stem_tile_hp_kernel, dim3((unsigned)(ntiles < budget ? ntiles : budget)), dim3(256), 0, (hipStream_t)stream, a);

@@ -788,7 +788,7 @@ class Engine:
     @staticmethod
     def _partials_cap(N, h, w, C, per):
         """floats of a tile launch's BatchNorm side output: `per` values per pixel tile (8 x 16 or 6 x 20 pixels, bounded by 6 x 16-pixel ones)
-        and channel; split-K grids: per block of the reduce launch (fp_splitk_reduce_stats_launch / fp_splitk_reduce_bnb_launch)"""
+        and channel; split-K grids: per block of the reduce launch (the block rule of fp_splitk_finish)"""
         cap = N * ((h + 5) // 6) * ((w + 15) // 16) * C * per
         if C % 4 == 0 and 256 % (C // 4) == 0:
             rows = 256 // (C // 4) * 4

@@ -141,25 +141,32 @@ def make_desc(N, OH, OW, IH, IW, C0, C1, Nout, K, stride, pad, gather, act=0, ep
     return ConvDesc(N, OH, OW, IH, IW, C0, C1, Nout, K, K, stride, pad, gather, act, epi)
 
 
-def conv_igemm(desc, src0, src1, wpacked, y, bias=None, addend=None, addend_mask=None, actsrc=None, bn_out=None):
-    lib = _lib.load()
-    epi = desc.epi
-    if bias is not None:
-        epi |= _lib.EPI_BIAS
-    if addend is not None:
-        epi |= _lib.EPI_ADDEND
-    if addend_mask is not None:
-        epi |= _lib.EPI_ADDEND_MASK
+def _conv(fn, ws_query, desc, operands, y, bias, addend, addend_mask, actsrc, bn_out, slots=(), epi=0):
+    """One forward / data-gradient convolution launch through entry point `fn`: a private copy of the descriptor with the epilogue flags
+    of the optional arguments (and `epi`), the split-K workspace `ws_query` asks for (None: none is passed), the call, the check.
+    `operands` / `slots`: the entry point's pointers in front of `bias` / behind the workspace."""
     d = ConvDesc.from_buffer_copy(desc)
-    d.epi = epi
-    need = 0 if _NO_SPLITK else _cached_query("fp_conv_igemm_workspace", d)
+    d.epi = desc.epi | epi | (_lib.EPI_BIAS if bias is not None else 0) | (_lib.EPI_ADDEND if addend is not None else 0) | \
+        (_lib.EPI_ADDEND_MASK if addend_mask is not None else 0)
+    need = _cached_query(ws_query, d) if ws_query else 0
     ws_ptr, ws_n = 0, 0
     if need > 0:
         ws = workspace(need, y.device, "igemm")
         ws_ptr, ws_n = ws.data_ptr(), ws.numel()
-    _lib.check(lib.fp_conv_igemm(C.byref(d), _f32(src0, "src0"), _f32(src1, "src1"), _f32(wpacked, "wpacked"), _f32(bias),
-                                 _f32(addend), _f32(addend_mask), _f32(actsrc), _f32(y, "y"), ws_ptr, ws_n, _aux(bn_out=bn_out), stream()), "fp_conv_igemm")
+    _lib.check(getattr(_lib.load(), fn)(C.byref(d), *operands, _f32(bias), _f32(addend), _f32(addend_mask), _f32(actsrc), _f32(y, "y"), ws_ptr, ws_n,
+                                        *slots, _aux(bn_out=bn_out), stream()), fn)
     return y
+
+
+# The one difference between the two families: the flattened kernels split only when they are handed a workspace, so FP_NO_SPLITK is
+# honoured by passing none; the tile plan decides the split from the shape alone and requires its workspace, so it is always passed.
+_IGEMM_WS = None if _NO_SPLITK else "fp_conv_igemm_workspace"
+_TILE_WS = "fp_conv3x3_bf3_workspace"
+
+
+def conv_igemm(desc, src0, src1, wpacked, y, bias=None, addend=None, addend_mask=None, actsrc=None, bn_out=None):
+    return _conv("fp_conv_igemm", _IGEMM_WS, desc, (_f32(src0, "src0"), _f32(src1, "src1"), _f32(wpacked, "wpacked")), y, bias, addend, addend_mask,
+                 actsrc, bn_out)
 
 
 def conv_stem_hp_supported(desc):
@@ -191,25 +198,8 @@ def conv_igemm_hp_supported(desc):
 
 def conv_igemm_hp(desc, src, wpacked_hp, y, amax_src, amax_w, bias=None, addend=None, addend_mask=None, actsrc=None, bn_out=None):
     """flattened implicit GEMM with fp16-pair operands (3x3 stride 2, 1x1, their data gradients): weights from FP_PACK_{FWD,DGRAD}_HP"""
-    lib = _lib.load()
-    epi = desc.epi
-    if bias is not None:
-        epi |= _lib.EPI_BIAS
-    if addend is not None:
-        epi |= _lib.EPI_ADDEND
-    if addend_mask is not None:
-        epi |= _lib.EPI_ADDEND_MASK
-    d = ConvDesc.from_buffer_copy(desc)
-    d.epi = epi
-    need = 0 if _NO_SPLITK else _cached_query("fp_conv_igemm_workspace", d)
-    ws_ptr, ws_n = 0, 0
-    if need > 0:
-        ws = workspace(need, y.device, "igemm")
-        ws_ptr, ws_n = ws.data_ptr(), ws.numel()
-    _lib.check(lib.fp_conv_igemm_hp(C.byref(d), _f32(src, "src"), _chk(wpacked_hp, "wpacked_hp"), _f32(bias), _f32(addend), _f32(addend_mask),
-                                    _f32(actsrc), _f32(y, "y"), ws_ptr, ws_n, _u32(amax_src), _u32(amax_w), _aux(bn_out=bn_out), stream()),
-               "fp_conv_igemm_hp")
-    return y
+    return _conv("fp_conv_igemm_hp", _IGEMM_WS, desc, (_f32(src, "src"), _chk(wpacked_hp, "wpacked_hp")), y, bias, addend, addend_mask, actsrc, bn_out,
+                 slots=(_u32(amax_src), _u32(amax_w)))
 
 
 def conv3x3_bf3_supported(desc):
@@ -222,21 +212,9 @@ _bf16x2 = False      # opt-in inference mode of the bf16 tile kernel (Engine.for
 def conv3x3_bf3(desc, src, wpacked_bf3, y, bias=None, addend=None, addend_mask=None, actsrc=None, src1=None, bn_out=None):
     """3x3 stride-1 conv / data-gradient with exactly split bf16x3 operands (same semantics as conv_igemm; src1 = the skip tensor
     of the GATHER_FWD_REFLECT_UP2 concat)"""
-    epi = desc.epi | (_lib.EPI_BIAS if bias is not None else 0) | (_lib.EPI_ADDEND if addend is not None else 0) | \
-        (_lib.EPI_ADDEND_MASK if addend_mask is not None else 0)
-    if _bf16x2 and desc.gather in (_lib.GATHER_FWD_ZERO, _lib.GATHER_FWD_REFLECT, _lib.GATHER_FWD_REFLECT_UP2):
-        epi |= _lib.EPI_BF16X2
-    lib = _lib.load()
-    d = ConvDesc.from_buffer_copy(desc)
-    d.epi = epi
-    need = _cached_query("fp_conv3x3_bf3_workspace", d)
-    ws_ptr, ws_n = 0, 0
-    if need > 0:
-        ws = workspace(need, y.device, "igemm")
-        ws_ptr, ws_n = ws.data_ptr(), ws.numel()
-    _lib.check(lib.fp_conv3x3_bf3(C.byref(d), _f32(src, "src"), _f32(src1, "src1"), _f32(wpacked_bf3, "wpacked"), _f32(bias), _f32(addend),
-                                  _f32(addend_mask), _f32(actsrc), _f32(y, "y"), ws_ptr, ws_n, _aux(bn_out=bn_out), stream()), "fp_conv3x3_bf3")
-    return y
+    fwd = desc.gather in (_lib.GATHER_FWD_ZERO, _lib.GATHER_FWD_REFLECT, _lib.GATHER_FWD_REFLECT_UP2)
+    return _conv("fp_conv3x3_bf3", _TILE_WS, desc, (_f32(src, "src"), _f32(src1, "src1"), _f32(wpacked_bf3, "wpacked")), y, bias, addend, addend_mask,
+                 actsrc, bn_out, epi=_lib.EPI_BF16X2 if _bf16x2 and fwd else 0)
 
 
 # ---- fp16-pair operands (include/footprints_hip.h "hp"): amax slots are int32 tensors of amax_elems() elements ---------------------
@@ -329,44 +307,14 @@ def pack_conv_weight_hp(w, wp, slot, for_dgrad=False, amax_ready=False):
 def conv3x3_hp(desc, src, wpacked_hp, y, amax_src, amax_w, amax_out=None, bias=None, addend=None, addend_mask=None, actsrc=None, src1=None,
                amax_src1=None, bn_out=None):
     """conv3x3_bf3 with fp16-pair operands; amax_* are slots (see amax_f32); amax_out (zeroed by the caller) receives max |y|"""
-    epi = desc.epi | (_lib.EPI_BIAS if bias is not None else 0) | (_lib.EPI_ADDEND if addend is not None else 0) | \
-        (_lib.EPI_ADDEND_MASK if addend_mask is not None else 0)
-    lib = _lib.load()
-    d = ConvDesc.from_buffer_copy(desc)
-    d.epi = epi
-    need = _cached_query("fp_conv3x3_bf3_workspace", d)
-    ws_ptr, ws_n = 0, 0
-    if need > 0:
-        ws = workspace(need, y.device, "igemm")
-        ws_ptr, ws_n = ws.data_ptr(), ws.numel()
-    _lib.check(lib.fp_conv3x3_hp(C.byref(d), _f32(src, "src"), _f32(src1, "src1"), _f32(wpacked_hp, "wpacked"), _f32(bias), _f32(addend),
-                                 _f32(addend_mask), _f32(actsrc), _f32(y, "y"), ws_ptr, ws_n, _u32(amax_src, "amax_src"),
-                                 _u32(amax_src1, "amax_src1"), _u32(amax_w, "amax_w"), _u32(amax_out, "amax_out"), _aux(bn_out=bn_out), stream()),
-               "fp_conv3x3_hp")
-    return y
+    return _conv("fp_conv3x3_hp", _TILE_WS, desc, (_f32(src, "src"), _f32(src1, "src1"), _f32(wpacked_hp, "wpacked")), y, bias, addend, addend_mask,
+                 actsrc, bn_out, slots=(_u32(amax_src, "amax_src"), _u32(amax_src1, "amax_src1"), _u32(amax_w, "amax_w"), _u32(amax_out, "amax_out")))
 
 
 def conv_igemm_bf3(desc, src, wpacked_bf3, y, bias=None, addend=None, addend_mask=None, actsrc=None, bn_out=None):
     """flattened implicit GEMM with EXACTLY split bf16x3 operands (3x3 stride 2, 1x1, their data gradients; the default operand format):
     weights from FP_PACK_{FWD,DGRAD}_BF3; shapes as conv_igemm_hp_supported"""
-    lib = _lib.load()
-    epi = desc.epi
-    if bias is not None:
-        epi |= _lib.EPI_BIAS
-    if addend is not None:
-        epi |= _lib.EPI_ADDEND
-    if addend_mask is not None:
-        epi |= _lib.EPI_ADDEND_MASK
-    d = ConvDesc.from_buffer_copy(desc)
-    d.epi = epi
-    need = 0 if _NO_SPLITK else _cached_query("fp_conv_igemm_workspace", d)
-    ws_ptr, ws_n = 0, 0
-    if need > 0:
-        ws = workspace(need, y.device, "igemm")
-        ws_ptr, ws_n = ws.data_ptr(), ws.numel()
-    _lib.check(lib.fp_conv_igemm_bf3(C.byref(d), _f32(src, "src"), _chk(wpacked_bf3, "wpacked_bf3"), _f32(bias), _f32(addend), _f32(addend_mask),
-                                     _f32(actsrc), _f32(y, "y"), ws_ptr, ws_n, _aux(bn_out=bn_out), stream()), "fp_conv_igemm_bf3")
-    return y
+    return _conv("fp_conv_igemm_bf3", _IGEMM_WS, desc, (_f32(src, "src"), _chk(wpacked_bf3, "wpacked_bf3")), y, bias, addend, addend_mask, actsrc, bn_out)
 
 
 def packed_weight_elems_bf3(Cout, Cin, K, for_dgrad=False):

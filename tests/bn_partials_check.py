@@ -6,7 +6,7 @@ import numpy as np
 
 
 def reduce_geometry(M, Nout):
-    """(R, nblk) of the reduce launch for an [M][Nout] output, or None where the launch does not emit (fp_splitk_reduce_stats_launch)"""
+    """(R, nblk) of the reduce launch for an [M][Nout] output, or None where the launch does not emit (the block rule of fp_splitk_finish)"""
     if Nout % 4 or Nout // 4 > 256 or 256 % (Nout // 4):
         return None
     R = 256 // (Nout // 4)

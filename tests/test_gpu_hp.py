@@ -1,10 +1,13 @@
 """GPU: the fp16-pair ("hp") operand format (include/footprints_hip.h): amax slots and their publication by producers, HP weight
 packing, and every hp kernel against a float64 reference with the bounds of the exact bf16x3 kernels it replaces (the operands
 carry 22 significant bits after a per-tensor power-of-two scaling; products and accumulation are as exact as the bf16 split's)."""
+import os
+
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.bn_partials_check import reduce_geometry
 from tests.test_gpu_kernels import _ops, _up2_ref, check, nchw, nhwc, relerr, rnd
 
 pytestmark = pytest.mark.gpu
@@ -407,6 +410,125 @@ def test_conv3x3_hp_data_gradient_emits_batchnorm_backward_sums(N, H, W, C, emit
     dg2, db2 = dg.clone(), db.clone()                               # accumulate = True adds on top
     ops.bn_bwd_partials(gout.view(-1, C), zs.view(-1, C), mean_d, invstd_d, gamma.cuda(), dz.view(-1, C), dg2, db2, part, tiles, accumulate=True)
     assert relerr(dg2, 2 * s2) < tol_s and relerr(db2, 2 * s1) < tol_s
+
+
+# The smallest shapes the tile plan takes (it wants tiles x SK >= 128).  name: (N, H, W, C0, Nout, pixel tile, SK); C0 channels of the
+# launch's source, Nout of its output, whichever the gather
+NO_EMIT_SHAPES = {
+    "unsplit": (6, 48, 80, 64, 64, (8, 16), 1),          # 180 tiles
+    "SK 2": (3, 48, 80, 64, 64, (8, 16), 2),             # 90 tiles
+    "SK 3": (3, 48, 80, 96, 64, (8, 16), 3),             # the reduce runs its tail loop only
+    "SK 5": (3, 48, 80, 160, 64, (8, 16), 5),            # one block of four plus a tail
+    "SK 4, 6 x 20": (8, 12, 40, 128, 128, (6, 20), 4),   # 64 tiles
+}
+# name: (shape, sink form armed, gather, options).  Each launch lacks exactly one thing of what an emitting launch needs -- "short": the
+# capacity is one float under what the launch would write, per pixel tile on an unsplit grid and per block of the reduce on a split one
+NO_EMIT_TILE = {
+    "stats, bias, unsplit": ("unsplit", "stats", "fwd", {"bias"}),
+    "stats, bias, split": ("SK 2", "stats", "fwd", {"bias"}),
+    "stats, elu, unsplit": ("unsplit", "stats", "fwd", {"elu"}),
+    "stats, elu, split": ("SK 3", "stats", "fwd", {"elu"}),
+    "stats, addend, unsplit": ("unsplit", "stats", "fwd", {"addend"}),
+    "stats, addend, split": ("SK 5", "stats", "fwd", {"addend"}),
+    "stats, accum, unsplit": ("unsplit", "stats", "fwd", {"accum"}),
+    "stats, accum, split": ("SK 4, 6 x 20", "stats", "fwd", {"accum"}),
+    "stats, data gradient, unsplit": ("unsplit", "stats", "dgrad", set()),
+    "stats, data gradient, split": ("SK 3", "stats", "dgrad", set()),
+    "stats, short, unsplit": ("unsplit", "stats", "fwd", {"short"}),
+    "stats, short, split": ("SK 5", "stats", "fwd", {"short"}),
+    "backward, forward gather, unsplit": ("unsplit", "backward", "fwd", set()),
+    "backward, forward gather, split": ("SK 2", "backward", "fwd", set()),
+    "backward, reflection fold, unsplit": ("unsplit", "backward", "dgrad_reflect", set()),
+    "backward, reflection fold, split": ("SK 4, 6 x 20", "backward", "dgrad_reflect", set()),
+    "backward, accum, unsplit": ("unsplit", "backward", "dgrad", {"accum"}),
+    "backward, accum, split": ("SK 5", "backward", "dgrad", {"accum"}),
+    "backward, elu, unsplit": ("unsplit", "backward", "dgrad", {"elu"}),
+    "backward, elu, split": ("SK 3", "backward", "dgrad", {"elu"}),
+    "backward, short, unsplit": ("unsplit", "backward", "dgrad", {"short"}),
+    "backward, short, split": ("SK 2", "backward", "dgrad", {"short"}),
+}
+_no_emit_refs = {}
+
+
+def _no_emit_ref(shape, gather):
+    """operands and the float64 result of the bare convolution, once per (shape, gather)"""
+    key = (shape, gather)
+    if key not in _no_emit_refs:
+        N, H, W, C0, Nout = NO_EMIT_SHAPES[shape][:5]
+        x = rnd((N, C0, H, W), 801)
+        if gather == "fwd":
+            w = rnd((Nout, C0, 3, 3), 802, -0.1, 0.1)
+            ref = F.conv2d(x.double(), w.double(), None, 1, 1)
+        else:                                            # the gradient of a forward convolution Nout -> C0 with respect to its input
+            w = rnd((C0, Nout, 3, 3), 802, -0.1, 0.1)
+            xin = torch.zeros((N, Nout, H, W), dtype=torch.float64, requires_grad=True)
+            pad = F.pad(xin, (1, 1, 1, 1), mode="reflect") if gather == "dgrad_reflect" else F.pad(xin, (1, 1, 1, 1))
+            F.conv2d(pad, w.double()).backward(x.double())
+            ref = xin.grad
+        _no_emit_refs[key] = (x, w, ref)
+    return _no_emit_refs[key]
+
+
+@pytest.mark.parametrize("fmt", ["fp16_pair", "exact"])
+@pytest.mark.parametrize("case", list(NO_EMIT_TILE))
+def test_tile_launches_that_must_not_emit(case, fmt):
+    """the sibling of test_gpu_igemm_epilogue.py's test_launches_that_must_not_emit for fp_conv3x3_hp / fp_conv3x3_bf3: a launch that lacks
+    one condition of the sink rule (csrc/fp_common.h, next to FpBnSink) reports nblk == 0, leaves the partials buffer untouched and stores
+    exactly what it stores without a sink -- on an unsplit grid, where the kernel's epilogue would emit, and on a split one, where the reduce
+    launch would"""
+    ops, L = _ops()
+    shape, sink, gather, opts = NO_EMIT_TILE[case]
+    N, H, W, C0, Nout, (th, tw), SK = NO_EMIT_SHAPES[shape]
+    x, w, ref = _no_emit_ref(shape, gather)
+    M, per = N * H * W, 3 if sink == "stats" else 2
+    d = ops.make_desc(N, H, W, H, W, C0, 0, Nout, 3, 1, 1, {"fwd": L.GATHER_FWD_ZERO, "dgrad": L.GATHER_DGRAD_ZERO, "dgrad_reflect": L.GATHER_DGRAD_REFLECT}[gather],
+                      act=L.ACT_ELU if "elu" in opts else 0, epi=L.EPI_ACCUM if "accum" in opts else 0)
+    assert ops.conv3x3_bf3_supported(d)
+    if not any(k.startswith("FP_TILE_") for k in os.environ):                 # the table's grid forms are those of the default plan
+        assert ops._cached_query("fp_conv3x3_bf3_workspace", d) == (SK * M * Nout * 4 if SK > 1 else 0)
+    kw = {}
+    ref = ref.clone()
+    if "bias" in opts:
+        b = rnd((Nout,), 803)
+        kw["bias"], ref = b.cuda(), ref + b.double().view(1, -1, 1, 1)
+    if "addend" in opts:
+        add = rnd((N, Nout, H, W), 804)
+        kw["addend"], ref = nhwc(add), ref + add.double()
+    if "elu" in opts:
+        ref = F.elu(ref)
+    y0 = rnd((N, Nout, H, W), 805) if "accum" in opts else torch.full((N, Nout, H, W), float("nan"))
+    if "accum" in opts:
+        ref = ref + y0.double()
+    emit_blocks = N * -(-H // th) * -(-W // tw) if SK == 1 else reduce_geometry(M, Nout)[1]
+    cap = emit_blocks * Nout * per - 1 if "short" in opts else max(N * -(-H // 6) * -(-W // 16), reduce_geometry(M, Nout)[1]) * Nout * per + 5
+    part = torch.full((cap,), float("nan"), device="cuda")
+    if sink == "backward":
+        z = rnd((M, Nout), 806).cuda()
+        cell = ops.bn_bwd_out(part, z, z.mean(0), 1.0 / torch.sqrt(z.var(0, unbiased=False) + 1e-5))
+    else:
+        cell = ops.bn_stats_out(part)
+    hp = fmt == "fp16_pair"
+    if hp:
+        wp, sw = pack_hp(w, dgrad=gather != "fwd")
+    else:
+        from tests.test_gpu_kernels import pack_bf3
+        wp, sw = pack_bf3(w, dgrad=gather != "fwd"), None
+    xs = nhwc(x)
+
+    def conv(bn_out):
+        y = nhwc(y0)
+        if hp:
+            ops.conv3x3_hp(d, xs, wp, y, slot_of(xs), sw, bn_out=bn_out, **kw)
+        else:
+            ops.conv3x3_bf3(d, xs, wp, y, bn_out=bn_out, **kw)
+        return y
+    y = conv(cell)
+    torch.cuda.synchronize()
+    print("TILE_NOEMIT | %s | %s | nblk %d | y %.3e" % (fmt, case, cell.nblk, relerr(nchw(y), ref)))
+    assert cell.nblk == 0, cell.nblk
+    assert bool(torch.isnan(part).all()), "a launch that reports nothing emitted wrote into the partials buffer"
+    assert torch.equal(y, conv(None))
+    check(nchw(y), ref, "tile launch with an armed sink it cannot serve: " + case, 2e-6)
 
 
 @pytest.mark.parametrize("N,h,w,C0,C1,Cout", [(12, 6, 20, 256, 256, 256), (8, 24, 32, 32, 16, 32), (16, 16, 32, 32, 0, 64), (12, 4, 24, 64, 64, 96)])

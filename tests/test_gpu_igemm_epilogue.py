@@ -1,6 +1,6 @@
 """GPU: the epilogues and the BatchNorm side output of the flattened convolutions (csrc/conv_igemm.hip: igemm_hp_kernel<TN, NP> behind
-fp_conv_igemm_bf3 / fp_conv_igemm_hp, igemm_kernel behind fp_conv_igemm, igemm_store_tile, splitk_reduce_kernel,
-splitk_reduce_stats_kernel), every launch against float64 of the same fp32 operands:
+fp_conv_igemm_bf3 / fp_conv_igemm_hp, igemm_kernel behind fp_conv_igemm, igemm_store_tile, and the reduce launch fp_splitk_finish picks for a
+split grid: splitk_reduce_kernel or splitk_reduce_stats_kernel), every launch against float64 of the same fp32 operands:
 
     acc (+bias) -> +addend * (mask > 0) -> * actgrad (ELU: sv > 0 ? 1 : sv + 1; ReLU: sv > 0) -> act -> + previous y
 
@@ -87,8 +87,8 @@ def _dims(g):
 
 
 def grid_form(fmt, g):
-    """the launcher's decision restated (conv_igemm.hip: fp_conv_igemm / igemm_split_operands pick the tile, fp_conv_igemm_workspace and
-    pick_splitk the split): (form, SK)"""
+    """the launcher's decision restated (conv_igemm.hip: fp_conv_igemm / igemm_split_operands pick the tile; fp_conv_igemm_workspace, the
+    clamp of igemm_fill and plan_grid with pick_splitk the split): (form, SK)"""
     M, Nout, C0, T, pm = _dims(g)
     if pm:
         return "parity-major", 1
