@@ -318,13 +318,9 @@ extern "C" int32_t fp_resize_ksize(int32_t in_size, int32_t out_size, int32_t fi
   return ks < (double)(1 << 30) ? (int32_t)ks : -1;
 }
 
-// Resample.c precompute_coeffs + normalize_coeffs_8bpc
-extern "C" int fp_resize_coeffs(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* kk, int32_t ksize) {
-  double (*fn)(double);
-  double support;
-  FP_REQUIRE(bounds && kk && in_size > 0 && out_size > 0, "fp_resize_coeffs: bad arguments");
-  FP_REQUIRE(filter_of(filter, &fn, &support), "fp_resize_coeffs: filter must be FP_RESIZE_LANCZOS, _BILINEAR, _BICUBIC or _BOX");
-  FP_REQUIRE(ksize == fp_resize_ksize(in_size, out_size, filter), "fp_resize_coeffs: ksize differs from fp_resize_ksize");
+// Resample.c precompute_coeffs: the double stage both table forms share.  kk double [out][ksize] = the taps normalised by their running
+// sum, rows padded with zeros; bounds [out][2] = first source index, tap count.  The caller has checked the arguments.
+static void precompute_coeffs(int32_t in_size, int32_t out_size, double (*fn)(double), double support, int32_t* bounds, double* kk, int32_t ksize) {
   const double scale = (double)in_size / out_size;
   const double filterscale = scale < 1.0 ? 1.0 : scale;
   support = support * filterscale;
@@ -337,24 +333,45 @@ extern "C" int fp_resize_coeffs(int32_t in_size, int32_t out_size, int32_t filte
     int xmax = (int)(center + support + 0.5);
     if (xmax > in_size) xmax = in_size;
     xmax -= xmin;
-    int32_t* k = kk + (size_t)xx * ksize;
-    // Pillow keeps the double weights in the table and quantises afterwards; a row of its own here
-    double wrow[64], *wp = xmax <= 64 ? wrow : (double*)malloc(sizeof(double) * (size_t)xmax);
-    FP_REQUIRE(wp, "fp_resize_coeffs: out of memory");
+    double* k = kk + (size_t)xx * ksize;
     for (int x = 0; x < xmax; ++x) {
       const double w = fn((x + xmin - center + 0.5) * ss);
-      wp[x] = w;
+      k[x] = w;
       ww += w;
     }
-    for (int x = 0; x < xmax; ++x) {
-      if (ww != 0.0) wp[x] /= ww;
-      k[x] = wp[x] < 0 ? (int)(-0.5 + wp[x] * (1 << PRECISION_BITS)) : (int)(0.5 + wp[x] * (1 << PRECISION_BITS));
-    }
+    for (int x = 0; x < xmax; ++x)
+      if (ww != 0.0) k[x] /= ww;
     for (int x = xmax; x < ksize; ++x) k[x] = 0;
-    if (wp != wrow) free(wp);
     bounds[xx * 2 + 0] = xmin;
     bounds[xx * 2 + 1] = xmax;
   }
+}
+
+// the taps as Pillow's 32-bit-per-channel passes (mode "F") use them: normalised, not quantised
+extern "C" int fp_resize_coeffs_f64(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, double* kk, int32_t ksize) {
+  double (*fn)(double);
+  double support;
+  FP_REQUIRE(bounds && kk && in_size > 0 && out_size > 0, "fp_resize_coeffs_f64: bad arguments");
+  FP_REQUIRE(filter_of(filter, &fn, &support), "fp_resize_coeffs_f64: filter must be FP_RESIZE_LANCZOS, _BILINEAR, _BICUBIC or _BOX");
+  FP_REQUIRE(ksize == fp_resize_ksize(in_size, out_size, filter), "fp_resize_coeffs_f64: ksize differs from fp_resize_ksize");
+  precompute_coeffs(in_size, out_size, fn, support, bounds, kk, ksize);
+  return 0;
+}
+
+// Resample.c precompute_coeffs + normalize_coeffs_8bpc
+extern "C" int fp_resize_coeffs(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* kk, int32_t ksize) {
+  double (*fn)(double);
+  double support;
+  FP_REQUIRE(bounds && kk && in_size > 0 && out_size > 0, "fp_resize_coeffs: bad arguments");
+  FP_REQUIRE(filter_of(filter, &fn, &support), "fp_resize_coeffs: filter must be FP_RESIZE_LANCZOS, _BILINEAR, _BICUBIC or _BOX");
+  FP_REQUIRE(ksize == fp_resize_ksize(in_size, out_size, filter), "fp_resize_coeffs: ksize differs from fp_resize_ksize");
+  // Pillow keeps the double weights in the table and quantises afterwards
+  double* w = (double*)malloc(sizeof(double) * (size_t)out_size * (size_t)ksize);
+  FP_REQUIRE(w, "fp_resize_coeffs: out of memory");
+  precompute_coeffs(in_size, out_size, fn, support, bounds, w, ksize);
+  for (size_t i = 0, n = (size_t)out_size * (size_t)ksize; i < n; ++i)
+    kk[i] = w[i] < 0 ? (int)(-0.5 + w[i] * (1 << PRECISION_BITS)) : (int)(0.5 + w[i] * (1 << PRECISION_BITS));
+  free(w);
   return 0;
 }
 

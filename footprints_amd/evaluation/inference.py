@@ -8,6 +8,10 @@ sigmoid and rounds to float16 on the device, so the D2H copy is half the bytes a
 File decoding (KITTI, Matterport, handheld readers) stays on the host; the reader's `Image.resize((W, H), LANCZOS)` + ToTensor
 (datasets/inference_dataset.py:26,48) can run on the device: `InferenceManager(..., device_resize=True, height_width=(H, W))` takes
 `inputs['raw_image']`, the decoded uint8 frames at their native sizes, uploads them once and produces the same input tensor bit for bit.
+With `save_test_visualisations=True` (the reference's --save_test_visualisations, inference.py:110-119) `run` also writes <stem>.jpg: the
+network's input beside the hidden-ground mask in the first and last colour of matplotlib's plasma map, drawn by one kernel
+(`fp_vis_side_by_side`) from the logits -- `logit > 0` where the reference tests `sigmoid > 0.5`, the same except for positive logits
+below fp32's resolution at 0.5.  The picture is encoded by Pillow on the host (the reference calls plt.imsave).
 """
 import os
 
@@ -19,7 +23,8 @@ from ..model_manager import ModelManager
 
 
 class InferenceManager:
-    def __init__(self, load_path=None, model_manager=None, save_path=None, device_resize=False, height_width=None):
+    def __init__(self, load_path=None, model_manager=None, save_path=None, device_resize=False, height_width=None,
+                 save_test_visualisations=False):
         if device_resize and height_width is None:
             raise ValueError("device_resize=True needs height_width=(H, W), the network's input size")
         self.device_resize, self.height_width = bool(device_resize), height_width
@@ -32,6 +37,13 @@ class InferenceManager:
         self.model.eval()
         self.model.inference_scales = ("1/1",)          # "just take max resolution prediction" (inference.py:104)
         self.savepath = save_path
+        self.save_test_visualisations = bool(save_test_visualisations)
+
+    @classmethod
+    def from_options(cls, opt, model_manager=None, **kwargs):
+        """the manager the command line describes: --load_path, --inference_save_path, --save_test_visualisations (options.py)"""
+        return cls(load_path=opt.load_path, model_manager=model_manager, save_path=opt.inference_save_path,
+                   save_test_visualisations=opt.save_test_visualisations, **kwargs)
 
     def input_tensor(self, inputs):
         """the network's input [B,3,H,W] on the device"""
@@ -42,10 +54,19 @@ class InferenceManager:
     def test_batch(self, inputs):
         """inputs['image']: [B,3,H,W] float tensor -- or, with device_resize, inputs['raw_image']: list of B decoded uint8 [h,w,3] frames.
         Returns a float16 numpy array [B,4,H,W]: sigmoid(mask logits), depth."""
+        return self._test_batch(inputs, False)[0]
+
+    def _test_batch(self, inputs, visualise):
         image = self.input_tensor(inputs)
         with torch.no_grad():
             pred = self.model(image)["1/1"]
-            return ops.pack_pred_fp16(pred).cpu().numpy()
+            vis = self.visualise_batch(image, pred) if visualise else None
+            return ops.pack_pred_fp16(pred).cpu().numpy(), vis
+
+    def visualise_batch(self, image, pred):
+        """image: the network's input [B,3,H,W] on the device, pred: its logits [B,4,H,W] -> uint8 numpy [B,H,2W,3]: the input beside the
+        two-colour hidden-ground mask (reference inference.py:114-118), drawn on the device"""
+        return ops.vis_side_by_side(image.contiguous(), pred.contiguous()).cpu().numpy()
 
     def save_result(self, filename, prediction, savepath=None):
         savepath = savepath or self.savepath
@@ -55,6 +76,12 @@ class InferenceManager:
     def run(self, loader):
         """loader yields dicts with 'image' and 'idx' (file stems), like the reference's InferenceDataset batches"""
         for inputs in loader:
-            preds = self.test_batch(inputs)
+            if not self.save_test_visualisations:
+                preds, vis = self.test_batch(inputs), None
+            else:
+                preds, vis = self._test_batch(inputs, True)
             for i, pred in enumerate(preds):
                 self.save_result(inputs["idx"][i], pred)
+                if vis is not None:
+                    from PIL import Image
+                    Image.fromarray(vis[i]).save(os.path.join(self.savepath, "{}.jpg".format(inputs["idx"][i])), quality=95)

@@ -1062,12 +1062,17 @@ class ResizeTableSet:
         with self.lock:
             i = self.keys.get(key)
             if i is None:
-                bounds, kk = resize_tables(*key)
+                bounds, kk, ksize = self._host_tables(key)
                 i = self.keys[key] = len(self.records)
-                self.records.append(_lib.ResizeTable(key[0], key[1], kk.shape[1], self.length, self.length + bounds.size))
-                self.coeffs += [bounds.reshape(-1), kk.reshape(-1)]
+                self.records.append(_lib.ResizeTable(key[0], key[1], ksize, self.length, self.length + bounds.size))
+                self.coeffs += [bounds, kk]
                 self.length += bounds.size + kk.size
         return i
+
+    def _host_tables(self, key):
+        """(bounds, kk, ksize) of one axis as flat arrays of the buffer's element type"""
+        bounds, kk = resize_tables(*key)
+        return bounds.reshape(-1), kk.reshape(-1), kk.shape[1]
 
     def device_buffers(self):
         """(table records, count, coefficient buffer) on the device"""
@@ -1207,3 +1212,162 @@ def load_images_u8(images, H, W, filter="lanczos", device="cuda"):
     """Resize((H, W)) + ToTensor of decoded RGB frames (numpy uint8 [h, w, 3], any sizes) on the device: one upload of the raw bytes
     -> float32 [B, 3, H, W], bit-equal to PIL's resize followed by a division by 255 in float32"""
     return to_tensor_u8(resize_u8(images, H, W, filter, device))
+
+
+# ---- visualisations on the device: predict_simple's overlay and the test-set side-by-side picture (csrc/visualise.hip) -----------------------
+_vis_host_tables = {}
+
+
+def vis_tables(in_size, out_size, filter="bilinear"):
+    """the tables of `resize_tables` before the quantisation, as Pillow's mode-"F" passes use them, cached per (in, out, filter)
+    -> (bounds int32 [out, 2], kk float64 [out, ksize] = the taps normalised in double)"""
+    import numpy as np
+    key = (int(in_size), int(out_size), _resize_filter(filter))
+    t = _vis_host_tables.get(key)
+    if t is None:
+        lib = _lib.load()
+        ksize = lib.fp_resize_ksize(*key)
+        if ksize < 0:
+            raise ValueError("footprints_amd.ops.vis_tables: bad sizes %r" % (key,))
+        bounds, kk = np.empty((key[1], 2), np.int32), np.empty((key[1], ksize), np.float64)
+        _lib.check(lib.fp_resize_coeffs_f64(key[0], key[1], key[2], bounds.ctypes.data, kk.ctypes.data, ksize), "fp_resize_coeffs_f64")
+        bounds.setflags(write=False)
+        kk.setflags(write=False)
+        t = _vis_host_tables[key] = (bounds, kk)
+    return t
+
+
+class VisTableSet(ResizeTableSet):
+    """ResizeTableSet over the double tables: one buffer of 8-byte elements (uploaded as int64, bit for bit) in which a table's bounds take
+    one element per output index and its taps one each; offsets count those elements"""
+
+    def index(self, in_size, out_size, filter="bilinear"):
+        return super().index(in_size, out_size, filter)
+
+    def _host_tables(self, key):
+        import numpy as np
+        bounds, kk = vis_tables(*key)
+        return bounds.view(np.int64).reshape(-1), kk.view(np.int64).reshape(-1), kk.shape[1]
+
+
+_vis_table_sets = {}
+_vis_luts = {}
+
+
+def vis_table_set(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    s = _vis_table_sets.get(device)
+    if s is None:
+        assert _lib.load().fp_resize_table_bytes() == C.sizeof(_lib.ResizeTable) and _lib.load().fp_resize_sample_bytes() == C.sizeof(_lib.ResizeSample)
+        s = _vis_table_sets[device] = VisTableSet(device)
+    return s
+
+
+def vis_colour_table():
+    """uint8 [256, 3] numpy: matplotlib's plasma map with 256 entries, `(rgba[:, :3] * 255).astype(uint8)`, read at first use"""
+    import numpy as np
+    lut = _vis_luts.get("host")
+    if lut is None:
+        import matplotlib
+        # what matplotlib.pyplot.get_cmap("plasma", 256) returns, without importing pyplot or touching the caller's backend
+        rgba = matplotlib.colormaps["plasma"].resampled(256)(np.arange(256))
+        lut = _vis_luts["host"] = np.ascontiguousarray((rgba[:, :3] * 255).astype(np.uint8))
+        lut.setflags(write=False)
+    return lut
+
+
+def _vis_lut(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    t = _vis_luts.get(device)
+    if t is None:
+        t = _vis_luts[device] = torch.from_numpy(vis_colour_table().copy()).to(device)
+    return t
+
+
+def vis_records(shapes, H, W, tables):
+    """fp_resize_sample records of photos of `shapes` = [(h, w), ...] lying one after the other in a packed buffer, for a prediction of
+    H x W -> (records uint8 numpy, bytes of the packed buffer, max_h, max_w)"""
+    import numpy as np
+    rec = (_lib.ResizeSample * len(shapes))()
+    off = 0
+    for b, (h, w) in enumerate(shapes):
+        rec[b] = _lib.ResizeSample(off, h, w, tables.index(W, w), tables.index(H, h))
+        off += h * w * 3
+    return np.frombuffer(bytes(rec), dtype=np.uint8).copy(), off, max(s[0] for s in shapes), max(s[1] for s in shapes)
+
+
+def vis_overlay_packed(pred, src, src_bytes, samples, max_h, max_w, tables, out=None, check=False):
+    """device half of the overlay: pred float32 [B, 4, H, W], `src` the packed photos (uint8 device buffer, src_bytes used), `samples`
+    B fp_resize_sample records on the device (vis_records) -> uint8 device buffer with the photos' layout.  check=True reads the
+    library's status word afterwards (this WAITS for the stream) and raises ValueError when a record was turned down."""
+    lib = _lib.load()
+    if pred.dim() != 4 or pred.shape[1] != 4:
+        raise RuntimeError("footprints_amd.ops.vis_overlay_packed: pred must be float32 [B, 4, H, W]")
+    B, _, H, W = pred.shape
+    d_tables, n_tables, d_coeffs = tables.device_buffers()
+    if out is None:
+        out = torch.empty(int(src_bytes), dtype=torch.uint8, device=pred.device)
+    if out.dtype != torch.uint8 or src.dtype != torch.uint8 or src.numel() < src_bytes or out.numel() < src_bytes:
+        raise RuntimeError("footprints_amd.ops.vis_overlay_packed: src and out must be uint8 buffers of at least src_bytes bytes")
+    if samples.numel() * samples.element_size() < B * C.sizeof(_lib.ResizeSample):
+        raise RuntimeError("footprints_amd.ops.vis_overlay_packed: fewer than B sample records")
+    need = lib.fp_vis_overlay_workspace(B, H, W, max_h, max_w)
+    if need < 0:
+        raise RuntimeError("footprints_amd.ops.vis_overlay_packed: bad sizes, or too large")
+    ws = workspace(need, pred.device, "vis")
+    _lib.check(lib.fp_vis_overlay(_f32(pred, "pred"), _chk(src, "src"), int(src_bytes), _chk(samples, "samples"), _chk(d_tables) if n_tables else None,
+                                  n_tables, _chk(d_coeffs) if n_tables else None, d_coeffs.numel() if n_tables else 0, _chk(_vis_lut(pred.device)),
+                                  _chk(out, "out"), B, H, W, max_h, max_w, ws.data_ptr(), ws.numel(), stream()), "fp_vis_overlay")
+    if check:
+        off = lib.fp_vis_overlay_status_offset(B, H, W, max_h, max_w)
+        if int(ws[off:off + 4].view(torch.int32).item()) != 0:
+            raise ValueError("footprints_amd.ops.vis_overlay_packed: a sample or table record was turned down on the device; its output is unwritten")
+    return out
+
+
+def vis_overlay(pred, originals=None, packed=None, shapes=None):
+    """predict_simple.InferenceManager.visualise for a batch, byte for byte, in one library call and one copy to the host:
+    pred float32 device [B, 4, H, W]; the photos either as `originals` (list of numpy uint8 [h, w, 3] of any sizes, uploaded here) or, when
+    they are on the device already (the buffer resize_pack filled, uploaded for the device resize), as `packed` + `shapes` = their
+    (h, w) in the buffer's order -> list of B numpy uint8 [h, w, 3]"""
+    import numpy as np
+    B, H, W = pred.shape[0], pred.shape[2], pred.shape[3]
+    if (originals is None) == (packed is None) or (packed is not None and shapes is None):
+        raise ValueError("footprints_amd.ops.vis_overlay: pass either originals, or packed and shapes")
+    if originals is not None:
+        if any(im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 for im in originals):
+            raise ValueError("footprints_amd.ops.vis_overlay: originals must be uint8 [h, w, 3]")
+        shapes = [im.shape[:2] for im in originals]
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    if len(shapes) != B:
+        raise ValueError("footprints_amd.ops.vis_overlay: %d predictions, %d photos" % (B, len(shapes)))
+    tables = vis_table_set(pred.device)
+    records, total, max_h, max_w = vis_records(shapes, H, W, tables)
+    if originals is not None:
+        packed = torch.from_numpy(np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in originals])).to(pred.device)
+    out = vis_overlay_packed(pred, packed, total, torch.from_numpy(records).to(pred.device), max_h, max_w, tables)
+    host = out[:total].cpu().numpy()
+    views, off = [], 0
+    for h, w in shapes:
+        views.append(host[off:off + h * w * 3].reshape(h, w, 3))
+        off += h * w * 3
+    return views
+
+
+def vis_side_by_side(image, pred, out=None):
+    """the test-set picture (reference evaluation/inference.py:114-118): image float32 [B, 3, H, W] in [0, 1] and the logits pred
+    [B, 4, H, W] -> uint8 device tensor [B, H, 2 W, 3], the image as bytes beside the mask channel in the colour table's first and last colour"""
+    B, _, H, W = pred.shape
+    if tuple(image.shape) != (B, 3, H, W) or pred.shape[1] != 4:
+        raise RuntimeError("footprints_amd.ops.vis_side_by_side: image must be [B, 3, H, W] and pred [B, 4, H, W]")
+    if out is None:
+        out = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8, device=pred.device)
+    lut = vis_colour_table()
+    colour = lambda c: int(c[0]) | int(c[1]) << 8 | int(c[2]) << 16
+    _lib.check(_lib.load().fp_vis_side_by_side(_f32(image, "image"), _f32(pred, "pred"), _chk(out, "out"), B, H, W, colour(lut[0]), colour(lut[255]),
+                                               stream()), "fp_vis_side_by_side")
+    return out

@@ -9,6 +9,15 @@ restated without the libraries this image lacks: torchvision's Resize(ANTIALIAS)
 numpy (identical arithmetic), cv2.resize(bilinear) becomes PIL BILINEAR, cv2.imwrite becomes PIL save.
 The reference quirk of thresholding the *logit* at 0.5 for the visualisation mask (predict_simple.py:77) is
 kept.  `--no_cuda` is accepted for CLI compatibility but raises: this package has no CPU compute path.
+
+Two options beyond the reference, both off by default (without them nothing here behaves differently):
+`--device_vis` draws the overlay on the GPU (csrc/visualise.hip), byte for byte what `InferenceManager.visualise` -- the host path, kept
+as it is -- gives for the same prediction: Pillow's mode-"F" BILINEAR restated, not the reference's cv2.resize; the JPEG encoder stays
+on the host.  `--batch_size N` predicts a folder N files at a time, in sorted order: one forward pass, one copy of the predictions and
+(with --device_vis) one overlay call and one copy of the overlays per group; the photos of a group may differ in size, and the same
+files are written under the same names.  A batched forward pass differs from per-image passes at fp32 round-off -- the small
+convolutions split their K loop by a rule that depends on the batch size -- so a .npy of a batched run is within the contract's 1e-4 of
+its channel maximum of the per-image one, not bit-equal; every overlay still equals `visualise` of its own .npy.
 """
 import argparse
 import os
@@ -39,7 +48,7 @@ def preprocess(pil_image, height_width, device_resize=False):
 
 class InferenceManager:
     def __init__(self, model_name, save_dir, use_cuda=True, save_visualisations=True, weights_path=None, model_manager=None,
-                 device_resize=False):
+                 device_resize=False, device_vis=False, batch_size=1):
         if not use_cuda or not torch.cuda.is_available():
             raise RuntimeError("footprints_amd.predict_simple needs a MI355X: the package has no CPU compute path "
                                "(--no_cuda is accepted for CLI compatibility only)")
@@ -52,6 +61,10 @@ class InferenceManager:
         self.model_manager.model.eval()
         self.model_manager.model.inference_scales = ("1/1",)      # only the full-resolution prediction is consumed below
         self.device_resize = bool(device_resize)
+        self.device_vis, self.batch_size = bool(device_vis), int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        self.overlay_hook = None       # callable(file stem, uint8 [h, w, 3]): sees every overlay before it is encoded
         self.save_dir = save_dir
         os.makedirs(os.path.join(save_dir, "outputs"), exist_ok=True)
         self.save_visualisations = save_visualisations
@@ -65,6 +78,8 @@ class InferenceManager:
         return pred["1/1"].cpu().numpy().squeeze(0)          # [4,H,W]
 
     def predict_for_single_image(self, image_path):
+        if self.device_vis:
+            return self.predict_for_images([image_path])[0]
         print("Predicting for {}".format(image_path))
         original = pil_loader(image_path)
         pred = self.predict_array(original)
@@ -73,11 +88,51 @@ class InferenceManager:
         print("└> Saving predictions to {}".format(npy_save_path))
         np.save(npy_save_path, pred)
         if self.save_visualisations:
-            vis = self.visualise(pred, original)
-            vis_save_path = os.path.join(self.save_dir, "visualisations", filename + ".jpg")
-            print("└> Saving visualisation to {}".format(vis_save_path))
-            Image.fromarray(vis).save(vis_save_path, quality=95)
+            self._save_visualisation(filename, self.visualise(pred, original))
         return pred
+
+    def _save_visualisation(self, filename, vis):
+        if self.overlay_hook is not None:
+            self.overlay_hook(filename, vis)
+        vis_save_path = os.path.join(self.save_dir, "visualisations", filename + ".jpg")
+        print("└> Saving visualisation to {}".format(vis_save_path))
+        Image.fromarray(vis).save(vis_save_path, quality=95)
+
+    def predict_for_images(self, image_paths):
+        """one group of files in ONE forward pass: the same artefacts as predict_for_single_image on each; returns [B,4,H,W].
+        With device_resize the decoded photos are uploaded once, for the resize and for the overlay."""
+        from . import ops
+        originals = [pil_loader(p) for p in image_paths]
+        for p in image_paths:
+            print("Predicting for {}".format(p))
+        h, w = self.height_width
+        packed = None
+        if self.device_resize:
+            arrays = [np.asarray(o, dtype=np.uint8) for o in originals]
+            tables = ops.resize_table_set("cuda")
+            host, records, total, cn, max_h, max_w = ops.resize_pack(arrays, h, w, tables)
+            packed = torch.from_numpy(host).cuda()
+            x = ops.to_tensor_u8(ops.resize_u8_packed(packed, total, torch.from_numpy(records).cuda(), len(arrays), h, w, cn, max_h, max_w, tables))
+        else:
+            x = torch.cat([preprocess(o, self.height_width) for o in originals]).cuda()
+        with torch.no_grad():
+            pred_dev = self.model_manager.model(x)["1/1"].contiguous()
+        preds = pred_dev.cpu().numpy()                           # [B,4,H,W]: one copy for the group
+        overlays = None
+        if self.save_visualisations and self.device_vis:
+            shapes = [(o.size[1], o.size[0]) for o in originals]
+            if packed is not None:
+                overlays = ops.vis_overlay(pred_dev, packed=packed, shapes=shapes)
+            else:
+                overlays = ops.vis_overlay(pred_dev, originals=[np.asarray(o, dtype=np.uint8) for o in originals])
+        for i, path in enumerate(image_paths):
+            filename, _ = os.path.splitext(os.path.basename(path))
+            npy_save_path = os.path.join(self.save_dir, "outputs", filename + ".npy")
+            print("└> Saving predictions to {}".format(npy_save_path))
+            np.save(npy_save_path, preds[i])
+            if self.save_visualisations:
+                self._save_visualisation(filename, overlays[i] if overlays is not None else self.visualise(preds[i], originals[i]))
+        return preds
 
     @staticmethod
     def visualise(pred, original):
@@ -111,6 +166,10 @@ class InferenceManager:
             targets = [image_path]
         else:
             raise FileNotFoundError("--image: no such file or folder: %r" % (image_path,))
+        if self.batch_size > 1:
+            for i in range(0, len(targets), self.batch_size):
+                self.predict_for_images(targets[i:i + self.batch_size])
+            return len(targets)
         for path in targets:
             self.predict_for_single_image(path)
         return len(targets)
@@ -128,6 +187,8 @@ def parse_args(argv=None):
     ap.add_argument("--weights", type=str, default=None,
                     help="folder holding model.pth (default: %s/<model>; this build cannot download)" % MODEL_DIR)
     ap.add_argument("--device_resize", action="store_true", help="resize the decoded image on the GPU (same bytes as PIL's LANCZOS)")
+    ap.add_argument("--device_vis", action="store_true", help="draw the overlays on the GPU (same bytes as the host path before the JPEG encoder)")
+    ap.add_argument("--batch_size", type=int, default=1, help="files of a folder per forward pass (sorted order; sizes may differ)")
     return ap.parse_args(argv)
 
 
@@ -135,7 +196,7 @@ def main(argv=None):
     args = parse_args(argv)
     manager = InferenceManager(model_name=args.model, use_cuda=torch.cuda.is_available() and not args.no_cuda,
                                save_visualisations=not args.no_save_vis, save_dir=args.save_dir, weights_path=args.weights,
-                               device_resize=args.device_resize)
+                               device_resize=args.device_resize, device_vis=args.device_vis, batch_size=args.batch_size)
     manager.predict(image_path=args.image)
 
 

@@ -488,7 +488,8 @@ int fp_assemble_labels(const void* visible_ground, const void* ground_depth, con
                        double depth_scaling, fp_stream_t stream);
 
 /* ---- device-side reader work: Pillow's 8-bit Image.resize and filter_depth_mask (footprint_dataset.py:73-80, :96-105; csrc/reader.hip) ---- */
-/* Resample filters, numbered like Pillow's Image.Resampling.  NEAREST (0) and the mode-"F" paths are not provided. */
+/* Resample filters, numbered like Pillow's Image.Resampling.  NEAREST (0) is not provided; of the mode-"F" (float) paths only
+ * what the overlay below needs: the double tables as an entry point of their own, the float passes inside the overlay. */
 #define FP_RESIZE_LANCZOS 1
 #define FP_RESIZE_BILINEAR 2
 #define FP_RESIZE_BICUBIC 3
@@ -532,6 +533,34 @@ int fp_resize_u8(const uint8_t* src, int64_t src_bytes, const void* samples, con
 int64_t fp_filter_depth_mask_workspace(int32_t B, int32_t H, int32_t W);
 int fp_filter_depth_mask(const void* mask, int32_t is_double, void* out, int32_t B, int32_t H, int32_t W, void* workspace,
                          int64_t workspace_bytes, fp_stream_t stream);
+
+/* ---- device-side visualisations (footprints/predict_simple.py:75-92, footprints/evaluation/inference.py:114-118; csrc/visualise.hip) ---- */
+/* HOST function (no GPU needed): the tables of fp_resize_coeffs before the quantisation -- kk double [out][ksize] = the taps normalised in
+ * double, as Pillow's mode-"F" passes use them; bounds as there.  Both functions share the double stage. */
+int fp_resize_coeffs_f64(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, double* kk, int32_t ksize);
+/* The overlay of footprints_amd.predict_simple.InferenceManager.visualise for B predictions, byte for byte: pred float [B][4][H][W]
+ * (channel 1 = hidden-ground logit, channel 3 = hidden-depth sigmoid).  The B photos are dense uint8 [h][w][3] at any byte offsets of `src`
+ * (4-byte aligned, `bytes` long); `out` has the same length and layout.  samples: B fp_resize_sample records on the device, here with
+ * (h, w) = the photo's size, table_h = index of its (W -> w) table and table_v = index of its (H -> h) table (-1 = equal sizes).  tables:
+ * n_tables fp_resize_table records over `coeffs`, a device buffer of coeffs_len 8-BYTE elements in which offsets count: a table's bounds are
+ * one element per output index (two int32: first source index, tap count), its kk the doubles of fp_resize_coeffs_f64.  lut: uint8
+ * [256][3].  Per sample: both maps through Pillow's float resample (double accumulation in tap order, float store, horizontal pass first,
+ * a pass whose sizes agree skipped), the depth as float 1 / (0.01 + 9.99 d) first; mask = logit > 0.5; where the mask is not empty the
+ * depth is normalised by its minimum and maximum inside the mask (float; a range below 1e-12 counts as 1e-12); index = the clipped depth
+ * times 256, 256 -> 255, truncated, clamped to 0..255; out = lut[index] inside the mask, the photo's bytes outside.  Integer atomics only:
+ * the result does not depend on scheduling.  A record that points outside a buffer, or whose table does not fit its sizes, leaves that
+ * sample's output unwritten and sets the int32 status word of the workspace (at the status offset; every call clears it first; read it
+ * after the stream has finished).  The workspace query returns -1 on bad arguments or when the sizes are too large. */
+int64_t fp_vis_overlay_workspace(int32_t B, int32_t H, int32_t W, int32_t max_h, int32_t max_w);
+int64_t fp_vis_overlay_status_offset(int32_t B, int32_t H, int32_t W, int32_t max_h, int32_t max_w);
+int fp_vis_overlay(const float* pred, const uint8_t* src, int64_t bytes, const void* samples, const void* tables, int32_t n_tables,
+                   const double* coeffs, int64_t coeffs_len, const uint8_t* lut, uint8_t* out, int32_t B, int32_t H, int32_t W, int32_t max_h,
+                   int32_t max_w, void* workspace, int64_t workspace_bytes, fp_stream_t stream);
+/* image float [B][3][H][W] in [0,1], pred logits float [B][4][H][W] -> out uint8 [B][H][2W][3]: left half uint8(image * 255.0f), right half
+ * colour1 where pred[:,1] > 0 and colour0 elsewhere (a colour = r | g << 8 | b << 16).  The reference tests sigmoid > 0.5 in fp32, which
+ * differs only for positive logits so small that the fp32 sigmoid rounds to exactly 0.5. */
+int fp_vis_side_by_side(const float* image, const float* pred, uint8_t* out, int32_t B, int32_t H, int32_t W, uint32_t colour0,
+                        uint32_t colour1, fp_stream_t stream);
 
 /* ---- pyramid pooling of the ground-segmentation network (footprints/preprocessing/segmentation/network.py:174-207) ---- */
 /* nn.AdaptiveAvgPool2d(P) (network.py:180,188): y[N][P][P][C] = window means of x[N][H][W][C]; windows floor(i*H/P) .. ceil((i+1)*H/P) */
