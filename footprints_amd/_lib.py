@@ -39,6 +39,26 @@ class ResizeTable(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("in_size", "out_size", "ksize", "bounds_off", "kk_off")]
 
 
+class ResizeWindowTable(C.Structure):
+    """fp_resize_window_table (include/footprints_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("in_size", "out_size", "ksize", "first", "count", "bounds_off", "kk_off")]
+
+
+class ResizeWindowSample(C.Structure):
+    """fp_resize_window_sample (include/footprints_hip.h)"""
+    _fields_ = [("src_offset", C.c_int64), ("out_offset", C.c_int64)] + [(n, C.c_int32) for n in (
+        "src_h", "src_w", "src_y0", "src_x0", "table_h", "table_v", "top", "left", "win_h", "win_w")]
+
+
+class SegLabelSample(C.Structure):
+    """fp_seg_label_sample (include/footprints_hip.h)"""
+    _fields_ = [("src_offset", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "C", "rows_off", "cols_off", "decode", "labelled", "ground_set")]
+
+
+SEG_DECODE_CHANNEL0, SEG_DECODE_ADE20K = 0, 1              # FP_SEG_DECODE_*
+SEG_LABELLED_ONES, SEG_LABELLED_NONZERO = 0, 1             # FP_SEG_LABELLED_*
+
+
 class ResizeSample(C.Structure):
     """fp_resize_sample (include/footprints_hip.h)"""
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("table_h", C.c_int32), ("table_v", C.c_int32)]
@@ -90,6 +110,15 @@ SIGNATURES = {
     "fp_resize_workspace": (_I64, [_I32, _I32, _I32, _I32]),
     "fp_resize_status_offset": (_I64, [_I32, _I32, _I32, _I32]),
     "fp_resize_u8": (C.c_int, [_P, _I64, _P, _P, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_resize_coeffs_range": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I32]),
+    "fp_nearest_index": (C.c_int, [_I32, _I32, _P]),
+    "fp_resize_window_table_bytes": (_I32, []),
+    "fp_resize_window_sample_bytes": (_I32, []),
+    "fp_resize_window_workspace": (_I64, [_I32, _I32, _I32, _I32]),
+    "fp_resize_window_status_offset": (_I64, [_I32, _I32, _I32, _I32]),
+    "fp_resize_window_u8": (C.c_int, [_P, _I64, _P, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_seg_label_sample_bytes": (_I32, []),
+    "fp_seg_labels": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _P]),
     "fp_filter_depth_mask_workspace": (_I64, [_I32, _I32, _I32]),
     "fp_filter_depth_mask": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P, _I64, _P]),
     "fp_resize_coeffs_f64": (C.c_int, [_I32, _I32, _I32, _P, _P, _I32]),

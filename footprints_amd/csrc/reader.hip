@@ -319,13 +319,15 @@ extern "C" int32_t fp_resize_ksize(int32_t in_size, int32_t out_size, int32_t fi
 }
 
 // Resample.c precompute_coeffs: the double stage both table forms share.  kk double [out][ksize] = the taps normalised by their running
-// sum, rows padded with zeros; bounds [out][2] = first source index, tap count.  The caller has checked the arguments.
-static void precompute_coeffs(int32_t in_size, int32_t out_size, double (*fn)(double), double support, int32_t* bounds, double* kk, int32_t ksize) {
+// sum, rows padded with zeros; bounds [out][2] = first source index, tap count.  Pillow computes every output index on its own, so the
+// rows of output indices first .. first + count - 1 alone are the same rows of the whole table.  The caller has checked the arguments.
+static void precompute_coeffs(int32_t in_size, int32_t out_size, double (*fn)(double), double support, int32_t first, int32_t count,
+                              int32_t* bounds, double* kk, int32_t ksize) {
   const double scale = (double)in_size / out_size;
   const double filterscale = scale < 1.0 ? 1.0 : scale;
   support = support * filterscale;
   const double ss = 1.0 / filterscale;
-  for (int xx = 0; xx < out_size; ++xx) {
+  for (int xx = first; xx < first + count; ++xx) {
     const double center = 0.0 + (xx + 0.5) * scale;
     double ww = 0.0;
     int xmin = (int)(center - support + 0.5);
@@ -333,7 +335,7 @@ static void precompute_coeffs(int32_t in_size, int32_t out_size, double (*fn)(do
     int xmax = (int)(center + support + 0.5);
     if (xmax > in_size) xmax = in_size;
     xmax -= xmin;
-    double* k = kk + (size_t)xx * ksize;
+    double* k = kk + (size_t)(xx - first) * ksize;
     for (int x = 0; x < xmax; ++x) {
       const double w = fn((x + xmin - center + 0.5) * ss);
       k[x] = w;
@@ -342,8 +344,8 @@ static void precompute_coeffs(int32_t in_size, int32_t out_size, double (*fn)(do
     for (int x = 0; x < xmax; ++x)
       if (ww != 0.0) k[x] /= ww;
     for (int x = xmax; x < ksize; ++x) k[x] = 0;
-    bounds[xx * 2 + 0] = xmin;
-    bounds[xx * 2 + 1] = xmax;
+    bounds[(xx - first) * 2 + 0] = xmin;
+    bounds[(xx - first) * 2 + 1] = xmax;
   }
 }
 
@@ -354,24 +356,45 @@ extern "C" int fp_resize_coeffs_f64(int32_t in_size, int32_t out_size, int32_t f
   FP_REQUIRE(bounds && kk && in_size > 0 && out_size > 0, "fp_resize_coeffs_f64: bad arguments");
   FP_REQUIRE(filter_of(filter, &fn, &support), "fp_resize_coeffs_f64: filter must be FP_RESIZE_LANCZOS, _BILINEAR, _BICUBIC or _BOX");
   FP_REQUIRE(ksize == fp_resize_ksize(in_size, out_size, filter), "fp_resize_coeffs_f64: ksize differs from fp_resize_ksize");
-  precompute_coeffs(in_size, out_size, fn, support, bounds, kk, ksize);
+  precompute_coeffs(in_size, out_size, fn, support, 0, out_size, bounds, kk, ksize);
   return 0;
 }
 
-// Resample.c precompute_coeffs + normalize_coeffs_8bpc
-extern "C" int fp_resize_coeffs(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* kk, int32_t ksize) {
+// Resample.c precompute_coeffs + normalize_coeffs_8bpc for the output indices first .. first + count - 1: work and memory of `count` rows
+extern "C" int fp_resize_coeffs_range(int32_t in_size, int32_t out_size, int32_t filter, int32_t first, int32_t count, int32_t* bounds, int32_t* kk,
+                                      int32_t ksize) {
   double (*fn)(double);
   double support;
   FP_REQUIRE(bounds && kk && in_size > 0 && out_size > 0, "fp_resize_coeffs: bad arguments");
   FP_REQUIRE(filter_of(filter, &fn, &support), "fp_resize_coeffs: filter must be FP_RESIZE_LANCZOS, _BILINEAR, _BICUBIC or _BOX");
   FP_REQUIRE(ksize == fp_resize_ksize(in_size, out_size, filter), "fp_resize_coeffs: ksize differs from fp_resize_ksize");
+  FP_REQUIRE(first >= 0 && count > 0 && count <= out_size - first, "fp_resize_coeffs_range: first .. first + count - 1 must lie inside the output");
   // Pillow keeps the double weights in the table and quantises afterwards
-  double* w = (double*)malloc(sizeof(double) * (size_t)out_size * (size_t)ksize);
+  double* w = (double*)malloc(sizeof(double) * (size_t)count * (size_t)ksize);
   FP_REQUIRE(w, "fp_resize_coeffs: out of memory");
-  precompute_coeffs(in_size, out_size, fn, support, bounds, w, ksize);
-  for (size_t i = 0, n = (size_t)out_size * (size_t)ksize; i < n; ++i)
+  precompute_coeffs(in_size, out_size, fn, support, first, count, bounds, w, ksize);
+  for (size_t i = 0, n = (size_t)count * (size_t)ksize; i < n; ++i)
     kk[i] = w[i] < 0 ? (int)(-0.5 + w[i] * (1 << PRECISION_BITS)) : (int)(0.5 + w[i] * (1 << PRECISION_BITS));
   free(w);
+  return 0;
+}
+
+extern "C" int fp_resize_coeffs(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* kk, int32_t ksize) {
+  FP_REQUIRE(out_size > 0, "fp_resize_coeffs: bad arguments");
+  return fp_resize_coeffs_range(in_size, out_size, filter, 0, out_size, bounds, kk, ksize);
+}
+
+// Pillow's NEAREST resize of one axis (libImaging Geometry.c, ImagingScaleAffine with the scale in / out and the offset of half a step): the
+// source coordinate is ACCUMULATED in double, one addition per output index, and truncated
+extern "C" int fp_nearest_index(int32_t in_size, int32_t out_size, int32_t* idx) {
+  FP_REQUIRE(idx && in_size > 0 && out_size > 0, "fp_nearest_index: bad arguments");
+  const double step = (double)in_size / out_size;
+  double o = step * 0.5;
+  for (int x = 0; x < out_size; ++x) {
+    const int i = (int)o;
+    idx[x] = i < in_size ? i : in_size - 1;
+    o += step;
+  }
   return 0;
 }
 

@@ -37,6 +37,20 @@ class AugParams(C.Structure):
                 ("pad", C.c_int32)]
 
 
+def draw_jitter(p, ranges=JITTER_RANGES, rng=random):
+    """torchvision 0.4.2's ColorJitter.get_params into `p`: four uniforms in the order brightness, contrast, saturation, hue over
+    `ranges`, then one shuffle of the order in which the four operations are applied"""
+    factors = [rng.uniform(lo, hi) for lo, hi in ranges]
+    order = [BRIGHTNESS, CONTRAST, SATURATION, HUE]
+    rng.shuffle(order)
+    p.n_ops = 4
+    for k in range(4):
+        p.ops[k] = order[k]
+        p.factor[k] = factors[k]
+    p.hue_shift = int(factors[HUE] * 255) & 0xFF                         # np.uint8(hue_factor * 255): truncation, wrap-around
+    return p
+
+
 def draw_augmentation(is_train=True, rng=random):
     """the reference's draws for one sample, in its order (kitti_dataset.py:55-56, then ColorJitter.get_params only when the colour
     augmentation fires) -> AugParams"""
@@ -44,18 +58,75 @@ def draw_augmentation(is_train=True, rng=random):
     p.flip = int(bool(is_train and rng.random() > 0.5))
     color_aug = bool(is_train and rng.random() > 0.5)
     if color_aug:
-        factors = [rng.uniform(lo, hi) for lo, hi in JITTER_RANGES]
-        order = [BRIGHTNESS, CONTRAST, SATURATION, HUE]
-        rng.shuffle(order)
-        p.n_ops = 4
-        for k in range(4):
-            p.ops[k] = order[k]
-            p.factor[k] = factors[k]
-        p.hue_shift = int(factors[HUE] * 255) & 0xFF                     # np.uint8(hue_factor * 255): truncation, wrap-around
+        draw_jitter(p, JITTER_RANGES, rng)
     return p
 
 
-class DeviceBatchAssembler:
+class SlotAssembler:
+    """What every batch assembler shares: a ring of slots (dicts of pinned and device buffers, made by the subclass), the copy / assembly
+    stream, and the events that order a slot's reuse -- `ready` (its copies and kernels are done) and `consumed` (the consumer has
+    finished reading its outputs).  A subclass fills a slot's pinned buffers in `fill` (after `_take_slot`), queues the copies and
+    kernels in `_launch(s)` and names the outputs in `_batch(s)`."""
+
+    def _init_slots(self, device, stream):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            # "cuda" means the CURRENT device at construction, pinned to an explicit index (ADVICE r4): under a launcher the current device
+            # changes when DistContext.from_env selects LOCAL_RANK, and a bare "cuda" stream / buffer created before that lives on GPU 0
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        # the copy / assembly stream.  A process owns four hardware queues and the engine uses all four (footprints_amd/engine.py): a
+        # stream of its own is a fifth one and shares a queue with whichever engine stream the runtime picks -- a 3.6 ms H2D copy then
+        # sits in front of that stream's kernels (637 vs 851 img/s on two boxes of the pool).  Pass the engine's decoder weight-gradient
+        # stream (`model.engine().dwg[0]`): the next batch is staged before the current step is launched, the copy is done long before
+        # that stream's first kernel of the step (6 ms in), and nothing on the critical path ever waits behind it.
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
+        self.slots = []
+        self._next = 0
+
+    def _add_slot(self, **buffers):
+        self.slots.append(dict(buffers, ready=torch.cuda.Event(), consumed=None, launched=False))
+        return self.slots[-1]
+
+    def _take_slot(self):
+        """the next slot of the ring, once its previous H2D copies have landed (its pinned buffers are free then) -> (index, slot)"""
+        i = self._next
+        self._next = (self._next + 1) % len(self.slots)
+        s = self.slots[i]
+        if s["launched"]:
+            s["ready"].synchronize()
+        return i, s
+
+    def launch(self, i):
+        """device half: H2D copies + assembly kernels of a filled slot on the copy stream, behind the consumer's last read of the slot's
+        device buffers (an event wait on the stream: the host does not block)."""
+        s = self.slots[i]
+        if s["consumed"] is not None:
+            self.stream.wait_event(s["consumed"])            # the consumer finished reading this slot's outputs
+        with ops.on_stream(self.stream):
+            self._launch(s)
+            s["ready"].record(self.stream)
+        s["launched"] = True
+        return i
+
+    def submit(self, samples, params):
+        """stage one batch (fill + launch); returns the slot index to pass to collect()"""
+        return self.launch(self.fill(samples, params))
+
+    def collect(self, slot):
+        """batch dict (reference schema) of the slot; the current stream waits for the slot's kernels.  The tensors are views of the
+        slot's buffers: they stay valid until the slot is submitted again (call `release(slot)` after the step that used them was
+        queued, or let DeviceLoader do it)."""
+        s = self.slots[slot]
+        torch.cuda.current_stream().wait_event(s["ready"])
+        return self._batch(s)
+
+    def release(self, slot):
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        self.slots[slot]["consumed"] = ev
+
+
+class DeviceBatchAssembler(SlotAssembler):
     """Pinned staging buffers (one set per slot), a copy stream, and the two assembly kernels.  Three slots by default: while the
     network works on batch i (slot a) and batch i + 1 sits assembled in slot b, the host can already fill slot c with batch i + 2 --
     with two slots the refill of a slot has to wait for the step that last read it, and the GPU idles for the host's memcpy.
@@ -95,38 +166,25 @@ class DeviceBatchAssembler:
         # left to numpy so that the scalar promotion rules of the installed numpy apply, as they do to the reference's own code
         self.fxb = float(np.float32(0.58 * width) * baseline) if dataset == "kitti" else 0.0
         self.depth_scaling = float(depth_scaling)
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            # "cuda" means the CURRENT device at construction, pinned to an explicit index: under a launcher the current device
-            # changes when DistContext.from_env selects LOCAL_RANK, and a bare "cuda" stream / buffer created before that lives on GPU 0
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        # the copy / assembly stream.  A process owns four hardware queues and the engine uses all four (footprints_amd/engine.py): a
-        # stream of its own is a fifth one and shares a queue with whichever engine stream the runtime picks -- a 3.6 ms H2D copy then
-        # sits in front of that stream's kernels (637 vs 851 img/s on two boxes of the pool).  Pass the engine's decoder weight-gradient
-        # stream (`model.engine().dwg[0]`): the next batch is staged before the current step is launched, the copy is done long before
-        # that stream's first kernel of the step (6 ms in), and nothing on the critical path ever waits behind it.
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
+        self._init_slots(device, stream)
         npx = batch_size * height * width
         tdt = torch.float64 if self.map_dtype == np.float64 else torch.float32
-        self.slots = []
         self.tables = ops.resize_table_set(self.device) if self.raw_images else None
         for _ in range(slots):
             h_img = torch.empty((batch_size, height, width, 3), dtype=torch.uint8).pin_memory()
             h_maps = torch.empty((len(self.keys), batch_size, height, width), dtype=tdt).pin_memory()
             h_par = torch.empty(batch_size * C.sizeof(AugParams), dtype=torch.uint8).pin_memory()
-            self.slots.append(dict(
+            self._add_slot(
                 h_img=h_img, h_maps=h_maps, h_par=h_par,
                 d_img=torch.empty_like(h_img, device=self.device), d_maps=torch.empty_like(h_maps, device=self.device),
                 d_par=torch.empty_like(h_par, device=self.device), sums=torch.zeros(batch_size, dtype=torch.int64, device=self.device),
                 image=torch.empty((batch_size, 3, height, width), device=self.device),
-                out=torch.empty((len(OUT_KEYS), batch_size, height, width), device=self.device),
-                ready=torch.cuda.Event(), consumed=None, launched=False))
+                out=torch.empty((len(OUT_KEYS), batch_size, height, width), device=self.device))
             if self.raw_images:             # the packed native-size frames and their fp_resize_sample records
                 h_src = torch.empty(batch_size * self.max_src_hw[0] * self.max_src_hw[1] * 3, dtype=torch.uint8).pin_memory()
                 h_rec = torch.empty(batch_size * C.sizeof(_lib.ResizeSample), dtype=torch.uint8).pin_memory()
                 self.slots[-1].update(h_src=h_src, h_rec=h_rec, d_src=torch.empty_like(h_src, device=self.device),
                                       d_rec=torch.empty_like(h_rec, device=self.device), src_bytes=0)
-        self._next = 0
         assert npx > 0
 
     def fill(self, samples, params):
@@ -135,11 +193,7 @@ class DeviceBatchAssembler:
         H2D copies.  Returns the slot index for launch()."""
         if len(samples) != self.B or len(params) != self.B:
             raise ValueError("expected %d samples" % self.B)
-        i = self._next
-        self._next = (self._next + 1) % len(self.slots)
-        s = self.slots[i]
-        if s["launched"]:
-            s["ready"].synchronize()                         # the pinned buffers are free once the slot's last copies have landed
+        i, s = self._take_slot()
         img_np, maps_np = s["h_img"].numpy(), s["h_maps"].numpy()
         if self.raw_images:
             images = [img for img, _ in samples]
@@ -155,59 +209,36 @@ class DeviceBatchAssembler:
         s["h_par"].numpy()[:] = np.frombuffer(bytes(arr), dtype=np.uint8)
         return i
 
-    def launch(self, i):
-        """device half: H2D copies + assembly kernels of a filled slot on the copy stream, behind the consumer's last read of the slot's
-        device buffers (an event wait on the stream: the host does not block)."""
-        s = self.slots[i]
-        if s["consumed"] is not None:
-            self.stream.wait_event(s["consumed"])            # the consumer finished reading this slot's outputs
-        with ops.on_stream(self.stream):
-            if self.raw_images:                 # Image.resize first, like the reference (footprint_dataset.py:77), straight into d_img
-                n = s["src_bytes"]
-                s["d_src"][:n].copy_(s["h_src"][:n], non_blocking=True)
-                s["d_rec"].copy_(s["h_rec"], non_blocking=True)
-                ops.resize_u8_packed(s["d_src"], n, s["d_rec"], self.B, self.H, self.W, 3, self.max_src_hw[0], self.max_src_hw[1], self.tables,
-                                     out=s["d_img"])
-            else:
-                s["d_img"].copy_(s["h_img"], non_blocking=True)
-            s["d_maps"].copy_(s["h_maps"], non_blocking=True)
-            s["d_par"].copy_(s["h_par"], non_blocking=True)
-            if self.filter_mask:                # filter_depth_mask in place, in front of the label algebra
-                ops.filter_depth_mask(s["d_maps"][2], out=s["d_maps"][2])
-            lib = _lib.load()
-            st = ops.stream()
-            _lib.check(lib.fp_assemble_images(s["d_img"].data_ptr(), s["d_par"].data_ptr(), s["sums"].data_ptr(), s["image"].data_ptr(),
-                                              self.B, self.H, self.W, st), "fp_assemble_images")
-            m, o = s["d_maps"], s["out"]
-            kitti = self.dataset == "kitti"
-            _lib.check(lib.fp_assemble_labels(m[0].data_ptr(), m[1].data_ptr(), m[2].data_ptr(), m[3].data_ptr(),
-                                              m[4].data_ptr() if kitti else None, int(self.map_dtype == np.float64), s["d_par"].data_ptr(),
-                                              o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(), o[5].data_ptr(),
-                                              self.B, self.H, self.W, 0 if kitti else 1, int(self.no_depth_mask), int(self.pdb),
-                                              int(self.use_moving), self.threshold, self.fxb, self.depth_scaling, st), "fp_assemble_labels")
-            s["ready"].record(self.stream)
-        s["launched"] = True
-        return i
+    def _launch(self, s):
+        if self.raw_images:                 # Image.resize first, like the reference (footprint_dataset.py:77), straight into d_img
+            n = s["src_bytes"]
+            s["d_src"][:n].copy_(s["h_src"][:n], non_blocking=True)
+            s["d_rec"].copy_(s["h_rec"], non_blocking=True)
+            ops.resize_u8_packed(s["d_src"], n, s["d_rec"], self.B, self.H, self.W, 3, self.max_src_hw[0], self.max_src_hw[1], self.tables,
+                                 out=s["d_img"])
+        else:
+            s["d_img"].copy_(s["h_img"], non_blocking=True)
+        s["d_maps"].copy_(s["h_maps"], non_blocking=True)
+        s["d_par"].copy_(s["h_par"], non_blocking=True)
+        if self.filter_mask:                # filter_depth_mask in place, in front of the label algebra
+            ops.filter_depth_mask(s["d_maps"][2], out=s["d_maps"][2])
+        lib = _lib.load()
+        st = ops.stream()
+        _lib.check(lib.fp_assemble_images(s["d_img"].data_ptr(), s["d_par"].data_ptr(), s["sums"].data_ptr(), s["image"].data_ptr(),
+                                          self.B, self.H, self.W, st), "fp_assemble_images")
+        m, o = s["d_maps"], s["out"]
+        kitti = self.dataset == "kitti"
+        _lib.check(lib.fp_assemble_labels(m[0].data_ptr(), m[1].data_ptr(), m[2].data_ptr(), m[3].data_ptr(),
+                                          m[4].data_ptr() if kitti else None, int(self.map_dtype == np.float64), s["d_par"].data_ptr(),
+                                          o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(), o[5].data_ptr(),
+                                          self.B, self.H, self.W, 0 if kitti else 1, int(self.no_depth_mask), int(self.pdb),
+                                          int(self.use_moving), self.threshold, self.fxb, self.depth_scaling, st), "fp_assemble_labels")
 
-    def submit(self, samples, params):
-        """stage one batch (fill + launch); returns the slot index to pass to collect()"""
-        return self.launch(self.fill(samples, params))
-
-    def collect(self, slot):
-        """batch dict (reference schema) of the slot; the current stream waits for the slot's kernels.  The tensors are views of the
-        slot's buffers: they stay valid until the slot is submitted again (call `release(slot)` after the step that used them was
-        queued, or let DeviceLoader do it)."""
-        s = self.slots[slot]
-        torch.cuda.current_stream().wait_event(s["ready"])
+    def _batch(self, s):
         batch = {"image": s["image"]}
         for k, key in enumerate(OUT_KEYS):
             batch[key] = s["out"][k]
         return batch
-
-    def release(self, slot):
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.slots[slot]["consumed"] = ev
 
 
 class DeviceLoader:
@@ -215,10 +246,12 @@ class DeviceLoader:
     assembled on the copy stream (the assembler's second slot).
 
     source: iterable yielding lists of `batch_size` samples (image uint8 [H,W,3], maps dict); rng: Python RNG for the reference's
-    augmentation draws (the module-level `random` by default, like the reference)."""
+    augmentation draws (the module-level `random` by default, like the reference); draw(samples, is_train, rng) -> the list of
+    per-sample parameters handed to the assembler's fill() (by default one `draw_augmentation` per sample, in batch order)."""
 
-    def __init__(self, source, assembler, is_train=True, rng=random):
+    def __init__(self, source, assembler, is_train=True, rng=random, draw=None):
         self.source, self.asm, self.is_train, self.rng = source, assembler, is_train, rng
+        self.draw = draw if draw is not None else (lambda samples, is_train, rng: [draw_augmentation(is_train, rng) for _ in samples])
 
     def __len__(self):
         return len(self.source)
@@ -228,7 +261,7 @@ class DeviceLoader:
         batches), the assembler and its slots stay this process's"""
         if not hasattr(self.source, "shard"):
             raise TypeError("DeviceLoader.shard: the sample source has no shard(rank, world)")
-        return DeviceLoader(self.source.shard(rank, world), self.asm, self.is_train, self.rng)
+        return DeviceLoader(self.source.shard(rank, world), self.asm, self.is_train, self.rng, self.draw)
 
     def __iter__(self):
         # one worker thread does the host half of staging (augmentation draws in batch order + the copies into pinned memory: numpy
@@ -241,7 +274,7 @@ class DeviceLoader:
                 samples = next(it)
             except StopIteration:
                 return None
-            return self.asm.fill(samples, [draw_augmentation(self.is_train, self.rng) for _ in samples])
+            return self.asm.fill(samples, self.draw(samples, self.is_train, self.rng))
 
         with ThreadPoolExecutor(1) as ex:
             pending = fill_next()
@@ -277,6 +310,221 @@ class SyntheticSampleSource:
                     "moving_objects": (rng.random((height, width)) < 0.05).astype(np.float64)}
             ih, iw = raw_hw[j % len(raw_hw)] if raw_hw else (height, width)
             self.pool.append((rng.integers(0, 256, (ih, iw, 3), dtype=np.uint8), maps))
+        self.dataset = range(steps * batch_size)
+
+    def __len__(self):
+        return len(range(self.first, self.steps, self.stride))
+
+    def shard(self, rank, world):
+        import copy
+        v = copy.copy(self)
+        v.steps = (self.steps // world) * world
+        v.first, v.stride = rank, world
+        return v
+
+    def __iter__(self):
+        for i in range(self.first, self.steps, self.stride):
+            yield [self.pool[(i * self.B + j) % len(self.pool)] for j in range(self.B)]
+
+
+class SegBatchAssembler(SlotAssembler):
+    """Batches of the ground-segmentation trainer, assembled on the device in the reference's schema {image, ground_mask, labelled_pix}
+    (footprints/preprocessing/segmentation/datasets/base_dataset.py:76-102) from decoded frames and label images at their native sizes.
+
+        asm = SegBatchAssembler(12, 192, 640, max_src_hw=(795, 2048))
+        plans = asm.draw(samples, is_train=True, rng=random)      # host: every size, crop offset and augmentation draw of the reference
+        batch = asm.collect(asm.submit(samples, plans))
+
+    samples: list of (dataset name, image uint8 [h, w, 3], labels uint8 [h, w] or [h, w, 3]); one batch may mix datasets.  The crop
+    window is known before any pixel is touched (preprocessing/segmentation/datasets/plan.py), so `fill` stages only the rectangle of
+    the frame that the window's resize taps reach and the rectangle of the label image that the composed NEAREST tables address;
+    `launch` copies them and runs one or two windowed resizes (csrc/seg_reader.hip; two when _preprocess AND prepare_size resize), the
+    flip + ColorJitter + ToTensor kernel of the Footprints trainer, and the label kernel.  max_src_hw = the staged rectangle of a sample
+    the pinned buffers are sized for at the start (batch_size of them; they grow when a batch needs more)."""
+
+    def __init__(self, batch_size, height, width, max_src_hw, slots=3, device="cuda", stream=None, check=False):
+        from ..preprocessing.segmentation.datasets import plan as P
+        self.P = P
+        lib = _lib.load()
+        assert lib.fp_aug_params_bytes() == C.sizeof(AugParams)
+        assert lib.fp_resize_window_sample_bytes() == C.sizeof(_lib.ResizeWindowSample)
+        assert lib.fp_resize_window_table_bytes() == C.sizeof(_lib.ResizeWindowTable)
+        assert lib.fp_seg_label_sample_bytes() == C.sizeof(_lib.SegLabelSample)
+        self.B, self.H, self.W = int(batch_size), int(height), int(width)
+        self.max_src_hw = (int(max_src_hw[0]), int(max_src_hw[1]))
+        self.check = bool(check)          # read the kernels' status words after every launch (this WAITS for the stream): tests, debugging
+        self._init_slots(device, stream)
+        B, H, W = self.B, self.H, self.W
+        self.out_bytes = B * H * W * 3
+        self.mid_bytes = B * (H + 32) * (W + 32) * 3          # the first resize's windows of two-stage samples: the second never shrinks
+        ids, offs = [], [0]
+        for name in P.DATASETS:
+            ids += sorted(P.GROUND_IDS[name])
+            offs.append(len(ids))
+        self.ground_ids = torch.tensor(ids, dtype=torch.int32, device=self.device)
+        self.set_offsets = torch.tensor(offs, dtype=torch.int32, device=self.device)
+        src_cap = B * self.max_src_hw[0] * self.max_src_hw[1] * 3
+        for _ in range(slots):
+            s = self._add_slot(
+                d_buf=torch.empty(self.out_bytes + self.mid_bytes, dtype=torch.uint8, device=self.device),
+                sums=torch.zeros(B, dtype=torch.int64, device=self.device), image=torch.empty((B, 3, H, W), device=self.device),
+                ground_mask=torch.empty((B, H, W), device=self.device), labelled_pix=torch.empty((B, H, W), device=self.device),
+                status=torch.zeros(1, dtype=torch.int32, device=self.device), used={}, calls=[])
+            self._pair(s, "src", src_cap, torch.uint8)
+            self._pair(s, "lab", src_cap, torch.uint8)
+            self._pair(s, "par", B * C.sizeof(AugParams), torch.uint8)
+            self._pair(s, "lrec", B * C.sizeof(_lib.SegLabelSample), torch.uint8)
+            self._pair(s, "lidx", B * (H + W), torch.int32)
+            for k in (0, 1):
+                self._pair(s, "rec%d" % k, B * C.sizeof(_lib.ResizeWindowSample), torch.uint8)
+                self._pair(s, "tab%d" % k, 2 * B * C.sizeof(_lib.ResizeWindowTable), torch.uint8)
+                self._pair(s, "coef%d" % k, B * (H + W + 64) * 24, torch.int32)
+
+    def _pair(self, s, name, n, dtype):
+        """a pinned host buffer and its device twin"""
+        s["h_" + name] = torch.empty(int(n), dtype=dtype).pin_memory()
+        s["d_" + name] = torch.empty(int(n), dtype=dtype, device=self.device)
+
+    def _reserve(self, s, name, n):
+        """the buffers grow when a batch needs more than they hold (a frame larger than max_src_hw; longer tap rows than the reference's
+        resize factors give)"""
+        if n > s["h_" + name].numel():
+            ops.release(s["d_" + name], "seg_assembler:" + name)
+            self._pair(s, name, n + n // 2, s["h_" + name].dtype)
+
+    def _put(self, s, name, arr):
+        """`arr` into the pinned buffer `name` from its start"""
+        n = arr.size
+        self._reserve(s, name, n)
+        s["h_" + name].numpy()[:n] = arr
+        s["used"][name] = n
+
+    def draw(self, samples, is_train=True, rng=random):
+        """the reference's draws for every sample of a batch, in batch order -> list of SegPlan (the `draw` of a DeviceLoader)"""
+        return [self.P.draw_seg_plan(name, img.shape[:2], (self.H, self.W), is_train, rng) for name, img, _ in samples]
+
+    def loader(self, source, is_train=True, rng=random):
+        return DeviceLoader(source, self, is_train, rng, draw=self.draw)
+
+    def fill(self, samples, plans):
+        """host half: the plans' tables, the staged rectangles and every record into the next slot's pinned buffers"""
+        if len(samples) != self.B or len(plans) != self.B:
+            raise ValueError("expected %d samples" % self.B)
+        P, H, W = self.P, self.H, self.W
+        i, s = self._take_slot()
+        nearest = {}
+
+        def nearest_index(a, b):
+            if (a, b) not in nearest:
+                nearest[(a, b)] = ops.nearest_index(a, b)
+            return nearest[(a, b)]
+
+        # ---- geometry first: what every sample needs staged, so that the pinned buffers can grow before anything is copied
+        geo = []
+        for b, ((name, img, labels), plan) in enumerate(zip(samples, plans)):
+            if plan.dataset != name or tuple(plan.src_hw) != img.shape[:2] or labels.shape[:2] != img.shape[:2] or tuple(plan.window[2:]) != (H, W):
+                raise ValueError("sample %d: the plan was drawn for another sample" % b)
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or labels.dtype != np.uint8:
+                raise ValueError("sample %d: the image must be uint8 [h, w, 3] and the labels uint8" % b)
+            ade = name == "ADE20K"
+            if ade and (labels.ndim != 3 or labels.shape[2] != 3):
+                raise ValueError("sample %d: ADE20K labels are the RGB segmentation image" % b)
+            stages, rect = P.image_stages(plan, ops.resize_window_axis)         # the rectangle of the frame the window's taps reach
+            rows, cols = P.label_tables(plan, nearest_index)                    # the rectangle the composed tables address
+            lrect = (int(rows.min()), int(rows.max()) + 1, int(cols.min()), int(cols.max()) + 1)
+            geo.append((stages, rect, rows, cols, lrect, 3 if ade else 1))
+        self._reserve(s, "src", sum(g[1][2] * g[1][3] * 3 for g in geo))
+        self._reserve(s, "lab", sum((g[4][1] - g[4][0]) * (g[4][3] - g[4][2]) * g[5] for g in geo))
+        src_np, lab_np = s["h_src"].numpy(), s["h_lab"].numpy()
+        calls = [ops.WindowBatch(3), ops.WindowBatch(3)]
+        lrec = (_lib.SegLabelSample * self.B)()
+        lidx = np.empty(self.B * (H + W), np.int32)
+        src_off = lab_off = 0
+        mid_off = self.out_bytes
+        for b, ((name, img, labels), (stages, (y0, x0, rh, rw), rows, cols, (r0, r1, c0, c1), lc)) in enumerate(zip(samples, geo)):
+            # ---- image: its staged rectangle and the records of its one or two resizes
+            n = rh * rw * 3
+            src_np[src_off:src_off + n].reshape(rh, rw, 3)[:] = img[y0:y0 + rh, x0:x0 + rw]
+            offset, rect = src_off, (y0, x0, rh, rw)
+            src_off += n
+            for k, st in enumerate(stages):
+                last = k == len(stages) - 1
+                out_offset = b * H * W * 3 if last else mid_off
+                call = calls[k]
+                call.add(offset, rect, call.table(st["in_hw"][1], st["out_hw"][1], st["table_h"]),
+                         call.table(st["in_hw"][0], st["out_hw"][0], st["table_v"]), st["window"], out_offset)
+                if not last:                    # the next resize reads this one's window as its staged rectangle
+                    offset, rect = mid_off, st["window"]
+                    mid_off += st["window"][2] * st["window"][3] * 3
+                    if mid_off > self.out_bytes + self.mid_bytes:
+                        raise ValueError("sample %d: the intermediate of its two resizes does not fit" % b)
+            # ---- labels: one channel, but ADE20K's R and G
+            lab = labels[r0:r1, c0:c1] if lc == 3 or labels.ndim == 2 else labels[r0:r1, c0:c1, 0]
+            lab_np[lab_off:lab_off + lab.size].reshape(lab.shape)[:] = lab
+            lidx[b * (H + W):b * (H + W) + H] = rows - r0
+            lidx[b * (H + W) + H:(b + 1) * (H + W)] = cols - c0
+            lrec[b] = _lib.SegLabelSample(lab_off, r1 - r0, c1 - c0, lc, b * (H + W), b * (H + W) + H,
+                                          _lib.SEG_DECODE_ADE20K if lc == 3 else _lib.SEG_DECODE_CHANNEL0,
+                                          _lib.SEG_LABELLED_NONZERO if name == "cityscapes" else _lib.SEG_LABELLED_ONES, P.DATASETS.index(name))
+            lab_off += lab.size
+        s["used"] = {"src": src_off, "lab": lab_off}
+        s["calls"] = []
+        for k, call in enumerate(calls):
+            if call.samples:
+                rec, tab, coef = call.arrays()
+                self._put(s, "rec%d" % k, rec)
+                self._put(s, "tab%d" % k, tab)
+                self._put(s, "coef%d" % k, coef)
+                s["calls"].append((k, len(call.samples), len(call.tables), coef.size, call.max_src_h, call.max_src_w, call.max_win_h, call.max_win_w))
+        self._put(s, "lrec", np.frombuffer(bytes(lrec), dtype=np.uint8))
+        self._put(s, "lidx", lidx)
+        self._put(s, "par", np.frombuffer(bytes((AugParams * self.B)(*[p.aug for p in plans])), dtype=np.uint8))
+        return i
+
+    def _launch(self, s, copies=True):
+        """copies=False: the kernels alone, on what an earlier launch of the slot uploaded (benchmarks)"""
+        for name, n in s["used"].items():
+            if n and copies:
+                s["d_" + name][:n].copy_(s["h_" + name][:n], non_blocking=True)
+        buf = s["d_buf"]
+        for k, n, n_tables, coeffs_len, msh, msw, mwh, mww in s["calls"]:
+            # the first call reads the staged rectangles; the second one reads the first one's windows inside `buf`
+            src, src_bytes = (s["d_src"], s["used"]["src"]) if k == 0 else (buf, buf.numel())
+            ops.resize_window_u8(src, src_bytes, s["d_rec%d" % k], n, s["d_tab%d" % k], n_tables, s["d_coef%d" % k], coeffs_len, buf, 3,
+                                 msh, msw, mwh, mww, check=self.check)
+        _lib.check(_lib.load().fp_assemble_images(buf.data_ptr(), s["d_par"].data_ptr(), s["sums"].data_ptr(), s["image"].data_ptr(),
+                                                  self.B, self.H, self.W, ops.stream()), "fp_assemble_images")
+        ops.seg_labels(s["d_lab"], s["used"]["lab"], s["d_lrec"], self.B, s["d_lidx"], s["used"]["lidx"], self.ground_ids, self.set_offsets,
+                       self.H, self.W, ground_mask=s["ground_mask"], labelled_pix=s["labelled_pix"], status=s["status"], check=self.check)
+
+    def _batch(self, s):
+        return {"image": s["image"], "ground_mask": s["ground_mask"], "labelled_pix": s["labelled_pix"]}
+
+
+class SyntheticSegSource:
+    """`steps` batches of host samples (dataset name, image uint8 [h, w, 3], labels uint8) with the shapes the segmentation file readers
+    deliver, for the benchmark and the tests: a small pool of random frames, cycled.  frames: list of (dataset name, (h, w)), taken in
+    turn.  Label images carry ids of the dataset's range, a fair share of them ground ids."""
+
+    def __init__(self, batch_size, steps, frames, seed=10, pool=None):
+        from ..preprocessing.segmentation.datasets.plan import GROUND_IDS
+        rng = np.random.default_rng(seed)
+        self.B, self.steps, self.first, self.stride = batch_size, steps, 0, 1
+        self.pool = []
+        for j in range(pool or max(len(frames), batch_size)):
+            name, (h, w) = frames[j % len(frames)]
+            image = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+            blocks = rng.integers(0, 4, ((h + 15) // 16, (w + 15) // 16))             # 16 x 16 patches: 0 unlabelled, 1-2 ground, 3 other
+            ground = np.asarray(GROUND_IDS[name])[rng.integers(0, len(GROUND_IDS[name]), blocks.shape)]
+            ids = np.where(blocks == 0, 0, np.where(blocks == 3, ground + 1, ground))
+            ids = np.kron(ids, np.ones((16, 16), np.int64))[:h, :w]
+            if name == "ADE20K":
+                labels = np.stack([ids // 256 * 10 + rng.integers(0, 10, ids.shape), ids % 256, rng.integers(0, 256, ids.shape)], -1).astype(np.uint8)
+            elif name == "cityscapes":
+                labels = np.repeat(ids[..., None], 3, -1).astype(np.uint8)
+            else:
+                labels = (ids == 1).astype(np.uint8)
+            self.pool.append((name, image, labels))
         self.dataset = range(steps * batch_size)
 
     def __len__(self):

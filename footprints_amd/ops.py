@@ -1214,6 +1214,141 @@ def load_images_u8(images, H, W, filter="lanczos", device="cuda"):
     return to_tensor_u8(resize_u8(images, H, W, filter, device))
 
 
+# ---- reader work of the segmentation trainer: windowed per-sample resize and the label path (csrc/seg_reader.hip) ---------------------------
+def resize_tables_range(in_size, out_size, first, count, filter="lanczos"):
+    """rows first .. first + count - 1 of `resize_tables(in_size, out_size, filter)`, built alone: the cost is that of `count` rows.  Not
+    cached -- the segmentation reader's target sizes are random per sample."""
+    import numpy as np
+    lib = _lib.load()
+    key = (int(in_size), int(out_size), _resize_filter(filter))
+    ksize = lib.fp_resize_ksize(*key)
+    if ksize < 0:
+        raise ValueError("footprints_amd.ops.resize_tables_range: bad sizes %r" % (key,))
+    bounds, kk = np.empty((count, 2), np.int32), np.empty((count, ksize), np.int32)
+    _lib.check(lib.fp_resize_coeffs_range(key[0], key[1], key[2], int(first), int(count), bounds.ctypes.data, kk.ctypes.data, ksize),
+               "fp_resize_coeffs_range")
+    return bounds, kk
+
+
+def nearest_index(in_size, out_size):
+    """source index of every output index of Pillow's NEAREST resize of one axis -> int32 [out_size]"""
+    import numpy as np
+    idx = np.empty(int(out_size), np.int32)
+    _lib.check(_lib.load().fp_nearest_index(int(in_size), int(out_size), idx.ctypes.data), "fp_nearest_index")
+    return idx
+
+
+def resize_window_axis(in_size, out_size, first, count, filter="lanczos", whole_table=False):
+    """one axis of a windowed resize on the host -> (table, lo, hi): table = None when the sizes agree (the pass is skipped), else
+    (first row described, bounds, kk) for the window's output indices (or for all of them with whole_table); [lo, hi) = the source
+    indices the window's taps reach"""
+    if first < 0 or count <= 0 or first + count > out_size:
+        raise ValueError("footprints_amd.ops.resize_window_axis: the window %d + %d leaves the target size %d" % (first, count, out_size))
+    if in_size == out_size:
+        return None, first, first + count
+    t0, n = (0, out_size) if whole_table else (first, count)
+    bounds, kk = resize_tables_range(in_size, out_size, t0, n, filter)
+    w = bounds[first - t0:first - t0 + count]
+    return (t0, bounds, kk), int(w[:, 0].min()), int((w[:, 0] + w[:, 1]).max())
+
+
+class WindowBatch:
+    """host half of one fp_resize_window_u8 call: the sample records, table records and coefficient rows, collected sample by sample"""
+
+    def __init__(self, channels=3):
+        self.C = int(channels)
+        self.samples, self.tables, self.coeffs, self.length = [], [], [], 0
+        self.max_src_h = self.max_src_w = self.max_win_h = self.max_win_w = 1
+
+    def table(self, in_size, out_size, t):
+        """index of the table `t` of resize_window_axis in this call's table list; -1 for None"""
+        if t is None:
+            return -1
+        first, bounds, kk = t
+        self.tables.append(_lib.ResizeWindowTable(in_size, out_size, kk.shape[1], first, bounds.shape[0], self.length, self.length + bounds.size))
+        self.coeffs += [bounds.reshape(-1), kk.reshape(-1)]
+        self.length += bounds.size + kk.size
+        return len(self.tables) - 1
+
+    def add(self, src_offset, rect, table_h, table_v, window, out_offset):
+        """rect = (y0, x0, h, w) of the staged source rectangle in its image, window = (top, left, h, w) of the target"""
+        y0, x0, h, w = (int(v) for v in rect)
+        top, left, wh, ww = (int(v) for v in window)
+        self.samples.append(_lib.ResizeWindowSample(int(src_offset), int(out_offset), h, w, y0, x0, table_h, table_v, top, left, wh, ww))
+        self.max_src_h, self.max_src_w = max(self.max_src_h, h), max(self.max_src_w, w)
+        self.max_win_h, self.max_win_w = max(self.max_win_h, wh), max(self.max_win_w, ww)
+
+    def arrays(self):
+        """(sample records uint8, table records uint8, coefficients int32) as numpy arrays"""
+        import numpy as np
+        rec = np.frombuffer(b"".join(bytes(r) for r in self.samples), dtype=np.uint8)
+        tab = np.frombuffer(b"".join(bytes(r) for r in self.tables), dtype=np.uint8)
+        return rec, tab, (np.concatenate(self.coeffs) if self.coeffs else np.zeros(0, np.int32))
+
+
+def resize_window_u8(src, src_bytes, samples, B, tables, n_tables, coeffs, coeffs_len, out, Cn, max_src_h, max_src_w, max_win_h, max_win_w,
+                     check=False):
+    """device half of a windowed resize (fp_resize_window_u8) on the current launch stream: src / out uint8 device buffers, samples B
+    fp_resize_window_sample records, tables n_tables fp_resize_window_table records over the int32 buffer `coeffs` -- all on the device.
+    Per sample the bytes of Image.resize(its target size).crop(its window) land at its out_offset.  check=True reads the status word
+    afterwards (this WAITS for the stream) and raises ValueError when a record was turned down."""
+    lib = _lib.load()
+    if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.numel() < src_bytes:
+        raise RuntimeError("footprints_amd.ops.resize_window_u8: src and out must be uint8 and src hold src_bytes bytes")
+    if samples.numel() * samples.element_size() < B * C.sizeof(_lib.ResizeWindowSample):
+        raise RuntimeError("footprints_amd.ops.resize_window_u8: fewer than B sample records")
+    if n_tables and (tables.numel() * tables.element_size() < n_tables * C.sizeof(_lib.ResizeWindowTable) or coeffs.dtype != torch.int32
+                     or coeffs.numel() < coeffs_len):
+        raise RuntimeError("footprints_amd.ops.resize_window_u8: fewer than n_tables table records, or coeffs is not int32 of coeffs_len")
+    need = lib.fp_resize_window_workspace(B, max_src_h, max_win_w, Cn)
+    if need < 0:
+        raise RuntimeError("footprints_amd.ops.resize_window_u8: bad sizes")
+    ws = workspace(need, src.device, "resize_window")
+    _lib.check(lib.fp_resize_window_u8(_chk(src, "src"), int(src_bytes), _chk(samples, "samples"), _chk(tables, "tables") if n_tables else None,
+                                       n_tables, _chk(coeffs, "coeffs") if n_tables else None, int(coeffs_len) if n_tables else 0, _chk(out, "out"),
+                                       out.numel(), B, Cn, max_src_h, max_src_w, max_win_h, max_win_w, ws.data_ptr(), ws.numel(), stream()),
+               "fp_resize_window_u8")
+    if check:
+        off = lib.fp_resize_window_status_offset(B, max_src_h, max_win_w, Cn)
+        if int(ws[off:off + 4].view(torch.int32).item()) != 0:
+            raise ValueError("footprints_amd.ops.resize_window_u8: a sample or table record was turned down on the device; its output is unwritten")
+    return out
+
+
+def resize_window_status(device, B, max_src_h, max_win_w, Cn):
+    """the status word the last resize_window_u8 call of these sizes on the current stream left (WAITS for the stream)"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    off = _lib.load().fp_resize_window_status_offset(B, max_src_h, max_win_w, Cn)
+    ws = workspace(off + 16, device, "resize_window")
+    return int(ws[off:off + 4].view(torch.int32).item())
+
+
+def seg_labels(src, src_bytes, samples, B, index, index_len, ground_ids, set_offsets, H, W, ground_mask=None, labelled_pix=None, status=None,
+               check=False):
+    """fp_seg_labels on the current launch stream: src uint8 device buffer with the staged label rectangles, samples B fp_seg_label_sample
+    records, index the int32 row / column tables, ground_ids / set_offsets the int32 ground-id sets -- all on the device
+    -> (ground_mask, labelled_pix) float32 [B, H, W]"""
+    dev = src.device
+    if src.dtype != torch.uint8 or index.dtype != torch.int32 or ground_ids.dtype != torch.int32 or set_offsets.dtype != torch.int32:
+        raise RuntimeError("footprints_amd.ops.seg_labels: src must be uint8; index, ground_ids and set_offsets int32")
+    if samples.numel() * samples.element_size() < B * C.sizeof(_lib.SegLabelSample) or src.numel() < src_bytes or index.numel() < index_len:
+        raise RuntimeError("footprints_amd.ops.seg_labels: fewer than B sample records, src_bytes source bytes or index_len table entries")
+    ground_mask = torch.empty((B, H, W), dtype=torch.float32, device=dev) if ground_mask is None else ground_mask
+    labelled_pix = torch.empty((B, H, W), dtype=torch.float32, device=dev) if labelled_pix is None else labelled_pix
+    status = torch.empty(1, dtype=torch.int32, device=dev) if status is None else status
+    if ground_mask.numel() != B * H * W or labelled_pix.numel() != B * H * W or status.dtype != torch.int32:
+        raise RuntimeError("footprints_amd.ops.seg_labels: outputs must be float32 [B, H, W] and status one int32")
+    _lib.check(_lib.load().fp_seg_labels(_chk(src, "src"), int(src_bytes), _chk(samples, "samples"), _chk(index, "index"), int(index_len),
+                                         _chk(ground_ids, "ground_ids"), ground_ids.numel(), _chk(set_offsets, "set_offsets"),
+                                         set_offsets.numel() - 1, _f32(ground_mask, "ground_mask"), _f32(labelled_pix, "labelled_pix"),
+                                         _chk(status, "status"), B, H, W, stream()), "fp_seg_labels")
+    if check and int(status.item()) != 0:
+        raise ValueError("footprints_amd.ops.seg_labels: a sample record or a table entry was turned down on the device")
+    return ground_mask, labelled_pix
+
+
 # ---- visualisations on the device: predict_simple's overlay and the test-set side-by-side picture (csrc/visualise.hip) -----------------------
 _vis_host_tables = {}
 

@@ -1,0 +1,117 @@
+"""Trainer of the ground-segmentation network on device-assembled batches (reference: footprints/preprocessing/segmentation/train.py).
+
+Per step: forward, the four bilinear up-sizes + per-sample masked BCE / 4 (one kernel, losses.py), backward, Adam at `lr`.  StepLR(10) is
+stepped at the START of every epoch, as the reference does.  Every `log_freq` steps the tracked losses are printed (there is no
+tensorboardX here) after `val_batches` validation batches from a cycling iterator.  `epoch_{n}.pth` holds the model's state_dict alone.
+Single process: data parallelism is not part of this trainer."""
+import os
+import random
+
+import torch
+
+from ...optim import FusedAdam
+from .evaluation import Evaluator
+from .network import Segmentor
+
+
+class Trainer:
+    def __init__(self, options, model=None, train_loader=None, val_loader=None):
+        """model / train_loader / val_loader: injected objects (tests, benchmarks); by default the Segmentor of the options and
+        DeviceLoaders over the file readers named in the config file"""
+        print("setting up...")
+        self.opt = options
+        if not torch.cuda.is_available():
+            raise RuntimeError("the segmentation trainer has no CPU compute path: it needs a MI355X")
+        if model is None:
+            model = Segmentor(pretrained=True, use_PSP=not self.opt.no_PSP)
+            if self.opt.load_path is not None:
+                print("loading weights from {}...".format(self.opt.load_path))
+                model.load_state_dict(torch.load(self.opt.load_path, map_location="cpu"))
+            model.cuda()
+        self.model = model
+        self.evaluator = Evaluator()
+        self.optimiser = FusedAdam(self.model, lr=self.opt.lr)
+        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimiser, step_size=10)
+        print("models done!")
+        if train_loader is None or val_loader is None:
+            made = self.create_dataloaders()
+            train_loader, val_loader = train_loader or made[0], val_loader or made[1]
+        self.train_loader, self.val_loader = train_loader, val_loader
+        self.val_iter = iter(self.val_loader)
+        print("datasets done!")
+        print("training images: {}".format(len(self.train_loader.dataset)))
+        print("validation images: {}".format(len(self.val_loader.dataset)))
+        self.step, self.epoch, self.lr = 0, 0, self.opt.lr
+        self.history = []                    # one entry per logged step: dict(epoch, step, lr, batch_loss, train, val)
+
+    def create_dataloaders(self):
+        """train.py:64-101 with the file readers of datasets/ and the device path: ConcatDataset of the chosen datasets, shuffled, so
+        one batch mixes datasets.  max_src_hw is Cityscapes' cropped frame, the largest of the three."""
+        import yaml
+        from ...datasets.device_path import SegBatchAssembler
+        from .datasets import READERS, BatchSource
+        with open(self.opt.config_path) as fh:
+            config = yaml.safe_load(fh)
+        loaders = []
+        for split, is_train in (("train", True), ("val", False)):
+            readers = []
+            for dataset in self.opt.training_datasets:
+                with open(os.path.join("splits", dataset, split + ".txt")) as fh:
+                    files = fh.read().splitlines()
+                if dataset == "matterport" and is_train:
+                    files = files[:5000]
+                readers.append(READERS[dataset](config[dataset]["dataset"], files))
+            source = BatchSource(readers, self.opt.batch_size, shuffle=True)
+            asm = SegBatchAssembler(self.opt.batch_size, self.opt.height, self.opt.width, max_src_hw=(1280, 2048))
+            loader = asm.loader(source, is_train, random)
+            loader.dataset = source.dataset
+            loaders.append(loader)
+        return loaders
+
+    def train(self):
+        print("training")
+        self.step = 0
+        for self.epoch in range(self.opt.epochs):
+            self.run_epoch()
+
+    def run_epoch(self):
+        self.scheduler.step()                # at the start of the epoch (train.py:111)
+        for inputs in self.train_loader:
+            self.model.train()
+            _, batch_loss = self.forward(inputs)
+            self.model.zero_grad()
+            batch_loss.backward()
+            self.optimiser.step()
+            self.lr = self.scheduler.get_last_lr()[0]
+            if (self.step % self.opt.log_freq) == 0:
+                tracked = self.evaluator.get_tracked_losses()
+                val = self.run_validation(self.opt.val_batches)
+                self.history.append(dict(epoch=self.epoch, step=self.step, lr=self.lr, batch_loss=float(batch_loss.detach()),
+                                         train={k: float(v) for k, v in tracked.items()}, val={k: float(v) for k, v in val.items()}))
+                print("Epoch {} -- Step {} -- lr {} -- Train Loss {} -- Val Loss {}".format(self.epoch, self.step, self.lr,
+                                                                                           self.history[-1]["train"]["loss"],
+                                                                                           self.history[-1]["val"]["loss"]))
+            self.step += 1
+        self.save_model()
+
+    def run_validation(self, batches=10):
+        """`batches` batches from the cycling validation iterator, in the reference's mode: the model stays as the training loop left it
+        (train.py:148-170 never calls eval()), without gradients"""
+        with torch.no_grad():
+            for _ in range(batches):
+                try:
+                    inputs = next(self.val_iter)
+                except StopIteration:
+                    self.val_iter = iter(self.val_loader)
+                    inputs = next(self.val_iter)
+                self.forward(inputs)
+            return self.evaluator.get_tracked_losses()
+
+    def forward(self, inputs):
+        outputs = self.model(inputs["image"])
+        return outputs, self.evaluator.compute_losses(outputs, inputs["ground_mask"], inputs["labelled_pix"])
+
+    def save_model(self):
+        save_path = os.path.join(self.opt.log_path, self.opt.model_name, "models")
+        os.makedirs(save_path, exist_ok=True)
+        torch.save(self.model.state_dict(), os.path.join(save_path, "epoch_{}.pth".format(self.epoch)))

@@ -534,6 +534,73 @@ int64_t fp_filter_depth_mask_workspace(int32_t B, int32_t H, int32_t W);
 int fp_filter_depth_mask(const void* mask, int32_t is_double, void* out, int32_t B, int32_t H, int32_t W, void* workspace,
                          int64_t workspace_bytes, fp_stream_t stream);
 
+/* ---- device-side reader work of the segmentation trainer (footprints/preprocessing/segmentation/datasets; csrc/seg_reader.hip) ---- */
+/* HOST function (no GPU needed): rows first .. first + count - 1 of fp_resize_coeffs' tables (bounds int32 [count][2], kk int32
+ * [count][ksize]).  Pillow computes every output index on its own, so the rows are identical; work and memory are those of `count` rows. */
+int fp_resize_coeffs_range(int32_t in_size, int32_t out_size, int32_t filter, int32_t first, int32_t count, int32_t* bounds, int32_t* kk,
+                           int32_t ksize);
+/* HOST function: the source index of every output index of Pillow's NEAREST resize of one axis (idx int32 [out_size]); the source
+ * coordinate starts at in / out / 2 and is accumulated in double, one addition of in / out per index, as libImaging does. */
+int fp_nearest_index(int32_t in_size, int32_t out_size, int32_t* idx);
+/* one axis table of the windowed resize: like fp_resize_table, but its rows describe the output indices first .. first + count - 1 only
+ * (first = 0, count = out_size: a whole table).  fp_resize_window_table_bytes() == sizeof(fp_resize_window_table) */
+typedef struct fp_resize_window_table {
+  int32_t in_size, out_size, ksize;
+  int32_t first, count;
+  int32_t bounds_off; /* element offsets into the coefficient buffer */
+  int32_t kk_off;
+} fp_resize_window_table;
+/* one sample of the windowed resize; fp_resize_window_sample_bytes() == sizeof(fp_resize_window_sample) */
+typedef struct fp_resize_window_sample {
+  int64_t src_offset; /* of the staged source rectangle's first byte in `src`; dense uint8 [src_h][src_w][C] */
+  int64_t out_offset; /* of the window's first byte in `out`; dense uint8 [win_h][win_w][C] */
+  int32_t src_h, src_w;
+  int32_t src_y0, src_x0; /* where the rectangle sits in the full source image: a table's source indices minus the origin address it */
+  int32_t table_h, table_v; /* index of the sample's (source width -> target width) / (height -> height) table; -1 = equal sizes, pass skipped */
+  int32_t top, left, win_h, win_w; /* the window of the target image that is produced */
+} fp_resize_window_sample;
+int32_t fp_resize_window_table_bytes(void);
+int32_t fp_resize_window_sample_bytes(void);
+/* bytes of the workspace: the uint8 intermediate (B * max_src_h * max_win_w * C) and, at fp_resize_window_status_offset, one int32 status
+ * word (-1 on bad arguments) */
+int64_t fp_resize_window_workspace(int32_t B, int32_t max_src_h, int32_t max_win_w, int32_t C);
+int64_t fp_resize_window_status_offset(int32_t B, int32_t max_src_h, int32_t max_win_w, int32_t C);
+/* Per sample, the bytes of PIL.Image.resize((tw, th), filter).crop((left, top, left + win_w, top + win_h)), where (tw, th) is the sample's
+ * OWN target size (the out_size of its tables): Pillow's 8-bit arithmetic as in fp_resize_u8, but the horizontal pass runs only over the
+ * source rows the window's vertical taps reach and over the window's columns, and the vertical pass produces only the window.  With both
+ * tables -1 the window is copied.  `src` (device, 4-byte aligned, src_bytes long) holds each sample's staged rectangle -- at least the rows
+ * and columns the window's taps reach, at most the whole image (origin 0, 0); it may be the `out` of an earlier call, which chains two
+ * resizes.  Tables may describe the window's output indices only (fp_resize_coeffs_range); their bounds must not decrease along a table, as
+ * Pillow's never do.  A record whose window leaves its target, whose rectangle does not cover the taps, that exceeds the stated maxima or
+ * points outside a buffer leaves its output unwritten and sets the workspace's status word to 1 (every call clears it first; read it after
+ * the stream has finished); the other samples are not affected.  max_src_w * C <= 65528 (the staged part of a row lives in LDS). */
+int fp_resize_window_u8(const uint8_t* src, int64_t src_bytes, const void* samples, const void* tables, int32_t n_tables, const int32_t* coeffs,
+                        int64_t coeffs_len, uint8_t* out, int64_t out_bytes, int32_t B, int32_t C, int32_t max_src_h, int32_t max_src_w,
+                        int32_t max_win_h, int32_t max_win_w, void* workspace, int64_t workspace_bytes, fp_stream_t stream);
+#define FP_SEG_DECODE_CHANNEL0 0 /* label id = channel 0 (Cityscapes, Matterport) */
+#define FP_SEG_DECODE_ADE20K 1   /* label id = R / 10 * 256 + G in integers (ade20k_dataset.py:51), 0 .. 6655 */
+#define FP_SEG_LABELLED_ONES 0    /* labelled_pix = 1 everywhere (ADE20K, Matterport) */
+#define FP_SEG_LABELLED_NONZERO 1 /* labelled_pix = id != 0 (cityscapes_dataset.py:69) */
+/* one label image of the batch; fp_seg_label_sample_bytes() == sizeof(fp_seg_label_sample) */
+typedef struct fp_seg_label_sample {
+  int64_t src_offset; /* of the staged label rectangle in `src`; dense uint8 [h][w][C] */
+  int32_t h, w, C;    /* C = 1 or 3 */
+  int32_t rows_off;   /* into `index`: [H] source row of every output row, relative to the rectangle */
+  int32_t cols_off;   /* into `index`: [W] source column of every output column */
+  int32_t decode;     /* FP_SEG_DECODE_* */
+  int32_t labelled;   /* FP_SEG_LABELLED_* */
+  int32_t ground_set; /* index of its ground-id set */
+} fp_seg_label_sample;
+int32_t fp_seg_label_sample_bytes(void);
+/* The label half of a segmentation batch (_process_labels of the three datasets): the NEAREST resizes, crops and the flip of a label
+ * image are index maps, composed by the host into one row and one column table per sample.  ground_mask[b][y][x] = id is in the sample's
+ * ground-id set (np.in1d), labelled_pix per the sample's mode; float32 [B][H][W] each.  ground_ids: the sets one after the other
+ * (ground_len int32), set s = ground_ids[set_offsets[s] .. set_offsets[s + 1]); one batch may mix datasets.  status: one int32 on the device,
+ * cleared by the call and set to 1 when a record or a table entry points outside a buffer (those outputs stay unwritten). */
+int fp_seg_labels(const uint8_t* src, int64_t src_bytes, const void* samples, const int32_t* index, int64_t index_len, const int32_t* ground_ids,
+                  int64_t ground_len, const int32_t* set_offsets, int32_t n_sets, float* ground_mask, float* labelled_pix, int32_t* status,
+                  int32_t B, int32_t H, int32_t W, fp_stream_t stream);
+
 /* ---- device-side visualisations (footprints/predict_simple.py:75-92, footprints/evaluation/inference.py:114-118; csrc/visualise.hip) ---- */
 /* HOST function (no GPU needed): the tables of fp_resize_coeffs before the quantisation -- kk double [out][ksize] = the taps normalised in
  * double, as Pillow's mode-"F" passes use them; bounds as there.  Both functions share the double stage. */
