@@ -126,6 +126,7 @@ SIGNATURES = {
     "fp_vis_overlay_status_offset": (_I64, [_I32, _I32, _I32, _I32, _I32]),
     "fp_vis_overlay": (C.c_int, [_P, _P, _I64, _P, _P, _I32, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "fp_vis_side_by_side": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.c_uint32, C.c_uint32, _P]),
+    "fp_seg_pack": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "fp_adaptive_avgpool_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "fp_adaptive_avgpool_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, C.c_int, _P]),
     "fp_bilinear_ac_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),

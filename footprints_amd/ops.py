@@ -1506,3 +1506,45 @@ def vis_side_by_side(image, pred, out=None):
     _lib.check(_lib.load().fp_vis_side_by_side(_f32(image, "image"), _f32(pred, "pred"), _chk(out, "out"), B, H, W, colour(lut[0]), colour(lut[255]),
                                                stream()), "fp_vis_side_by_side")
     return out
+
+
+# ---- output stage of the ground-segmentation network's inference mode (csrc/seg_infer.hip) ---------------------------------------------------
+def seg_pack(logits, image=None, want_f32=False, want_picture=False, out=None):
+    """sigmoid + float16 rounding (+ the reference's test picture) of full-resolution logits in one launch: logits float32 [B, 1, H, W],
+    dense or a `[:, 0:1]` view of the engine's [B, 2, H, W] head buffer (its batch stride is passed through, nothing is copied; any other
+    non-contiguity raises); image float32 [B, 3, H, W] in [0, 1], needed for the picture.  out = (half, f32, picture): buffers to write
+    into, each None or a contiguous tensor of the right shape and type.
+    -> (float16 [B, 1, H, W], float32 [B, 1, H, W] or None, uint8 [B, H, 2 W, 3] or None): the .npy contents of the reference's
+    save_result, the sigmoid before the rounding, matplotlib's imsave of [image | plasma(prediction)] byte for byte"""
+    if logits.dim() != 4 or logits.shape[1] != 1 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise RuntimeError("footprints_amd.ops.seg_pack: logits must be a float32 CUDA tensor [B, 1, H, W]")
+    B, _, H, W = logits.shape
+    if min(B, H, W) < 1:
+        raise RuntimeError("footprints_amd.ops.seg_pack: empty logits")
+    sb, _, sh, sw = logits.stride()
+    if B == 1:
+        sb = H * W
+    if (W > 1 and sw != 1) or (H > 1 and sh != W) or sb < H * W:
+        raise RuntimeError("footprints_amd.ops.seg_pack: logits must be dense planes at a batch stride >= H * W "
+                           "(a [:, 0:1] view of a contiguous [B, C, H, W] buffer), got strides %r" % (tuple(logits.stride()),))
+    half, f32, picture = out if out is not None else (None, None, None)
+    dev = logits.device
+    if half is None:
+        half = torch.empty((B, 1, H, W), dtype=torch.float16, device=dev)
+    if want_f32 and f32 is None:
+        f32 = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    if want_picture and picture is None:
+        picture = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8, device=dev)
+    if not want_f32:
+        f32 = None
+    if not want_picture:
+        picture = None
+    if half.dtype != torch.float16 or half.numel() != B * H * W or (f32 is not None and (f32.dtype != torch.float32 or f32.numel() != B * H * W)) \
+            or (picture is not None and (picture.dtype != torch.uint8 or picture.numel() != B * H * W * 6)):
+        raise RuntimeError("footprints_amd.ops.seg_pack: out buffers must be float16 / float32 [B, 1, H, W] and uint8 [B, H, 2 W, 3]")
+    if want_picture and (image is None or tuple(image.shape) != (B, 3, H, W)):
+        raise RuntimeError("footprints_amd.ops.seg_pack: the picture needs image float32 [B, 3, H, W]")
+    _lib.check(_lib.load().fp_seg_pack(logits.data_ptr(), int(sb), _f32(image, "image") if want_picture else None, _chk(half, "half"),
+                                       _f32(f32, "f32") if f32 is not None else None, _chk(picture, "picture") if picture is not None else None,
+                                       _chk(_vis_lut(dev)) if want_picture else None, B, H, W, stream()), "fp_seg_pack")
+    return half, f32, picture

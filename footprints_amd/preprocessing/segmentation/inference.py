@@ -1,7 +1,17 @@
-"""Ground-segmentation inference -- counterpart of footprints/preprocessing/segmentation/inference.py:60-84 (`test_batch`): the full
-resolution logit map through a sigmoid, as a numpy array [B,1,H,W].  Dataset readers / file writers stay the reference's."""
+"""Ground-segmentation inference -- counterpart of footprints/preprocessing/segmentation/inference.py.  `InferenceManager.test_batch` is
+the bare step (:60-84): an already resized tensor through the network, the full resolution logit map through a sigmoid, as a float32
+numpy array [B,1,H,W].  `Tester` is the reference's program around it (`--mode inference`): the datasets of datasets/inference.py, the
+resize, the network's full-resolution head alone and the output stage (csrc/seg_infer.hip) on the device, file writing on a thread."""
+import collections
+import ctypes as C
+import os
+import queue
+import threading
+import time
+
 import torch
 
+from ... import _lib, ops
 from .network import Segmentor
 
 
@@ -16,3 +26,236 @@ class InferenceManager:
         with torch.no_grad():
             preds = self.model(inputs["image"].cuda(non_blocking=True))
             return torch.sigmoid(preds[3][:, 0:1]).cpu().numpy()                          # "just take max resolution prediction"
+
+
+class Tester:
+    """The reference's `Tester` (segmentation/inference.py:20-91): the trained Segmentor over every frame of the train and val splits, one
+    float16 ground-probability map per frame under `<training_data>/<test_save_folder>/...` -- the files ground_truth_generation reads.
+
+    The reference is a loop of blocking steps (DataLoader workers that decode AND resize on the host, forward, float32 copy to the host,
+    cast, np.save, plt.imsave).  Here `test()` is a pipeline of three stages that overlap:
+      readers  `num_workers` THREADS (default 4, at most 16; Pillow releases the GIL while it decodes) read ahead, in order;
+      device   the calling thread packs a batch's frames -- uint8 at their native, mixed sizes -- into a slot's pinned buffer and queues
+               upload, Resize((H, W), ANTIALIAS) + ToTensor (ops.resize_u8_packed + ops.to_tensor_u8, bit-equal), the network in eval mode
+               with `inference_scales = ("1/1",)`, ops.seg_pack (sigmoid, float16, the picture) and the copies into the slot's pinned
+               result buffers; it does not wait for any of it, so batch k + 1 is queued while batch k's results come back;
+      writer   ONE thread waits for a slot's `ready` event, writes its files (np.save; Pillow encodes the device-drawn picture) and hands
+               the slot back.  A slot is not refilled before that.
+    An exception in a reader or in the writer ends `test()` with that exception; every wait on a queue, a future or a slot has a timeout
+    after which the waiting thread looks at the error flag.  `has_gt`, tensorboard and data parallelism are not part of this mode."""
+
+    POLL = 0.05          # seconds between two looks at the error flag while a thread waits
+    SPIN = 0.0002        # seconds between two queries of a slot's `ready` event (a batch takes milliseconds)
+
+    def __init__(self, options, model=None, dataset=None, save_path=None, slots=3):
+        """model / dataset / save_path: injected (tests, benchmarks); then neither the config file nor the split files are read"""
+        print("setting up...")
+        self.opt = options
+        self.height, self.width = int(options.height), int(options.width)
+        self.batch_size = int(options.batch_size)
+        self.num_workers = min(max(int(getattr(options, "num_workers", 4) or 1), 1), 16)
+        self.visualise = bool(options.save_test_visualisations)
+        if dataset is None or save_path is None:
+            import yaml
+            with open(self.opt.config_path) as fh:
+                path_data = yaml.safe_load(fh)[self.opt.test_data_type]
+            if save_path is None:
+                save_path = os.path.join(path_data["training_data"], self.opt.test_save_folder)
+        self.save_path = save_path
+        if model is None:
+            model = Segmentor(pretrained=False, use_PSP=not self.opt.no_PSP)
+            print("loading weights from {}...".format(self.opt.load_path))
+            model.load_state_dict(torch.load(self.opt.load_path, map_location="cpu"))
+            print("successfully loaded weights!")
+            model.cuda()
+        self.model = model
+        self.model.eval()
+        if dataset is None:
+            from .datasets.inference import INFERENCE_DATASETS
+            filenames = []
+            for textfile in ("train.txt", "val.txt"):               # train and val files, concatenated and sorted (inference.py:41-47)
+                with open(os.path.join("splits", self.opt.test_data_type, textfile)) as fh:
+                    filenames += fh.read().splitlines()
+            dataset = INFERENCE_DATASETS[self.opt.test_data_type](path_data["dataset"], sorted(filenames), self.height, self.width)
+        self.dataset = dataset
+        self.n_slots = max(int(slots), 1)
+        self.slots = None
+        self._error = None
+        self._stop = threading.Event()
+
+    # ---- device half ------------------------------------------------------------------------------------------------------------------
+    def _make_slots(self):
+        """the ring: per slot the pinned staging buffer of the packed frames and their records, the device twins, the device outputs and
+        the pinned buffers the results come back through"""
+        if not torch.cuda.is_available():
+            raise RuntimeError("the segmentation inference mode has no CPU compute path: it needs a MI355X")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.tables = ops.resize_table_set(self.device)
+        B, H, W = self.batch_size, self.height, self.width
+        rec_bytes = B * C.sizeof(_lib.ResizeSample)
+        slots = []
+        for _ in range(self.n_slots):
+            s = dict(ready=torch.cuda.Event(), src_cap=0, h_src=None, d_src=None,
+                     h_rec=torch.empty(rec_bytes, dtype=torch.uint8).pin_memory(), d_rec=torch.empty(rec_bytes, dtype=torch.uint8, device=self.device),
+                     d_u8=torch.empty((B, H, W, 3), dtype=torch.uint8, device=self.device),
+                     d_half=torch.empty((B, 1, H, W), dtype=torch.float16, device=self.device),
+                     h_half=torch.empty((B, 1, H, W), dtype=torch.float16).pin_memory(), d_pic=None, h_pic=None)
+            if self.visualise:
+                s["d_pic"] = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8, device=self.device)
+                s["h_pic"] = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8).pin_memory()
+            slots.append(s)
+        return slots
+
+    def _reserve_src(self, s, nbytes):
+        """the staging buffers of the packed frames grow when a batch needs more than they hold"""
+        if nbytes > s["src_cap"]:
+            ops.release(s["d_src"], "seg_tester:src")
+            s["src_cap"] = nbytes + nbytes // 8
+            s["h_src"] = torch.empty(s["src_cap"], dtype=torch.uint8).pin_memory()
+            s["d_src"] = torch.empty(s["src_cap"], dtype=torch.uint8, device=self.device)
+
+    def _device_half(self, s, frames):
+        """queue one batch on the current stream -- upload, resize, ToTensor, network, seg_pack, copies back into the slot's pinned
+        buffers -- and record the slot's `ready` event; nothing here waits for the device"""
+        n = len(frames)
+        if not 1 <= n <= self.batch_size:
+            raise ValueError("a batch holds 1 to %d frames" % self.batch_size)
+        if any(f.ndim != 3 or f.shape[2] != 3 for f in frames):
+            raise ValueError("frames must be decoded RGB images, uint8 [h, w, 3]")
+        H, W = self.height, self.width
+        self._reserve_src(s, sum(f.shape[0] * f.shape[1] * 3 for f in frames))
+        _, _, total, _, max_h, max_w = ops.resize_pack(frames, H, W, self.tables, packed=s["h_src"].numpy(), records=s["h_rec"].numpy())
+        self.model.eval()
+        with torch.no_grad():
+            s["d_src"][:total].copy_(s["h_src"][:total], non_blocking=True)
+            s["d_rec"].copy_(s["h_rec"], non_blocking=True)
+            u8 = ops.resize_u8_packed(s["d_src"], total, s["d_rec"], n, H, W, 3, max_h, max_w, self.tables, out=s["d_u8"][:n])
+            image = ops.to_tensor_u8(u8)
+            scales = getattr(self.model, "inference_scales", None)            # the model may be the caller's: its setting comes back
+            self.model.inference_scales = ("1/1",)          # "just take max resolution prediction" (inference.py:79)
+            try:
+                logits = self.model(image)[3]
+            finally:
+                self.model.inference_scales = scales
+            pic = s["d_pic"][:n] if self.visualise else None
+            ops.seg_pack(logits, image if self.visualise else None, want_picture=self.visualise, out=(s["d_half"][:n], None, pic))
+            s["h_half"][:n].copy_(s["d_half"][:n], non_blocking=True)
+            if self.visualise:
+                s["h_pic"][:n].copy_(s["d_pic"][:n], non_blocking=True)
+            s["ready"].record()
+
+    def _wait_slot(self, s, n):
+        """wait for the slot's results -> (float16 numpy [n, 1, H, W], uint8 numpy [n, H, 2 W, 3] or None): views of the pinned buffers"""
+        while not s["ready"].query():                       # a wait with a timeout, like every other one: look at the stop flag in between
+            if self._stop.is_set():
+                raise RuntimeError("the inference pipeline was stopped while a batch was in flight")
+            time.sleep(self.SPIN)
+        return s["h_half"].numpy()[:n], (s["h_pic"].numpy()[:n] if self.visualise else None)
+
+    def test_batch(self, frames):
+        """frames: list of decoded RGB frames, uint8 [h, w, 3] of any (mixed) sizes -> (float16 numpy [B, 1, H, W], uint8 numpy
+        [B, H, 2 W, 3] pictures or None without --save_test_visualisations); blocking, on the first slot"""
+        if self.slots is None:
+            self.slots = self._make_slots()
+        s = self.slots[0]
+        self._stop.clear()
+        self._device_half(s, frames)
+        half, pics = self._wait_slot(s, len(frames))
+        return half.copy(), (pics.copy() if pics is not None else None)
+
+    # ---- the pipeline -----------------------------------------------------------------------------------------------------------------
+    def _fail(self, exc):
+        if self._error is None:
+            self._error = exc
+        self._stop.set()
+
+    def _check(self):
+        if self._error is not None:
+            raise self._error
+
+    def _read(self, index):
+        if self._stop.is_set():
+            return None
+        return self.dataset[index]
+
+    def _writer(self, jobs, free):
+        try:
+            while True:
+                try:
+                    job = jobs.get(timeout=self.POLL)
+                except queue.Empty:
+                    if self._stop.is_set():
+                        return
+                    continue
+                if job is None:
+                    return
+                si, indices = job
+                half, pics = self._wait_slot(self.slots[si], len(indices))
+                for i, idx in enumerate(indices):
+                    self.dataset.save_result(idx, half[i], self.save_path, pics[i] if pics is not None else None)
+                free[si].set()                              # only now may the slot's pinned buffers be refilled
+        except BaseException as exc:                        # noqa: handed to the thread that called test()
+            self._fail(exc)
+
+    def _wait(self, done):
+        """poll `done()` (True when what is waited for has happened), looking at the error flag in between"""
+        while not done(self.POLL):
+            self._check()
+
+    def test(self):
+        """Run every frame of the dataset through the network and write its result"""
+        print("running inference...")
+        from concurrent.futures import ThreadPoolExecutor, TimeoutError as FutureTimeout
+        if self.slots is None:
+            self.slots = self._make_slots()
+        self._error = None
+        self._stop.clear()
+        N, B = len(self.dataset), self.batch_size
+        jobs = queue.Queue()
+        free = [threading.Event() for _ in self.slots]
+        for ev in free:
+            ev.set()
+        writer = threading.Thread(target=self._writer, args=(jobs, free), name="seg-infer-writer", daemon=True)
+        readers = ThreadPoolExecutor(self.num_workers, thread_name_prefix="seg-infer-reader")
+        pending = collections.deque()
+        ahead = B * (len(self.slots) + 1)                   # frames decoded ahead of the batch being queued
+        submitted = 0
+
+        def result_of(fut):
+            def done(timeout):
+                try:
+                    fut.result(timeout=timeout)
+                    return True
+                except FutureTimeout:
+                    return False
+            self._wait(done)
+            return fut.result()
+
+        writer.start()
+        try:
+            n_batches = (N + B - 1) // B
+            for k in range(n_batches):
+                indices = list(range(k * B, min((k + 1) * B, N)))               # the last batch may be short
+                while submitted < min(N, k * B + ahead):
+                    pending.append(readers.submit(self._read, submitted))
+                    submitted += 1
+                samples = [result_of(pending.popleft()) for _ in indices]
+                si = k % len(self.slots)
+                self._wait(free[si].wait)                   # the writer is done with this slot's previous batch
+                free[si].clear()
+                self._device_half(self.slots[si], [smp["image"] for smp in samples])
+                jobs.put((si, [smp["idx"] for smp in samples]))
+            jobs.put(None)
+            self._wait(lambda timeout: (writer.join(timeout), not writer.is_alive())[1])
+            self._check()
+        except BaseException as exc:
+            self._fail(exc)
+            raise
+        finally:
+            self._stop.set()
+            for fut in pending:
+                fut.cancel()
+            readers.shutdown(wait=True)
+            while writer.is_alive():
+                writer.join(self.POLL)
+        print("finished testing!")

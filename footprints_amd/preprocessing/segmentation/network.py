@@ -6,7 +6,8 @@ the Cin -> 2 head kernels with a zero second filter.
 
 The module tree only owns parameters under the reference's state_dict keys (`encoder.layerK...`, `decoder.blockK...`,
 `decoder.outconvK.conv1`, `decoder.outconv4.{0,1}...`, `decoder.PSP.blockK.reduce.weight`); `forward` returns the reference's
-list of four logit maps [B,1,H/8,W/8], [B,1,H/4,W/4], [B,1,H/2,W/2], [B,1,H,W] (network.py:84-99), autograd-capable.  The
+list of four logit maps [B,1,H/8,W/8], [B,1,H/4,W/4], [B,1,H/2,W/2], [B,1,H,W] (network.py:84-99), autograd-capable; with
+`inference_scales` set, a no-grad call evaluates only the named heads and leaves None at the other positions.  The
 bilinear up-sizing of the predictions and the masked BCE of the segmentation trainer (segmentation/train.py:184-193,
 evaluation.py:39-58) stay plain torch ops on those tensors: they are a few elementwise kernels on 1-channel maps, not a hot spot.
 No CPU compute path: a non-CUDA input raises.
@@ -15,6 +16,9 @@ import torch
 import torch.nn as nn
 
 from ...network import ConvBlock, ConvUpsampleAndConcatBlock, ResnetEncoder, _NoForward, is_dead_param
+
+
+SCALE_KEYS = ("1/8", "1/4", "1/2", "1/1")          # the positions of forward's list
 
 
 class OutConvBlock(_NoForward):
@@ -73,6 +77,7 @@ class Segmentor(nn.Module):
         self.encoder = ResnetEncoder(pretrained=pretrained)
         self.decoder = SkipDecoder(use_PSP=use_PSP)
         self._engine = None
+        self.inference_scales = None          # None = all four heads; a tuple of SCALE_KEYS = only those (no-grad calls only)
 
     def engine(self):
         from ...engine import Engine
@@ -89,9 +94,15 @@ class Segmentor(nn.Module):
             raise RuntimeError("footprints_amd Segmentor has no CPU compute path: move the model and the input to a MI355X (`.cuda()`)")
         eng = self.engine()
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        # inference_scales (e.g. ("1/1",)): evaluate only those heads, as FootprintNetwork does -- the inference mode consumes preds[3] alone
+        want = self.inference_scales
+        idx = None if want is None else sorted(SCALE_KEYS.index(k) for k in want)
+        if need_grad and idx is not None:
+            raise ValueError("Segmentor.inference_scales is an inference-only option: call under torch.no_grad(), or set it back to None")
         if need_grad:
             from ...engine import NetFunction
             outs = NetFunction.apply(eng, input_image, *eng.live_params)
         else:
-            outs = eng.forward(input_image, training=self.training, save_for_backward=False)
-        return [o[:, 0:1] for o in outs]          # channel 1 of every buffer is the padding filter's zero output
+            outs = eng.forward(input_image, training=self.training, save_for_backward=False, scales=idx)
+        # channel 1 of every buffer is the padding filter's zero output; a skipped head leaves None at its position
+        return [o[:, 0:1] if idx is None or i in idx else None for i, o in enumerate(outs)]

@@ -629,6 +629,18 @@ int fp_vis_overlay(const float* pred, const uint8_t* src, int64_t bytes, const v
 int fp_vis_side_by_side(const float* image, const float* pred, uint8_t* out, int32_t B, int32_t H, int32_t W, uint32_t colour0,
                         uint32_t colour1, fp_stream_t stream);
 
+/* ---- output stage of the ground-segmentation network's inference mode (footprints/preprocessing/segmentation/inference.py:80-90,
+ * datasets/inference_dataset.py:39-50; csrc/seg_infer.hip) ---- */
+/* One launch over the full-resolution logit planes: sample b's plane is the H * W floats at logits + b * logit_batch_stride (any stride >=
+ * H * W: channel 0 of the engine's [B][2][H][W] head buffer is stride 2 * H * W).  prob_half: float16 [B][1][H][W] = __float2half_rn(p)
+ * with p = 1 / (1 + expf(-x)) (accurate exponential, correctly rounded division; float16 subnormals kept) -- the .npy file's contents.
+ * prob_f32 (NULL ok): float [B][1][H][W] = p.  picture (NULL ok; needs image and lut): uint8 [B][H][2W][3], left half
+ * (uint8)((double)image * 255.0) of image float [B][3][H][W] (values outside [0, 1] clamped), right half lut[min((int)(p * 256.0f), 255)]
+ * with lut uint8 [256][3] -- matplotlib's imsave of the reference's visualisation, byte for byte.  Any H, W, B >= 1; operands that are
+ * not aligned for wide accesses (W % 4 != 0, an odd stride, an offset base pointer) take a scalar path. */
+int fp_seg_pack(const float* logits, int64_t logit_batch_stride, const float* image, void* prob_half, float* prob_f32, uint8_t* picture,
+                const uint8_t* lut, int32_t B, int32_t H, int32_t W, fp_stream_t stream);
+
 /* ---- pyramid pooling of the ground-segmentation network (footprints/preprocessing/segmentation/network.py:174-207) ---- */
 /* nn.AdaptiveAvgPool2d(P) (network.py:180,188): y[N][P][P][C] = window means of x[N][H][W][C]; windows floor(i*H/P) .. ceil((i+1)*H/P) */
 int fp_adaptive_avgpool_fwd(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t P, fp_stream_t stream);
