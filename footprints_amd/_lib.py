@@ -64,6 +64,14 @@ class ResizeSample(C.Structure):
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("table_h", C.c_int32), ("table_v", C.c_int32)]
 
 
+JPEG_TABLE_WORDS = 672            # fp_jpeg_table_words()
+
+
+class JpegSample(C.Structure):
+    """fp_jpeg_sample (include/footprints_hip.h)"""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
+
+
 _P, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _DESC = C.POINTER(ConvDesc)
 
@@ -127,6 +135,11 @@ SIGNATURES = {
     "fp_vis_overlay": (C.c_int, [_P, _P, _I64, _P, _P, _I32, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "fp_vis_side_by_side": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.c_uint32, C.c_uint32, _P]),
     "fp_seg_pack": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
+    "fp_jpeg_sample_bytes": (_I32, []),
+    "fp_jpeg_table_words": (_I32, []),
+    "fp_jpeg_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "fp_jpeg_max_scan_bytes": (_I64, [_I32, _I32, _I32]),
+    "fp_jpeg_encode": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _P, _I64, _P]),
     "fp_adaptive_avgpool_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "fp_adaptive_avgpool_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, C.c_int, _P]),
     "fp_bilinear_ac_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),

@@ -11,7 +11,8 @@ File decoding (KITTI, Matterport, handheld readers) stays on the host; the reade
 With `save_test_visualisations=True` (the reference's --save_test_visualisations, inference.py:110-119) `run` also writes <stem>.jpg: the
 network's input beside the hidden-ground mask in the first and last colour of matplotlib's plasma map, drawn by one kernel
 (`fp_vis_side_by_side`) from the logits -- `logit > 0` where the reference tests `sigmoid > 0.5`, the same except for positive logits
-below fp32's resolution at 0.5.  The picture is encoded by Pillow on the host (the reference calls plt.imsave).
+below fp32's resolution at 0.5.  The picture is encoded by Pillow on the host (the reference calls plt.imsave), or with `device_jpeg=True`
+on the device (csrc/jpeg.hip): the same files byte for byte, and the raw picture never crosses to the host.
 """
 import os
 
@@ -24,7 +25,7 @@ from ..model_manager import ModelManager
 
 class InferenceManager:
     def __init__(self, load_path=None, model_manager=None, save_path=None, device_resize=False, height_width=None,
-                 save_test_visualisations=False):
+                 save_test_visualisations=False, device_jpeg=False):
         if device_resize and height_width is None:
             raise ValueError("device_resize=True needs height_width=(H, W), the network's input size")
         self.device_resize, self.height_width = bool(device_resize), height_width
@@ -38,12 +39,13 @@ class InferenceManager:
         self.model.inference_scales = ("1/1",)          # "just take max resolution prediction" (inference.py:104)
         self.savepath = save_path
         self.save_test_visualisations = bool(save_test_visualisations)
+        self.device_jpeg = bool(device_jpeg)
 
     @classmethod
     def from_options(cls, opt, model_manager=None, **kwargs):
         """the manager the command line describes: --load_path, --inference_save_path, --save_test_visualisations (options.py)"""
         return cls(load_path=opt.load_path, model_manager=model_manager, save_path=opt.inference_save_path,
-                   save_test_visualisations=opt.save_test_visualisations, **kwargs)
+                   save_test_visualisations=opt.save_test_visualisations, device_jpeg=getattr(opt, "device_jpeg", False), **kwargs)
 
     def input_tensor(self, inputs):
         """the network's input [B,3,H,W] on the device"""
@@ -60,7 +62,11 @@ class InferenceManager:
         image = self.input_tensor(inputs)
         with torch.no_grad():
             pred = self.model(image)["1/1"]
-            vis = self.visualise_batch(image, pred) if visualise else None
+            vis = None
+            if visualise and self.device_jpeg:         # the .jpg files' bytes: the picture is drawn and encoded on the device
+                vis = ops.jpeg_encode(ops.vis_side_by_side(image.contiguous(), pred.contiguous()), quality=95)
+            elif visualise:
+                vis = self.visualise_batch(image, pred)
             return ops.pack_pred_fp16(pred).cpu().numpy(), vis
 
     def visualise_batch(self, image, pred):
@@ -82,6 +88,9 @@ class InferenceManager:
                 preds, vis = self._test_batch(inputs, True)
             for i, pred in enumerate(preds):
                 self.save_result(inputs["idx"][i], pred)
-                if vis is not None:
+                if vis is not None and self.device_jpeg:
+                    with open(os.path.join(self.savepath, "{}.jpg".format(inputs["idx"][i])), "wb") as fh:
+                        fh.write(vis[i])
+                elif vis is not None:
                     from PIL import Image
                     Image.fromarray(vis[i]).save(os.path.join(self.savepath, "{}.jpg".format(inputs["idx"][i])), quality=95)

@@ -1469,6 +1469,22 @@ def vis_overlay(pred, originals=None, packed=None, shapes=None):
     pred float32 device [B, 4, H, W]; the photos either as `originals` (list of numpy uint8 [h, w, 3] of any sizes, uploaded here) or, when
     they are on the device already (the buffer resize_pack filled, uploaded for the device resize), as `packed` + `shapes` = their
     (h, w) in the buffer's order -> list of B numpy uint8 [h, w, 3]"""
+    out, total, shapes = vis_overlay_device(pred, originals, packed, shapes)
+    return split_pictures(out[:total].cpu().numpy(), shapes)
+
+
+def split_pictures(host, shapes):
+    """views [h, w, 3] of pictures lying one after the other in a packed uint8 numpy buffer"""
+    views, off = [], 0
+    for h, w in shapes:
+        views.append(host[off:off + h * w * 3].reshape(h, w, 3))
+        off += h * w * 3
+    return views
+
+
+def vis_overlay_device(pred, originals=None, packed=None, shapes=None):
+    """vis_overlay without the copy to the host -> (uint8 device buffer, its bytes in use, the (h, w) of the overlays lying in it one
+    after the other): what jpeg_encode_packed takes with jpeg_records of the same shapes"""
     import numpy as np
     B, H, W = pred.shape[0], pred.shape[2], pred.shape[3]
     if (originals is None) == (packed is None) or (packed is not None and shapes is None):
@@ -1484,13 +1500,7 @@ def vis_overlay(pred, originals=None, packed=None, shapes=None):
     records, total, max_h, max_w = vis_records(shapes, H, W, tables)
     if originals is not None:
         packed = torch.from_numpy(np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in originals])).to(pred.device)
-    out = vis_overlay_packed(pred, packed, total, torch.from_numpy(records).to(pred.device), max_h, max_w, tables)
-    host = out[:total].cpu().numpy()
-    views, off = [], 0
-    for h, w in shapes:
-        views.append(host[off:off + h * w * 3].reshape(h, w, 3))
-        off += h * w * 3
-    return views
+    return vis_overlay_packed(pred, packed, total, torch.from_numpy(records).to(pred.device), max_h, max_w, tables), total, shapes
 
 
 def vis_side_by_side(image, pred, out=None):
@@ -1548,3 +1558,173 @@ def seg_pack(logits, image=None, want_f32=False, want_picture=False, out=None):
                                        _f32(f32, "f32") if f32 is not None else None, _chk(picture, "picture") if picture is not None else None,
                                        _chk(_vis_lut(dev)) if want_picture else None, B, H, W, stream()), "fp_seg_pack")
     return half, f32, picture
+
+
+# ---- baseline JPEG encoder (csrc/jpeg.hip) -------------------------------------------------------------------------------------------------
+class JpegTables:
+    """what a file of the installed Pillow at one quality is made of, parsed from the bytes up to and including the SOS segment:
+    header (those bytes), size_at (index of SOF0's two big-endian height bytes, the width's follow), quant {table id: 64 values in zigzag
+    order}, huff {class << 4 | id: {symbol: (code, length)}}, words (uint32 numpy: the code table of fp_jpeg_encode)"""
+
+    def __init__(self, data):
+        import numpy as np
+        self.quant, self.huff, self.size_at = {}, {}, None
+        if data[:2] != b"\xff\xd8":
+            raise ValueError("not a JPEG file")
+        i = 2
+        while True:
+            if data[i] != 0xFF:
+                raise ValueError("JPEG header: marker expected at byte %d" % i)
+            marker, length = data[i + 1], (data[i + 2] << 8) | data[i + 3]
+            body = data[i + 4:i + 2 + length]
+            if marker == 0xDB:                                      # DQT: 8-bit tables, zigzag order
+                for p in range(0, len(body), 65):
+                    if body[p] >> 4:
+                        raise ValueError("JPEG header: 16-bit quantisation table")
+                    self.quant[body[p] & 15] = np.frombuffer(body[p + 1:p + 65], dtype=np.uint8).astype(np.int64)
+            elif marker == 0xC4:                                    # DHT: canonical codes from the 16 counts and the values
+                p = 0
+                while p < len(body):
+                    counts = body[p + 1:p + 17]
+                    values = body[p + 17:p + 17 + sum(counts)]
+                    code, k, table = 0, 0, {}
+                    for length_bits in range(1, 17):
+                        for _ in range(counts[length_bits - 1]):
+                            table[values[k]] = (code, length_bits)
+                            code += 1
+                            k += 1
+                        code <<= 1
+                    self.huff[body[p]] = table
+                    p += 17 + len(values)
+            elif marker == 0xC0:                                    # SOF0: precision, height, width, components
+                if body[0] != 8 or body[5] != 3 or bytes(body[6:15]) != b"\x01\x22\x00\x02\x11\x01\x03\x11\x01":
+                    raise ValueError("JPEG header: not 8-bit YCbCr 4:2:0 with tables 0, 1, 1")
+                self.size_at = i + 5
+            elif marker in (0xC1, 0xC2, 0xC9, 0xCA, 0xDD):
+                raise ValueError("JPEG header: not a baseline file without restart markers")
+            elif marker == 0xDA:
+                self.header = bytes(data[:i + 2 + length])
+                break
+            i += 2 + length
+        if self.size_at is None or sorted(self.quant) != [0, 1] or sorted(self.huff) != [0x00, 0x01, 0x10, 0x11]:
+            raise ValueError("JPEG header: two quantisation and four Huffman tables expected")
+        words = np.zeros(_lib.JPEG_TABLE_WORDS, dtype=np.uint32)
+        for t in (0, 1):
+            words[64 * t:64 * t + 64] = self.quant[t]
+            for sym, (code, n) in self.huff[t].items():
+                words[128 + 16 * t + sym] = code | n << 16
+            for sym, (code, n) in self.huff[0x10 | t].items():
+                words[160 + 256 * t + sym] = code | n << 16
+        self.words = words
+        self._device = {}
+
+    def file_header(self, h, w):
+        """the header of an h x w picture: the parsed bytes with SOF0's size patched"""
+        at = self.size_at
+        return self.header[:at] + bytes((h >> 8, h & 255, w >> 8, w & 255)) + self.header[at + 4:]
+
+    def device_words(self, device):
+        t = self._device.get(device)
+        if t is None:
+            t = self._device[device] = torch.from_numpy(self.words.view("int32").copy()).to(device)
+        return t
+
+
+_jpeg_tables = {}
+
+
+def jpeg_tables(quality=95):
+    """JpegTables of the installed Pillow at `quality`: a small RGB dummy is encoded once per quality and its header parsed; nothing of a
+    JPEG header is compiled into this package"""
+    t = _jpeg_tables.get(int(quality))
+    if t is None:
+        import io
+        import numpy as np
+        from PIL import Image
+        buf = io.BytesIO()
+        Image.fromarray(np.zeros((16, 16, 3), dtype=np.uint8)).save(buf, format="JPEG", quality=int(quality))
+        t = _jpeg_tables[int(quality)] = JpegTables(buf.getvalue())
+    return t
+
+
+def jpeg_records(shapes):
+    """fp_jpeg_sample records of pictures of `shapes` = [(h, w), ...] lying one after the other in a packed buffer
+    -> (records uint8 numpy, bytes of the packed buffer, max_h, max_w)"""
+    import numpy as np
+    rec = (_lib.JpegSample * len(shapes))()
+    off = 0
+    for b, (h, w) in enumerate(shapes):
+        rec[b] = _lib.JpegSample(off, h, w)
+        off += h * w * 3
+    return np.frombuffer(bytes(rec), dtype=np.uint8).copy(), off, max(s[0] for s in shapes), max(s[1] for s in shapes)
+
+
+def jpeg_max_scan_bytes(B, max_h, max_w):
+    """the largest output jpeg_encode_packed can need for B pictures of at most max_h x max_w"""
+    n = _lib.load().fp_jpeg_max_scan_bytes(B, max_h, max_w)
+    if n < 0:
+        raise RuntimeError("footprints_amd.ops.jpeg_max_scan_bytes: bad sizes, or too large")
+    return n
+
+
+def jpeg_encode_packed(src, src_bytes, samples, B, quality=95, out=None, max_h=None, max_w=None, table=None):
+    """device half of the encoder: `src` the packed pictures (uint8 device buffer, src_bytes used), `samples` B fp_jpeg_sample records on
+    the device (jpeg_records), max_h / max_w the largest height and width among them (required: the records are not read here)
+    -> (out, table): `out` uint8 device buffer holding the entropy-coded scans back to back (default: one of the worst-case size; a given
+    one may be smaller), `table` int64 device [B + 1, 2]: offset and length of each scan, last row = bytes written, status (1: a record
+    was turned down or a scan did not fit; that sample has length 0 and nothing of it was written).  Does not wait for the device."""
+    lib = _lib.load()
+    if max_h is None or max_w is None:
+        raise ValueError("footprints_amd.ops.jpeg_encode_packed: max_h and max_w are required")
+    need = lib.fp_jpeg_workspace_bytes(B, max_h, max_w)
+    if need < 0:
+        raise RuntimeError("footprints_amd.ops.jpeg_encode_packed: bad sizes, or too large")
+    if src.dtype != torch.uint8 or src.numel() < src_bytes:
+        raise RuntimeError("footprints_amd.ops.jpeg_encode_packed: src must be a uint8 buffer of at least src_bytes bytes")
+    if samples.numel() * samples.element_size() < B * C.sizeof(_lib.JpegSample):
+        raise RuntimeError("footprints_amd.ops.jpeg_encode_packed: fewer than B sample records")
+    if out is None:
+        out = torch.empty(jpeg_max_scan_bytes(B, max_h, max_w), dtype=torch.uint8, device=src.device)
+    if table is None:
+        table = torch.empty((B + 1, 2), dtype=torch.int64, device=src.device)
+    if out.dtype != torch.uint8 or table.dtype != torch.int64 or table.numel() < 2 * (B + 1):
+        raise RuntimeError("footprints_amd.ops.jpeg_encode_packed: out must be uint8 and table int64 [B + 1, 2]")
+    ws = workspace(need, src.device, "jpeg")
+    words = jpeg_tables(quality).device_words(src.device)
+    _lib.check(lib.fp_jpeg_encode(_chk(src, "src"), int(src_bytes), _chk(samples, "samples"), _chk(words), _chk(out, "out"), out.numel(),
+                                  _chk(table, "table"), B, max_h, max_w, ws.data_ptr(), ws.numel(), stream()), "fp_jpeg_encode")
+    return out, table
+
+
+def jpeg_files(scans, table, shapes, quality=95):
+    """complete files from the encoder's output on the HOST: scans (bytes-like, at least the bytes the table's last row counts), table
+    (int64 [B + 1, 2] numpy), shapes [(h, w), ...] -> list of bytes: header + scan + EOI"""
+    if int(table[len(shapes)][1]) != 0:
+        raise ValueError("footprints_amd.ops.jpeg_encode: a sample record was turned down on the device, or the output buffer was too small")
+    t = jpeg_tables(quality)
+    view = memoryview(scans)
+    return [t.file_header(h, w) + bytes(view[int(table[b][0]):int(table[b][0]) + int(table[b][1])]) + b"\xff\xd9" for b, (h, w) in enumerate(shapes)]
+
+
+def jpeg_encode(pictures, quality=95):
+    """Pillow's `Image.fromarray(p).save(f, format="JPEG", quality=quality)` for a batch, byte for byte (Pillow on libjpeg-turbo), encoded
+    on the device: pictures = a uint8 device tensor [B, H, W, 3], or a list of numpy uint8 [h, w, 3] of any sizes (uploaded here)
+    -> list of B bytes objects, each a complete file.  Copies the length table, waits, copies exactly the bytes used."""
+    import numpy as np
+    if torch.is_tensor(pictures):
+        if pictures.dim() != 4 or pictures.shape[3] != 3 or pictures.dtype != torch.uint8 or not pictures.is_cuda:
+            raise ValueError("footprints_amd.ops.jpeg_encode: a tensor of pictures must be uint8 [B, H, W, 3] on the device")
+        shapes = [(int(pictures.shape[1]), int(pictures.shape[2]))] * int(pictures.shape[0])
+        packed = pictures.contiguous().view(-1)
+    else:
+        if any(p.dtype != np.uint8 or p.ndim != 3 or p.shape[2] != 3 for p in pictures):
+            raise ValueError("footprints_amd.ops.jpeg_encode: pictures must be uint8 [h, w, 3]")
+        shapes = [(int(p.shape[0]), int(p.shape[1])) for p in pictures]
+        packed = torch.from_numpy(np.concatenate([np.ascontiguousarray(p).reshape(-1) for p in pictures])).cuda()
+    if not shapes:
+        return []
+    records, total, max_h, max_w = jpeg_records(shapes)
+    out, table = jpeg_encode_packed(packed, total, torch.from_numpy(records).to(packed.device), len(shapes), quality, max_h=max_h, max_w=max_w)
+    table = table.cpu().numpy()                  # waits
+    used = int(table[len(shapes)][0])
+    return jpeg_files(out[:used].cpu().numpy().tobytes() if used else b"", table, shapes, quality)

@@ -10,10 +10,11 @@ numpy (identical arithmetic), cv2.resize(bilinear) becomes PIL BILINEAR, cv2.imw
 The reference quirk of thresholding the *logit* at 0.5 for the visualisation mask (predict_simple.py:77) is
 kept.  `--no_cuda` is accepted for CLI compatibility but raises: this package has no CPU compute path.
 
-Two options beyond the reference, both off by default (without them nothing here behaves differently):
+Options beyond the reference, all off by default (without them nothing here behaves differently):
 `--device_vis` draws the overlay on the GPU (csrc/visualise.hip), byte for byte what `InferenceManager.visualise` -- the host path, kept
 as it is -- gives for the same prediction: Pillow's mode-"F" BILINEAR restated, not the reference's cv2.resize; the JPEG encoder stays
-on the host.  `--batch_size N` predicts a folder N files at a time, in sorted order: one forward pass, one copy of the predictions and
+on the host unless `--device_jpeg` (needs --device_vis) is given too: then a group's overlays stay on the device, are encoded there
+(csrc/jpeg.hip) and the .jpg files are written from the returned bytes -- the files Pillow writes, byte for byte.  `--batch_size N` predicts a folder N files at a time, in sorted order: one forward pass, one copy of the predictions and
 (with --device_vis) one overlay call and one copy of the overlays per group; the photos of a group may differ in size, and the same
 files are written under the same names.  A batched forward pass differs from per-image passes at fp32 round-off -- the small
 convolutions split their K loop by a rule that depends on the batch size -- so a .npy of a batched run is within the contract's 1e-4 of
@@ -48,7 +49,7 @@ def preprocess(pil_image, height_width, device_resize=False):
 
 class InferenceManager:
     def __init__(self, model_name, save_dir, use_cuda=True, save_visualisations=True, weights_path=None, model_manager=None,
-                 device_resize=False, device_vis=False, batch_size=1):
+                 device_resize=False, device_vis=False, batch_size=1, device_jpeg=False):
         if not use_cuda or not torch.cuda.is_available():
             raise RuntimeError("footprints_amd.predict_simple needs a MI355X: the package has no CPU compute path "
                                "(--no_cuda is accepted for CLI compatibility only)")
@@ -64,6 +65,9 @@ class InferenceManager:
         self.device_vis, self.batch_size = bool(device_vis), int(batch_size)
         if self.batch_size < 1:
             raise ValueError("batch_size must be at least 1")
+        self.device_jpeg = bool(device_jpeg)
+        if self.device_jpeg and not self.device_vis:
+            raise ValueError("device_jpeg encodes the overlays where device_vis draws them: it needs device_vis")
         self.overlay_hook = None       # callable(file stem, uint8 [h, w, 3]): sees every overlay before it is encoded
         self.save_dir = save_dir
         os.makedirs(os.path.join(save_dir, "outputs"), exist_ok=True)
@@ -91,11 +95,16 @@ class InferenceManager:
             self._save_visualisation(filename, self.visualise(pred, original))
         return pred
 
-    def _save_visualisation(self, filename, vis):
+    def _save_visualisation(self, filename, vis, encoded=None):
+        """encoded: the file's bytes when the device has encoded the overlay already"""
         if self.overlay_hook is not None:
             self.overlay_hook(filename, vis)
         vis_save_path = os.path.join(self.save_dir, "visualisations", filename + ".jpg")
         print("└> Saving visualisation to {}".format(vis_save_path))
+        if encoded is not None:
+            with open(vis_save_path, "wb") as fh:
+                fh.write(encoded)
+            return
         Image.fromarray(vis).save(vis_save_path, quality=95)
 
     def predict_for_images(self, image_paths):
@@ -118,21 +127,34 @@ class InferenceManager:
         with torch.no_grad():
             pred_dev = self.model_manager.model(x)["1/1"].contiguous()
         preds = pred_dev.cpu().numpy()                           # [B,4,H,W]: one copy for the group
-        overlays = None
+        overlays, files = None, None
         if self.save_visualisations and self.device_vis:
             shapes = [(o.size[1], o.size[0]) for o in originals]
-            if packed is not None:
-                overlays = ops.vis_overlay(pred_dev, packed=packed, shapes=shapes)
+            source = dict(packed=packed, shapes=shapes) if packed is not None else dict(originals=[np.asarray(o, dtype=np.uint8) for o in originals])
+            if self.device_jpeg:
+                files, overlays = self._encode_overlays(*ops.vis_overlay_device(pred_dev, **source))
             else:
-                overlays = ops.vis_overlay(pred_dev, originals=[np.asarray(o, dtype=np.uint8) for o in originals])
+                overlays = ops.vis_overlay(pred_dev, **source)
         for i, path in enumerate(image_paths):
             filename, _ = os.path.splitext(os.path.basename(path))
             npy_save_path = os.path.join(self.save_dir, "outputs", filename + ".npy")
             print("└> Saving predictions to {}".format(npy_save_path))
             np.save(npy_save_path, preds[i])
-            if self.save_visualisations:
+            if files is not None:
+                self._save_visualisation(filename, overlays[i] if overlays is not None else None, files[i])
+            elif self.save_visualisations:
                 self._save_visualisation(filename, overlays[i] if overlays is not None else self.visualise(preds[i], originals[i]))
         return preds
+
+    def _encode_overlays(self, buffer, total, shapes):
+        """the overlays of a group, lying in a device buffer -> (their .jpg files' bytes, the raw overlays for the hook or None)"""
+        from . import ops
+        records, _, max_h, max_w = ops.jpeg_records(shapes)
+        scans, table = ops.jpeg_encode_packed(buffer, total, torch.from_numpy(records).to(buffer.device), len(shapes), 95, max_h=max_h, max_w=max_w)
+        table = table.cpu().numpy()                              # waits
+        files = ops.jpeg_files(scans[:int(table[len(shapes)][0])].cpu().numpy().tobytes(), table, shapes, 95)
+        # the hook sees the raw overlay: only then is it copied
+        return files, (ops.split_pictures(buffer[:total].cpu().numpy(), shapes) if self.overlay_hook is not None else None)
 
     @staticmethod
     def visualise(pred, original):
@@ -189,14 +211,19 @@ def parse_args(argv=None):
     ap.add_argument("--device_resize", action="store_true", help="resize the decoded image on the GPU (same bytes as PIL's LANCZOS)")
     ap.add_argument("--device_vis", action="store_true", help="draw the overlays on the GPU (same bytes as the host path before the JPEG encoder)")
     ap.add_argument("--batch_size", type=int, default=1, help="files of a folder per forward pass (sorted order; sizes may differ)")
-    return ap.parse_args(argv)
+    ap.add_argument("--device_jpeg", action="store_true", help="with --device_vis: encode the overlays on the GPU too (the same .jpg files)")
+    args = ap.parse_args(argv)
+    if args.device_jpeg and not args.device_vis:
+        ap.error("--device_jpeg needs --device_vis: it encodes the overlays where they are drawn")
+    return args
 
 
 def main(argv=None):
     args = parse_args(argv)
     manager = InferenceManager(model_name=args.model, use_cuda=torch.cuda.is_available() and not args.no_cuda,
                                save_visualisations=not args.no_save_vis, save_dir=args.save_dir, weights_path=args.weights,
-                               device_resize=args.device_resize, device_vis=args.device_vis, batch_size=args.batch_size)
+                               device_resize=args.device_resize, device_vis=args.device_vis, batch_size=args.batch_size,
+                               device_jpeg=args.device_jpeg)
     manager.predict(image_path=args.image)
 
 

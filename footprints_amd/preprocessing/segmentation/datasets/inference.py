@@ -5,7 +5,8 @@ A sample is {'image': the decoded RGB frame uint8 [h, w, 3] at its NATIVE size, 
 `Resize((height, width), ANTIALIAS)` + `ToTensor` run on the device for the whole batch (ops.resize_u8 + ops.to_tensor_u8, bit-equal).
 `save_result` writes what the reference writes -- `<savepath>/.../data/<name>.npy`, float16 [1, H, W], and, when a picture is passed,
 `<savepath>/.../visualisations/<name>.jpg` -- but takes the float16 array and the uint8 picture as the device produced them
-(ops.seg_pack): no cast, no colour map, and Pillow encodes the bytes where the reference calls plt.imsave.
+(ops.seg_pack): no cast, no colour map, and Pillow encodes the bytes where the reference calls plt.imsave -- or, with --device_jpeg,
+the file's bytes arrive encoded (ops.jpeg_encode_packed: what Pillow would write, byte for byte) and are written as they are.
 
 The reference's MatterportInferenceDataset cannot be constructed: `__init__` reads an undefined name `image_ext`
 (inference_dataset.py:101) and `_load_image` reads `self.datapath` where the attribute is `data_path` (:107).  It is built here as
@@ -35,7 +36,8 @@ class InferenceDataset:
         raise NotImplementedError
 
     def save_result(self, savepath, filename, prediction, visualisation=None):
-        """prediction: [1, H, W], written as float16; visualisation: uint8 [H, 2 W, 3] or None"""
+        """prediction: [1, H, W], written as float16; visualisation: uint8 [H, 2 W, 3], or the .jpg file's bytes as the device encoded
+        them (ops.jpeg_encode), or None"""
         _savepath = os.path.join(savepath, "data")
         os.makedirs(_savepath, exist_ok=True)
         np.save(os.path.join(_savepath, "{}.npy".format(str(filename).zfill(10))), np.asarray(prediction, dtype=np.float16))
@@ -43,6 +45,10 @@ class InferenceDataset:
             from PIL import Image
             _savepath = os.path.join(savepath, "visualisations")
             os.makedirs(_savepath, exist_ok=True)
+            if isinstance(visualisation, (bytes, bytearray, memoryview)):
+                with open(os.path.join(_savepath, "{}.jpg".format(str(filename).zfill(10))), "wb") as fh:
+                    fh.write(visualisation)
+                return
             Image.fromarray(np.asarray(visualisation, dtype=np.uint8)).save(
                 os.path.join(_savepath, "{}.jpg".format(str(filename).zfill(10))), quality=95)
 

@@ -9,6 +9,7 @@ import queue
 import threading
 import time
 
+import numpy as np
 import torch
 
 from ... import _lib, ops
@@ -40,7 +41,9 @@ class Tester:
                with `inference_scales = ("1/1",)`, ops.seg_pack (sigmoid, float16, the picture) and the copies into the slot's pinned
                result buffers; it does not wait for any of it, so batch k + 1 is queued while batch k's results come back;
       writer   ONE thread waits for a slot's `ready` event, writes its files (np.save; Pillow encodes the device-drawn picture) and hands
-               the slot back.  A slot is not refilled before that.
+               the slot back.  A slot is not refilled before that.  With --device_jpeg the picture stays on the device and is encoded
+               there behind seg_pack (ops.jpeg_encode_packed: the files Pillow writes, byte for byte); only the table of the scans'
+               lengths comes back with the batch, and the writer, which may wait, copies the bytes in use on a stream of its own.
     An exception in a reader or in the writer ends `test()` with that exception; every wait on a queue, a future or a slot has a timeout
     after which the waiting thread looks at the error flag.  `has_gt`, tensorboard and data parallelism are not part of this mode."""
 
@@ -55,6 +58,7 @@ class Tester:
         self.batch_size = int(options.batch_size)
         self.num_workers = min(max(int(getattr(options, "num_workers", 4) or 1), 1), 16)
         self.visualise = bool(options.save_test_visualisations)
+        self.device_jpeg = self.visualise and bool(getattr(options, "device_jpeg", False))
         if dataset is None or save_path is None:
             import yaml
             with open(self.opt.config_path) as fh:
@@ -102,8 +106,18 @@ class Tester:
                      h_half=torch.empty((B, 1, H, W), dtype=torch.float16).pin_memory(), d_pic=None, h_pic=None)
             if self.visualise:
                 s["d_pic"] = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8, device=self.device)
+            if self.device_jpeg:
+                s["d_scan"] = torch.empty(ops.jpeg_max_scan_bytes(B, H, 2 * W), dtype=torch.uint8, device=self.device)
+                s["d_tab"] = torch.empty((B + 1, 2), dtype=torch.int64, device=self.device)
+                s["h_tab"] = torch.empty((B + 1, 2), dtype=torch.int64).pin_memory()
+            elif self.visualise:
                 s["h_pic"] = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8).pin_memory()
             slots.append(s)
+        if self.device_jpeg:
+            # the pictures of a batch lie dense in d_pic: one set of records serves every slot, and its first n a batch of n
+            self.jpeg_records = torch.from_numpy(ops.jpeg_records([(H, 2 * W)] * B)[0]).to(self.device)
+            self.copy_stream = torch.cuda.Stream(self.device)
+            self.h_scan = None                  # the writer's pinned buffer for the bytes in use; grows
         return slots
 
     def _reserve_src(self, s, nbytes):
@@ -140,17 +154,37 @@ class Tester:
             pic = s["d_pic"][:n] if self.visualise else None
             ops.seg_pack(logits, image if self.visualise else None, want_picture=self.visualise, out=(s["d_half"][:n], None, pic))
             s["h_half"][:n].copy_(s["d_half"][:n], non_blocking=True)
-            if self.visualise:
+            if self.device_jpeg:
+                ops.jpeg_encode_packed(s["d_pic"].view(-1), n * H * 2 * W * 3, self.jpeg_records, n, 95, out=s["d_scan"], max_h=H, max_w=2 * W,
+                                       table=s["d_tab"][:n + 1])
+                s["h_tab"][:n + 1].copy_(s["d_tab"][:n + 1], non_blocking=True)
+            elif self.visualise:
                 s["h_pic"][:n].copy_(s["d_pic"][:n], non_blocking=True)
             s["ready"].record()
 
     def _wait_slot(self, s, n):
-        """wait for the slot's results -> (float16 numpy [n, 1, H, W], uint8 numpy [n, H, 2 W, 3] or None): views of the pinned buffers"""
+        """wait for the slot's results -> (float16 numpy [n, 1, H, W], uint8 numpy [n, H, 2 W, 3] or None): views of the pinned buffers;
+        with device_jpeg the second is the list of the n .jpg files' bytes"""
         while not s["ready"].query():                       # a wait with a timeout, like every other one: look at the stop flag in between
             if self._stop.is_set():
                 raise RuntimeError("the inference pipeline was stopped while a batch was in flight")
             time.sleep(self.SPIN)
+        if self.device_jpeg:
+            return s["h_half"].numpy()[:n], self._fetch_files(s, n)
         return s["h_half"].numpy()[:n], (s["h_pic"].numpy()[:n] if self.visualise else None)
+
+    def _fetch_files(self, s, n):
+        """the slot's batch is finished and its length table is on the host: copy the scans' bytes in use -- on a stream of this thread's
+        own, which it waits for; the thread that queues batches never does -- and put headers and EOI around them"""
+        table = s["h_tab"].numpy()[:n + 1]
+        used = int(table[n][0])
+        if self.h_scan is None or self.h_scan.numel() < used:
+            self.h_scan = torch.empty(max(used + used // 4, 1 << 16), dtype=torch.uint8).pin_memory()
+        if used:
+            with torch.cuda.stream(self.copy_stream):
+                self.h_scan[:used].copy_(s["d_scan"][:used], non_blocking=True)
+            self.copy_stream.synchronize()
+        return ops.jpeg_files(self.h_scan.numpy()[:used], table, [(self.height, 2 * self.width)] * n, 95)
 
     def test_batch(self, frames):
         """frames: list of decoded RGB frames, uint8 [h, w, 3] of any (mixed) sizes -> (float16 numpy [B, 1, H, W], uint8 numpy
@@ -161,7 +195,7 @@ class Tester:
         self._stop.clear()
         self._device_half(s, frames)
         half, pics = self._wait_slot(s, len(frames))
-        return half.copy(), (pics.copy() if pics is not None else None)
+        return half.copy(), (pics.copy() if isinstance(pics, np.ndarray) else pics)
 
     # ---- the pipeline -----------------------------------------------------------------------------------------------------------------
     def _fail(self, exc):

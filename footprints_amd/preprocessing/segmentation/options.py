@@ -31,6 +31,8 @@ class SegmentationOptions:
                        default="ground_seg")
         p.add_argument("--test_data_type", choices=["kitti", "matterport"], default="kitti")
         p.add_argument("--save_test_visualisations", action="store_true")
+        p.add_argument("--device_jpeg", action="store_true",
+                       help="with --save_test_visualisations: encode the pictures on the GPU (same files as Pillow writes)")
 
     def parse(self, args=None):
         self.options = self.parser.parse_args(args)

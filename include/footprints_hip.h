@@ -641,6 +641,32 @@ int fp_vis_side_by_side(const float* image, const float* pred, uint8_t* out, int
 int fp_seg_pack(const float* logits, int64_t logit_batch_stride, const float* image, void* prob_half, float* prob_f32, uint8_t* picture,
                 const uint8_t* lut, int32_t B, int32_t H, int32_t W, fp_stream_t stream);
 
+/* ---- baseline JPEG encoder (csrc/jpeg.hip): the scan Pillow's Image.save(quality=q) writes for an RGB picture, byte for byte ---- */
+typedef struct fp_jpeg_sample {
+  int64_t offset; /* of the picture's first byte in `src`; dense uint8 [h][w][3] */
+  int32_t h, w;   /* 1 .. 65535 each, and within the call's max_h, max_w */
+} fp_jpeg_sample;
+int32_t fp_jpeg_sample_bytes(void);
+/* uint32 words of the code table the caller builds from a header of its own JPEG library: [2][64] quantisation values in zigzag order
+ * (luma, chroma: as the DQT segments hold them), [2][16] DC categories and [2][256] AC run / size symbols as code | length << 16
+ * (length 0 = no such symbol), luma before chroma. */
+int32_t fp_jpeg_table_words(void);
+/* Scratch of one call over B pictures of at most max_h x max_w, from the worst case of one block -- 20 DC bits and 63 AC terms of 26
+ * bits -- for the unstuffed streams; int16 coefficients and a bit offset per block beside them.  -1 on bad arguments or when a stream
+ * could pass 2^31 bits.  The second query is the largest output the B scans can need: that worst case doubled for byte stuffing. */
+int64_t fp_jpeg_workspace_bytes(int32_t B, int32_t max_h, int32_t max_w);
+int64_t fp_jpeg_max_scan_bytes(int32_t B, int32_t max_h, int32_t max_w);
+/* Encodes B pictures of mixed sizes in one call: baseline sequential DCT, YCbCr 4:2:0 (luma 2x2, one interleaved scan), no restart
+ * markers, the code table's Huffman codes as they are; libjpeg's integer colour conversion, h2v2 downsample with its alternating bias,
+ * edge replication, jfdctint, quantiser and dummy blocks.  samples: B fp_jpeg_sample records on the device; tables: the code table on the
+ * device.  out receives the entropy-coded scans of the accepted samples back to back (FF bytes stuffed, the last byte filled with
+ * one-bits), neither header nor EOI; table: int64 [B + 1][2] on the device, row b = byte offset and length of sample b's scan in out, row
+ * B = the bytes written in all and the status.  The status is cleared by the call and set to 1 when a record was turned down -- h or w
+ * outside 1 .. 65535 or beyond max_h / max_w, an offset outside `src` -- or a scan did not fit into out_bytes; such a sample has length 0
+ * and nothing of it is written.  Nothing waits for the device: read the table after the stream has finished. */
+int fp_jpeg_encode(const uint8_t* src, int64_t src_bytes, const void* samples, const uint32_t* tables, uint8_t* out, int64_t out_bytes,
+                   int64_t* table, int32_t B, int32_t max_h, int32_t max_w, void* workspace, int64_t workspace_bytes, fp_stream_t stream);
+
 /* ---- pyramid pooling of the ground-segmentation network (footprints/preprocessing/segmentation/network.py:174-207) ---- */
 /* nn.AdaptiveAvgPool2d(P) (network.py:180,188): y[N][P][P][C] = window means of x[N][H][W][C]; windows floor(i*H/P) .. ceil((i+1)*H/P) */
 int fp_adaptive_avgpool_fwd(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t P, fp_stream_t stream);
