@@ -1012,9 +1012,14 @@ def gt_depth_mask(keys, depth, ground_seg, want_projection=False):
     return (mask.view(torch.bool), proj) if want_projection else mask.view(torch.bool)
 
 
-# ---- reader work on the device: Pillow's 8-bit resize and filter_depth_mask (csrc/reader.hip) -----------------------------------------
+# ---- reader work on the device: Pillow's 8-bit resize (csrc/resample_u8.hip) and filter_depth_mask (csrc/reader.hip) ------------------
 RESIZE_FILTERS = {"lanczos": _lib.RESIZE_LANCZOS, "bilinear": _lib.RESIZE_BILINEAR, "bicubic": _lib.RESIZE_BICUBIC, "box": _lib.RESIZE_BOX}
 _resize_host_tables = {}
+
+
+def _status_word(ws, off):
+    """the int32 a resize call left at byte `off` of its workspace (WAITS for the stream)"""
+    return int(ws[off:off + 4].view(torch.int32).item())
 
 
 def _resize_filter(f):
@@ -1156,8 +1161,7 @@ def resize_u8_packed(src, src_bytes, samples, B, H, W, Cn, max_h, max_w, tables,
                                 _chk(d_coeffs) if n_tables else None, d_coeffs.numel() if n_tables else 0, _chk(out, "out"), B, H, W, Cn,
                                 max_h, max_w, ws.data_ptr(), ws.numel(), stream()), "fp_resize_u8")
     if check:
-        off = lib.fp_resize_status_offset(B, max_h, W, Cn)
-        if int(ws[off:off + 4].view(torch.int32).item()) != 0:
+        if _status_word(ws, lib.fp_resize_status_offset(B, max_h, W, Cn)) != 0:
             raise ValueError("footprints_amd.ops.resize_u8_packed: a sample or table record was turned down on the device; its output is unwritten")
     return out
 
@@ -1214,7 +1218,7 @@ def load_images_u8(images, H, W, filter="lanczos", device="cuda"):
     return to_tensor_u8(resize_u8(images, H, W, filter, device))
 
 
-# ---- reader work of the segmentation trainer: windowed per-sample resize and the label path (csrc/seg_reader.hip) ---------------------------
+# ---- reader work of the segmentation trainer: windowed per-sample resize and the label path (csrc/resample_u8.hip, csrc/seg_reader.hip) ----------
 def resize_tables_range(in_size, out_size, first, count, filter="lanczos"):
     """rows first .. first + count - 1 of `resize_tables(in_size, out_size, filter)`, built alone: the cost is that of `count` rows.  Not
     cached -- the segmentation reader's target sizes are random per sample."""
@@ -1309,8 +1313,7 @@ def resize_window_u8(src, src_bytes, samples, B, tables, n_tables, coeffs, coeff
                                        out.numel(), B, Cn, max_src_h, max_src_w, max_win_h, max_win_w, ws.data_ptr(), ws.numel(), stream()),
                "fp_resize_window_u8")
     if check:
-        off = lib.fp_resize_window_status_offset(B, max_src_h, max_win_w, Cn)
-        if int(ws[off:off + 4].view(torch.int32).item()) != 0:
+        if _status_word(ws, lib.fp_resize_window_status_offset(B, max_src_h, max_win_w, Cn)) != 0:
             raise ValueError("footprints_amd.ops.resize_window_u8: a sample or table record was turned down on the device; its output is unwritten")
     return out
 
@@ -1321,8 +1324,7 @@ def resize_window_status(device, B, max_src_h, max_win_w, Cn):
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     off = _lib.load().fp_resize_window_status_offset(B, max_src_h, max_win_w, Cn)
-    ws = workspace(off + 16, device, "resize_window")
-    return int(ws[off:off + 4].view(torch.int32).item())
+    return _status_word(workspace(off + 16, device, "resize_window"), off)
 
 
 def seg_labels(src, src_bytes, samples, B, index, index_len, ground_ids, set_offsets, H, W, ground_mask=None, labelled_pix=None, status=None,

@@ -487,7 +487,8 @@ int fp_assemble_labels(const void* visible_ground, const void* ground_depth, con
                        int32_t no_depth_mask, int32_t project_down_baseline, int32_t use_moving, double threshold, double fxb,
                        double depth_scaling, fp_stream_t stream);
 
-/* ---- device-side reader work: Pillow's 8-bit Image.resize and filter_depth_mask (footprint_dataset.py:73-80, :96-105; csrc/reader.hip) ---- */
+/* ---- device-side reader work: Pillow's 8-bit Image.resize and filter_depth_mask (footprint_dataset.py:73-80, :96-105;
+ * csrc/resample_u8.hip, csrc/reader.hip) ---- */
 /* Resample filters, numbered like Pillow's Image.Resampling.  NEAREST (0) is not provided; of the mode-"F" (float) paths only
  * what the overlay below needs: the double tables as an entry point of their own, the float passes inside the overlay. */
 #define FP_RESIZE_LANCZOS 1
@@ -520,7 +521,8 @@ int64_t fp_resize_workspace(int32_t B, int32_t max_h, int32_t W, int32_t C);
 int64_t fp_resize_status_offset(int32_t B, int32_t max_h, int32_t W, int32_t C);
 /* B source images of different sizes (all h <= max_h, w <= max_w; C = 1 or 3), packed in `src` (4-byte aligned, src_bytes long) and
  * described by `samples` (device, B records), -> out uint8 [B][H][W][C], byte for byte what PIL.Image.resize((W, H), filter) gives:
- * horizontal pass into the uint8 workspace, then the vertical pass, a pass whose sizes agree skipped, int32 arithmetic throughout.
+ * horizontal pass into the uint8 workspace, then the vertical pass, a pass whose sizes agree skipped, int32 arithmetic throughout.  It is
+ * fp_resize_window_u8 (below) with window = target and rectangle = source: the same two kernels, two launches.
  * tables: n_tables device records over `coeffs` (device int32, coeffs_len elements).  A record that points outside a buffer, or whose
  * table does not fit its sizes, leaves that sample's output unwritten and sets the workspace's status word to 1 (every call clears it
  * first; read it after the stream has finished).  max_w * C <= 65528 (a source row is staged in LDS). */
@@ -534,7 +536,8 @@ int64_t fp_filter_depth_mask_workspace(int32_t B, int32_t H, int32_t W);
 int fp_filter_depth_mask(const void* mask, int32_t is_double, void* out, int32_t B, int32_t H, int32_t W, void* workspace,
                          int64_t workspace_bytes, fp_stream_t stream);
 
-/* ---- device-side reader work of the segmentation trainer (footprints/preprocessing/segmentation/datasets; csrc/seg_reader.hip) ---- */
+/* ---- device-side reader work of the segmentation trainer (footprints/preprocessing/segmentation/datasets;
+ * csrc/resample_u8.hip, csrc/seg_reader.hip) ---- */
 /* HOST function (no GPU needed): rows first .. first + count - 1 of fp_resize_coeffs' tables (bounds int32 [count][2], kk int32
  * [count][ksize]).  Pillow computes every output index on its own, so the rows are identical; work and memory are those of `count` rows. */
 int fp_resize_coeffs_range(int32_t in_size, int32_t out_size, int32_t filter, int32_t first, int32_t count, int32_t* bounds, int32_t* kk,
@@ -566,7 +569,7 @@ int32_t fp_resize_window_sample_bytes(void);
 int64_t fp_resize_window_workspace(int32_t B, int32_t max_src_h, int32_t max_win_w, int32_t C);
 int64_t fp_resize_window_status_offset(int32_t B, int32_t max_src_h, int32_t max_win_w, int32_t C);
 /* Per sample, the bytes of PIL.Image.resize((tw, th), filter).crop((left, top, left + win_w, top + win_h)), where (tw, th) is the sample's
- * OWN target size (the out_size of its tables): Pillow's 8-bit arithmetic as in fp_resize_u8, but the horizontal pass runs only over the
+ * OWN target size (the out_size of its tables): Pillow's 8-bit arithmetic and the two kernels of fp_resize_u8, but the horizontal pass runs only over the
  * source rows the window's vertical taps reach and over the window's columns, and the vertical pass produces only the window.  With both
  * tables -1 the window is copied.  `src` (device, 4-byte aligned, src_bytes long) holds each sample's staged rectangle -- at least the rows
  * and columns the window's taps reach, at most the whole image (origin 0, 0); it may be the `out` of an earlier call, which chains two

@@ -1,5 +1,5 @@
 """GPU box: time of the reader work for one KITTI batch of 12 -- mixed native frame sizes -> 192 x 640 through Pillow's LANCZOS, and the
-depth-mask filter on 192 x 640 masks at ~10 % density -- on the device (csrc/reader.hip) next to the host path it replaces, measured on
+depth-mask filter on 192 x 640 masks at ~10 % density -- on the device (csrc/resample_u8.hip, csrc/reader.hip) next to the host path it replaces, measured on
 the same machine: PIL.Image.resize and scipy.ndimage.label + the reference's loop (footprint_dataset.py:96-105), each on one core.
 
     python scripts/reader_bench.py [--seconds 2.0] [--rounds 5]

@@ -1,4 +1,4 @@
-"""GPU box: what a training batch of the ground-segmentation trainer costs on the device path (csrc/seg_reader.hip,
+"""GPU box: what a training batch of the ground-segmentation trainer costs on the device path (csrc/resample_u8.hip, csrc/seg_reader.hip,
 datasets/device_path.SegBatchAssembler) next to the host chain it replaces and to the step it feeds, for three kinds of batches of 12 at
 192 x 640: Cityscapes frames (1024 x 2048), Matterport frames (1024 rows x 1280 columns) and an ADE20K-like mix of small and large frames.
 

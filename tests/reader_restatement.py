@@ -1,4 +1,4 @@
-"""NumPy restatement of the two reader operations that csrc/reader.hip runs on the device (no Pillow, scipy or skimage needed):
+"""NumPy restatement of the two reader operations that csrc/resample_u8.hip and csrc/reader.hip run on the device (no Pillow, scipy or skimage needed):
 
 * Pillow's 8-bit `Image.resize` (libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc, ImagingResampleHorizontal_8bpc /
   Vertical_8bpc): per axis a table of window bounds and 22-bit fixed-point taps built in double, then int32 accumulation, an arithmetic

@@ -1,4 +1,4 @@
-"""NumPy restatement of what csrc/seg_reader.hip and footprints_amd/preprocessing/segmentation/datasets/plan.py do for a sample of the
+"""NumPy restatement of what csrc/resample_u8.hip, csrc/seg_reader.hip and footprints_amd/preprocessing/segmentation/datasets/plan.py do for a sample of the
 ground-segmentation trainer (no Pillow needed), built on tests/reader_restatement.py (Pillow's 8-bit resample) and on
 oracle/data_path.jitter_np (torchvision 0.4.2's ColorJitter in Pillow's byte arithmetic):
 

@@ -1,4 +1,4 @@
-"""GPU: the reader kernels (csrc/reader.hip) -- Pillow's 8-bit resize and the depth-mask filter -- bit for bit against the restatement
+"""GPU: the reader kernels -- Pillow's 8-bit resize (csrc/resample_u8.hip) and the depth-mask filter (csrc/reader.hip) -- bit for bit against the restatement
 (tests/reader_restatement.py, pinned to the installed Pillow and to scipy + the reference's loop by tests/test_reader_cpu.py) and against
 the fixture g14_reader (the real Pillow's and the reference class's outputs); then the assembler and predict_simple options built on them.
 Needs neither Pillow nor scipy nor the reference.  No tolerance anywhere: every comparison is np.array_equal."""

@@ -1,5 +1,5 @@
-"""GPU: the reader of the ground-segmentation trainer on the device (csrc/seg_reader.hip, datasets/device_path.SegBatchAssembler) against
-the NumPy restatement (tests/seg_reader_restatement.py, pinned to Pillow and to the reference on the CPU) and against what the
+"""GPU: the reader of the ground-segmentation trainer on the device (csrc/resample_u8.hip, csrc/seg_reader.hip,
+datasets/device_path.SegBatchAssembler) against the NumPy restatement (tests/seg_reader_restatement.py, pinned to Pillow and to the reference on the CPU) and against what the
 reference's own dataset code wrote (tests/golden/g16_seg_reader.npz), and the segmentation trainer on device-assembled batches.
 Everything but the trainer's loss is compared with np.array_equal.  Needs neither Pillow nor the reference."""
 import ctypes as C
@@ -181,6 +181,23 @@ def test_mixed_batch_in_one_call():
     assert status == 0
     for i, (g, c) in enumerate(zip(grey, SI.GREY_CASES)):
         assert np.array_equal(g, expect(c, seed=20 + i))
+
+
+@pytest.mark.parametrize("channels, shapes", [(3, [(37, 53), (17, 53), (37, 23), (17, 23), (5, 7), (41, 23)]), (1, [(37, 53), (17, 53), (37, 23)])],
+                         ids=["rgb", "grey"])
+def test_whole_frame_resize_is_the_window_resize_of_the_whole_target(channels, shapes):
+    """fp_resize_u8 = fp_resize_window_u8 with window = target and rectangle = source, byte for byte: the ragged batch of
+    test_gpu_reader.test_resize_ragged_batch_mixed_passes (both passes, each alone, neither, 5 -> 17 with the taps clamped at both borders,
+    23 * C bytes per row, 17 rows for a tile of 8), the window call's sources at odd byte offsets"""
+    from footprints_amd import ops
+    from tests.golden import reader_inputs as RI
+    H, W = 17, 23
+    imgs = [RI.image(h, w, channels, 40 + i) for i, (h, w) in enumerate(shapes)]
+    whole = ops.resize_u8(imgs, H, W).cpu().numpy()
+    got, status = run_windows([dict(img=im, target=(H, W), window=(0, 0, H, W), rect="whole", whole_tables=True) for im in imgs], channels=channels, pad=1)
+    assert status == 0
+    for i, g in enumerate(got):
+        assert np.array_equal(g, whole[i]), shapes[i]
 
 
 # ---- labels ---------------------------------------------------------------------------------------------------------------------------
