@@ -72,6 +72,15 @@ class JpegSample(C.Structure):
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+JPEG_DECODE_TABLE_WORDS = 1696    # fp_jpeg_decode_table_words()
+
+
+class JpegDecodeSample(C.Structure):
+    """fp_jpeg_decode_sample (include/footprints_hip.h)"""
+    _fields_ = [("scan_offset", C.c_int64), ("out_offset", C.c_int64)] + [(n, C.c_int32) for n in (
+        "scan_bytes", "h", "w", "ncomp", "hs", "vs", "table_set", "reserved")]
+
+
 _P, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _DESC = C.POINTER(ConvDesc)
 
@@ -140,6 +149,10 @@ SIGNATURES = {
     "fp_jpeg_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "fp_jpeg_max_scan_bytes": (_I64, [_I32, _I32, _I32]),
     "fp_jpeg_encode": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_jpeg_decode_sample_bytes": (_I32, []),
+    "fp_jpeg_decode_table_words": (_I32, []),
+    "fp_jpeg_decode_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32]),
+    "fp_jpeg_decode": (C.c_int, [_P, _I64, _P, _P, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "fp_adaptive_avgpool_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "fp_adaptive_avgpool_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, C.c_int, _P]),
     "fp_bilinear_ac_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),

@@ -1730,3 +1730,295 @@ def jpeg_encode(pictures, quality=95):
     table = table.cpu().numpy()                  # waits
     used = int(table[len(shapes)][0])
     return jpeg_files(out[:used].cpu().numpy().tobytes() if used else b"", table, shapes, quality)
+
+
+# ---- baseline JPEG decoder (csrc/jpeg_decode.hip) ------------------------------------------------------------------------------------------
+# Both defaults rest on the bench batch of profiles/jpeg_decode_notes.md (12 picture-like 375 x 1242 frames, quality 95, 4:2:0): 256 and
+# 512 bits were the fastest lengths, 512 by 1 to 2 %, and 256 keeps noise at quality 100 on the fallback path (the notes say why that
+# decided); the launch budget is twice the most launches a file of the batch needed to settle.
+JPEG_DECODE_SUBSEQ_BITS = 256
+JPEG_DECODE_MAX_ROUNDS = 4
+_JPEG_NATURAL = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42,
+                 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+
+
+class _JpegHost(Exception):
+    """the reason a file is decoded on the host"""
+
+
+def _jpeg_parse(data):
+    import numpy as np
+    n_data = len(data)
+    if n_data < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        raise _JpegHost("no start-of-image marker")
+    quant, huff, frame, jfif, i = {}, {}, None, False, 2
+    while True:
+        if i + 4 > n_data:
+            raise _JpegHost("the header is cut")
+        if data[i] != 0xFF:
+            raise _JpegHost("marker expected at byte %d" % i)
+        marker = data[i + 1]
+        if marker == 0xFF:                                          # fill byte
+            i += 1
+            continue
+        length = (data[i + 2] << 8) | data[i + 3]
+        if length < 2 or i + 2 + length > n_data:
+            raise _JpegHost("segment length %d at byte %d" % (length, i))
+        body = bytes(data[i + 4:i + 2 + length])
+        if marker == 0xE0:
+            jfif = jfif or (length >= 16 and body[:5] == b"JFIF\0")
+        elif marker == 0xEE:
+            if body[:5] == b"Adobe":
+                raise _JpegHost("Adobe marker")
+        elif marker == 0xDB:
+            p = 0
+            while p < len(body):
+                if body[p] >> 4 or (body[p] & 15) > 3 or p + 65 > len(body):
+                    raise _JpegHost("quantisation table of 16 bits, or cut")
+                quant[body[p] & 15] = body[p + 1:p + 65]            # zigzag order
+                p += 65
+        elif marker == 0xC4:
+            p = 0
+            while p < len(body):
+                if p + 17 > len(body) or (body[p] >> 4) > 1 or (body[p] & 15) > 1:
+                    raise _JpegHost("Huffman table id")
+                counts = body[p + 1:p + 17]
+                total = sum(counts)
+                values = body[p + 17:p + 17 + total]
+                if total > 256 or len(values) != total:
+                    raise _JpegHost("Huffman table cut")
+                code = 0
+                for bits in range(1, 17):                           # the codes of a length must fit into it
+                    code += counts[bits - 1]
+                    if code > (1 << bits):
+                        raise _JpegHost("Huffman table over-subscribed")
+                    code <<= 1
+                if (body[p] >> 4) == 0 and any(v > 15 for v in values):
+                    raise _JpegHost("DC category above 15")
+                huff[(body[p] >> 4, body[p] & 15)] = (counts, values)
+                p += 17 + total
+        elif marker == 0xC0:
+            if frame is not None or len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise _JpegHost("frame header")
+            if body[0] != 8:
+                raise _JpegHost("%d-bit samples" % body[0])
+            frame = ((body[1] << 8) | body[2], (body[3] << 8) | body[4],
+                     [(body[6 + 3 * c], body[7 + 3 * c] >> 4, body[7 + 3 * c] & 15, body[8 + 3 * c]) for c in range(body[5])])
+        elif 0xC1 <= marker <= 0xCF:                                # C4 was taken above
+            raise _JpegHost("not baseline sequential Huffman (SOF%d)" % (marker - 0xC0))
+        elif marker == 0xDD:
+            if len(body) == 2 and (body[0] or body[1]):
+                raise _JpegHost("restart interval")
+        elif marker == 0xDA:
+            break
+        elif marker in (0x01, 0xD8, 0xD9, 0xDC) or 0xD0 <= marker <= 0xD7:
+            raise _JpegHost("marker %02X in the header" % marker)
+        i += 2 + length
+    if frame is None:
+        raise _JpegHost("scan before the frame header")
+    h, w, comps = frame
+    if h < 1 or w < 1:
+        raise _JpegHost("empty picture")
+    if len(comps) not in (1, 3):
+        raise _JpegHost("%d components" % len(comps))
+    if len(body) != 4 + 2 * len(comps) or body[0] != len(comps):
+        raise _JpegHost("not one scan of all components")
+    if body[1 + 2 * len(comps):] != b"\x00\x3f\x00":
+        raise _JpegHost("spectral selection or successive approximation")
+    tq, td, ta = [], [], []
+    for c, (ident, _, _, q) in enumerate(comps):
+        if body[1 + 2 * c] != ident:
+            raise _JpegHost("scan components out of order")
+        tq.append(q)
+        td.append(body[2 + 2 * c] >> 4)
+        ta.append(body[2 + 2 * c] & 15)
+        if q not in quant or (0, td[-1]) not in huff or (1, ta[-1]) not in huff:
+            raise _JpegHost("a table the file does not define")
+    if len(comps) == 1:
+        if comps[0][1:3] != (1, 1):
+            raise _JpegHost("grey with sampling factors")
+        hs = vs = 1
+    else:
+        if not jfif and [c[0] for c in comps] != [1, 2, 3]:
+            raise _JpegHost("not YCbCr by libjpeg's rule")
+        hs, vs = comps[0][1:3]
+        if (hs, vs) not in ((1, 1), (2, 1), (2, 2)) or comps[1][1:3] != (1, 1) or comps[2][1:3] != (1, 1):
+            raise _JpegHost("sampling %r" % ([c[1:3] for c in comps],))
+    start = i + 2 + length
+    a = np.frombuffer(data, dtype=np.uint8)[start:]
+    marks = np.flatnonzero((a[:-1] == 0xFF) & (a[1:] != 0)) if a.size > 1 else np.zeros(0, np.int64)
+    if marks.size == 0 or marks[0] == 0:
+        raise _JpegHost("no entropy-coded segment, or no marker behind it")
+    if a[marks[0] + 1] != 0xD9:
+        raise _JpegHost("marker %02X inside the scan (restart markers, or several scans)" % a[marks[0] + 1])
+    if int(marks[0]) >= 1 << 28:
+        raise _JpegHost("scan of 256 MiB or more")
+    return dict(h=h, w=w, ncomp=len(comps), hs=hs, vs=vs, tq=tuple(tq), td=tuple(td), ta=tuple(ta), quant=quant, huff=huff,
+                scan_offset=start, scan_bytes=int(marks[0]))
+
+
+def jpeg_parse(data):
+    """the markers of a JPEG file (bytes) -> a dict: device=True with h, w, ncomp, hs, vs (luma sampling), tq / td / ta (per component
+    the quantisation, DC and AC table ids), quant {id: 64 bytes in zigzag order}, huff {(class, id): (16 counts, symbols)}, scan_offset
+    and scan_bytes of the entropy-coded segment -- or device=False with the reason the file goes to Pillow.  Accepted: SOF0, 8 bits, one
+    interleaved scan, no restart interval, no Adobe marker, grey or YCbCr (JFIF marker, or component ids 1, 2, 3) with chroma 1x1 and
+    luma 1x1, 2x1 or 2x2.  Never raises on a damaged header."""
+    try:
+        info = _jpeg_parse(data if isinstance(data, (bytes, bytearray)) else bytes(data))
+    except (_JpegHost, IndexError) as e:
+        return dict(device=False, reason=str(e) or "the header is cut")
+    info["device"] = True
+    return info
+
+
+def _jpeg_huff_words(counts, values):
+    """one Huffman table of a table block (fp_jpeg_decode_table_words in include/footprints_hip.h)"""
+    import numpy as np
+    words = np.zeros(356, dtype=np.int64)
+    packed = np.zeros(256, dtype=np.int64)
+    packed[:len(values)] = list(values)
+    code, k = 0, 0
+    for bits in range(1, 17):
+        n = counts[bits - 1]
+        words[274 + bits] = k - code                                # valptr - mincode
+        for _ in range(n):
+            if bits <= 8:
+                words[code << (8 - bits):(code + 1) << (8 - bits)] = bits << 8 | values[k]
+            code += 1
+            k += 1
+        words[256 + bits] = code - 1 if n else -1                   # maxcode
+        code <<= 1
+    words[256] = words[273] = -1
+    words[292:356] = packed[0::4] | packed[1::4] << 8 | packed[2::4] << 16 | packed[3::4] << 24
+    return words
+
+
+def _jpeg_table_block(info):
+    import numpy as np
+    words = np.zeros(_lib.JPEG_DECODE_TABLE_WORDS, dtype=np.int64)
+    for c in range(info["ncomp"]):
+        words[4 * c:4 * c + 3] = (info["tq"][c], info["td"][c], info["ta"][c])
+    for t, q in info["quant"].items():
+        nat = np.zeros(64, dtype=np.int64)
+        nat[list(_JPEG_NATURAL)] = list(q)
+        words[16 + 64 * t:16 + 64 * t + 64] = nat
+    for (cls, t), (counts, values) in info["huff"].items():
+        at = 272 + 356 * (2 * cls + t)
+        words[at:at + 356] = _jpeg_huff_words(counts, values)
+    return (words & 0xFFFFFFFF).astype(np.uint32)
+
+
+_jpeg_table_blocks = {}
+
+
+def jpeg_decode_pack(files, infos=None, out_offsets=None, pinned=False):
+    """host half of the decoder for files jpeg_parse accepted: their entropy-coded segments one after the other in one uint8 buffer
+    (pinned=True: a pinned torch tensor's), the fp_jpeg_decode_sample records, and one table block per distinct set of tables and
+    selectors (most files share the standard tables).  out_offsets: where each picture goes in the output (default: one after the other)
+    -> dict(scans, scan_bytes, records, tables, n_sets, B, shapes, out_bytes, max_h, max_w, max_scan)"""
+    import numpy as np
+    infos = [jpeg_parse(f) for f in files] if infos is None else infos
+    if not files or any(not i["device"] for i in infos):
+        raise ValueError("footprints_amd.ops.jpeg_decode_pack: needs at least one file, and only files jpeg_parse accepts")
+    total = sum(i["scan_bytes"] for i in infos)
+    holder = torch.empty(total, dtype=torch.uint8).pin_memory() if pinned else None
+    scans = holder.numpy() if pinned else np.empty(total, dtype=np.uint8)
+    rec = (_lib.JpegDecodeSample * len(files))()
+    sets, blocks, at, out_at = {}, [], 0, 0
+    for b, (f, i) in enumerate(zip(files, infos)):
+        key = (i["tq"], i["td"], i["ta"], tuple(sorted(i["quant"].items())), tuple(sorted(i["huff"].items())))
+        block = _jpeg_table_blocks.get(key)
+        if block is None:
+            if len(_jpeg_table_blocks) > 256:
+                _jpeg_table_blocks.clear()
+            block = _jpeg_table_blocks[key] = _jpeg_table_block(i)
+        if key not in sets:
+            sets[key] = len(blocks)
+            blocks.append(block)
+        scans[at:at + i["scan_bytes"]] = np.frombuffer(f, dtype=np.uint8, count=i["scan_bytes"], offset=i["scan_offset"])
+        off = out_at if out_offsets is None else int(out_offsets[b])
+        rec[b] = _lib.JpegDecodeSample(at, off, i["scan_bytes"], i["h"], i["w"], i["ncomp"], i["hs"], i["vs"], sets[key], 0)
+        at += i["scan_bytes"]
+        out_at += i["h"] * i["w"] * 3
+    return dict(scans=holder if pinned else scans, scan_bytes=total, records=np.frombuffer(bytes(rec), dtype=np.uint8).copy(),
+                tables=np.concatenate(blocks), n_sets=len(blocks), B=len(files), shapes=[(i["h"], i["w"]) for i in infos], out_bytes=out_at,
+                max_h=max(i["h"] for i in infos), max_w=max(i["w"] for i in infos), max_scan=max(i["scan_bytes"] for i in infos))
+
+
+def jpeg_decode_packed(pack, out=None, out_bytes=None, subseq_bits=None, max_rounds=None, status=None, device="cuda", want_info=False):
+    """device half: uploads the scans, records and table blocks of `pack` (jpeg_decode_pack) and decodes into `out` (uint8 device buffer,
+    default: one of pack["out_bytes"]; out_bytes: how much of it may be written), the packed layout resize_u8_packed, vis_overlay_device
+    and jpeg_encode_packed read -> (out, shapes, status): status int32 device [B + 1], per sample and their maximum: 0 decoded, 1 record
+    turned down, 2 not settled within max_rounds launches, 3 corrupt stream; a sample with a non-zero status wrote nothing.  Does not
+    wait for the device.  want_info=True appends the kernels' counters, int32 device [B, 8] (include/footprints_hip.h)."""
+    lib = _lib.load()
+    B = pack["B"]
+    subseq_bits = JPEG_DECODE_SUBSEQ_BITS if subseq_bits is None else int(subseq_bits)
+    max_rounds = JPEG_DECODE_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    scans = pack["scans"] if torch.is_tensor(pack["scans"]) else torch.from_numpy(pack["scans"])
+    d_scans = scans.to(device, non_blocking=True)
+    d_rec = torch.from_numpy(pack["records"]).to(device)
+    d_tab = torch.from_numpy(pack["tables"].view("int32")).to(device)
+    if out is None:
+        out = torch.empty(pack["out_bytes"], dtype=torch.uint8, device=d_scans.device)
+    out_bytes = out.numel() if out_bytes is None else int(out_bytes)
+    if status is None:
+        status = torch.empty(B + 1, dtype=torch.int32, device=d_scans.device)
+    if out.dtype != torch.uint8 or out.numel() < out_bytes or status.dtype != torch.int32 or status.numel() < B + 1:
+        raise RuntimeError("footprints_amd.ops.jpeg_decode_packed: out must be uint8 of at least out_bytes and status int32 [B + 1]")
+    need = lib.fp_jpeg_decode_workspace_bytes(B, pack["max_h"], pack["max_w"], pack["max_scan"], subseq_bits)
+    if need < 0:
+        raise RuntimeError("footprints_amd.ops.jpeg_decode_packed: bad sizes, or too large")
+    ws = workspace(need, d_scans.device, "jpeg_decode")
+    _lib.check(lib.fp_jpeg_decode(_chk(d_scans, "scans"), int(pack["scan_bytes"]), _chk(d_rec, "samples"), _chk(d_tab, "tables"), pack["n_sets"],
+                                  _chk(out, "out"), out_bytes, _chk(status, "status"), B, pack["max_h"], pack["max_w"], pack["max_scan"],
+                                  subseq_bits, max_rounds, ws.data_ptr(), ws.numel(), stream()), "fp_jpeg_decode")
+    if want_info:
+        return out, pack["shapes"], status, ws[:B * 32].view(torch.int32).view(B, 8).clone()
+    return out, pack["shapes"], status
+
+
+def _jpeg_host_decode(data):
+    import io
+    import numpy as np
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)
+
+
+def jpeg_decode(files, subseq_bits=None, max_rounds=None, return_status=False):
+    """`np.asarray(PIL.Image.open(f).convert("RGB"))` of a list of files (bytes), byte for byte: the files jpeg_parse accepts are decoded
+    on the device in one call, the others by Pillow on the host -- and so is a file the device turned down (status 1), did not settle
+    within max_rounds (2) or found corrupt (3): then whatever Pillow returns or raises is the result.  WAITS for the device.
+    return_status=True -> (arrays, statuses): the device's status per file, -1 for a file the parser sent to the host."""
+    files = [bytes(f) for f in files]
+    infos = [jpeg_parse(f) for f in files]
+    on_device = [n for n, i in enumerate(infos) if i["device"]]
+    arrays, statuses = [None] * len(files), [-1] * len(files)
+    if on_device:
+        pack = jpeg_decode_pack([files[n] for n in on_device], [infos[n] for n in on_device])
+        out, shapes, status = jpeg_decode_packed(pack, subseq_bits=subseq_bits, max_rounds=max_rounds)
+        status = status.cpu().numpy()               # waits
+        host = out.cpu().numpy() if int(status[-1]) == 0 or (status[:-1] == 0).any() else None
+        at = 0
+        for j, n in enumerate(on_device):
+            h, w = shapes[j]
+            statuses[n] = int(status[j])
+            if statuses[n] == 0:
+                arrays[n] = host[at:at + h * w * 3].reshape(h, w, 3).copy()
+            at += h * w * 3
+    for n, f in enumerate(files):
+        if arrays[n] is None:
+            arrays[n] = _jpeg_host_decode(f)
+    return (arrays, statuses) if return_status else arrays
+
+
+def resize_records(shapes, H, W, tables, filter="lanczos"):
+    """resize_pack's records for pictures of `shapes` = [(h, w), ...] (three channels) that lie one after the other in a packed buffer
+    already -> (records uint8 numpy, bytes of the buffer, max_h, max_w)"""
+    import numpy as np
+    rec = (_lib.ResizeSample * len(shapes))()
+    off = 0
+    for b, (h, w) in enumerate(shapes):
+        rec[b] = _lib.ResizeSample(off, h, w, tables.index(w, W, filter), tables.index(h, H, filter))
+        off += h * w * 3
+    return np.frombuffer(bytes(rec), dtype=np.uint8).copy(), off, max(s[0] for s in shapes), max(s[1] for s in shapes)

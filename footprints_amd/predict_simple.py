@@ -16,7 +16,10 @@ as it is -- gives for the same prediction: Pillow's mode-"F" BILINEAR restated, 
 on the host unless `--device_jpeg` (needs --device_vis) is given too: then a group's overlays stay on the device, are encoded there
 (csrc/jpeg.hip) and the .jpg files are written from the returned bytes -- the files Pillow writes, byte for byte.  `--batch_size N` predicts a folder N files at a time, in sorted order: one forward pass, one copy of the predictions and
 (with --device_vis) one overlay call and one copy of the overlays per group; the photos of a group may differ in size, and the same
-files are written under the same names.  A batched forward pass differs from per-image passes at fp32 round-off -- the small
+files are written under the same names.  `--device_decode` (needs --device_resize) reads the files' bytes and decodes the baseline
+JPEGs among them on the GPU (csrc/jpeg_decode.hip), straight into the packed buffer the resize and the overlay share -- the bytes Pillow
+decodes; every other file (PNG, progressive JPEG, ...) is decoded by Pillow and copied into the same buffer.  A batched forward pass
+differs from per-image passes at fp32 round-off -- the small
 convolutions split their K loop by a rule that depends on the batch size -- so a .npy of a batched run is within the contract's 1e-4 of
 its channel maximum of the per-image one, not bit-equal; every overlay still equals `visualise` of its own .npy.
 """
@@ -29,6 +32,18 @@ from PIL import Image
 
 from .model_manager import ModelManager
 from .utils import MODEL_DIR, model_folder, pil_loader, sigmoid_to_depth
+
+class _LazyOriginals:
+    """the photos of a group that were decoded into a device buffer: one is copied back only when the host path asks for it"""
+
+    def __init__(self, packed, shapes):
+        self.packed, self.shapes = packed, shapes
+
+    def __getitem__(self, n):
+        at = sum(h * w * 3 for h, w in self.shapes[:n])
+        h, w = self.shapes[n]
+        return Image.fromarray(self.packed[at:at + h * w * 3].cpu().numpy().reshape(h, w, 3))
+
 
 MODEL_HEIGHT_WIDTH = {"kitti": (192, 640), "matterport": (512, 640), "handheld": (256, 448)}   # predict_simple.py:21-25
 IMAGE_EXTENSIONS = {".jpg", ".jpeg", ".png"}
@@ -49,7 +64,7 @@ def preprocess(pil_image, height_width, device_resize=False):
 
 class InferenceManager:
     def __init__(self, model_name, save_dir, use_cuda=True, save_visualisations=True, weights_path=None, model_manager=None,
-                 device_resize=False, device_vis=False, batch_size=1, device_jpeg=False):
+                 device_resize=False, device_vis=False, batch_size=1, device_jpeg=False, device_decode=False):
         if not use_cuda or not torch.cuda.is_available():
             raise RuntimeError("footprints_amd.predict_simple needs a MI355X: the package has no CPU compute path "
                                "(--no_cuda is accepted for CLI compatibility only)")
@@ -68,6 +83,9 @@ class InferenceManager:
         self.device_jpeg = bool(device_jpeg)
         if self.device_jpeg and not self.device_vis:
             raise ValueError("device_jpeg encodes the overlays where device_vis draws them: it needs device_vis")
+        self.device_decode = bool(device_decode)
+        if self.device_decode and not self.device_resize:
+            raise ValueError("device_decode decodes into the buffer device_resize reads: it needs device_resize")
         self.overlay_hook = None       # callable(file stem, uint8 [h, w, 3]): sees every overlay before it is encoded
         self.save_dir = save_dir
         os.makedirs(os.path.join(save_dir, "outputs"), exist_ok=True)
@@ -82,7 +100,7 @@ class InferenceManager:
         return pred["1/1"].cpu().numpy().squeeze(0)          # [4,H,W]
 
     def predict_for_single_image(self, image_path):
-        if self.device_vis:
+        if self.device_vis or self.device_decode:
             return self.predict_for_images([image_path])[0]
         print("Predicting for {}".format(image_path))
         original = pil_loader(image_path)
@@ -111,12 +129,18 @@ class InferenceManager:
         """one group of files in ONE forward pass: the same artefacts as predict_for_single_image on each; returns [B,4,H,W].
         With device_resize the decoded photos are uploaded once, for the resize and for the overlay."""
         from . import ops
-        originals = [pil_loader(p) for p in image_paths]
         for p in image_paths:
             print("Predicting for {}".format(p))
         h, w = self.height_width
         packed = None
-        if self.device_resize:
+        originals = None if self.device_decode else [pil_loader(p) for p in image_paths]
+        if self.device_decode:
+            packed, total, shapes = self._decode_packed(image_paths)
+            originals = _LazyOriginals(packed, shapes)
+            tables = ops.resize_table_set("cuda")
+            records, _, max_h, max_w = ops.resize_records(shapes, h, w, tables)
+            x = ops.to_tensor_u8(ops.resize_u8_packed(packed, total, torch.from_numpy(records).cuda(), len(shapes), h, w, 3, max_h, max_w, tables))
+        elif self.device_resize:
             arrays = [np.asarray(o, dtype=np.uint8) for o in originals]
             tables = ops.resize_table_set("cuda")
             host, records, total, cn, max_h, max_w = ops.resize_pack(arrays, h, w, tables)
@@ -129,7 +153,7 @@ class InferenceManager:
         preds = pred_dev.cpu().numpy()                           # [B,4,H,W]: one copy for the group
         overlays, files = None, None
         if self.save_visualisations and self.device_vis:
-            shapes = [(o.size[1], o.size[0]) for o in originals]
+            shapes = originals.shapes if self.device_decode else [(o.size[1], o.size[0]) for o in originals]
             source = dict(packed=packed, shapes=shapes) if packed is not None else dict(originals=[np.asarray(o, dtype=np.uint8) for o in originals])
             if self.device_jpeg:
                 files, overlays = self._encode_overlays(*ops.vis_overlay_device(pred_dev, **source))
@@ -145,6 +169,32 @@ class InferenceManager:
             elif self.save_visualisations:
                 self._save_visualisation(filename, overlays[i] if overlays is not None else self.visualise(preds[i], originals[i]))
         return preds
+
+    def _decode_packed(self, image_paths):
+        """the photos of a group, decoded into one device buffer, one after the other -> (buffer, bytes, shapes): baseline JPEGs on the
+        device from the files' bytes, everything else -- and a JPEG the device did not take -- by Pillow"""
+        import io
+        from . import ops
+        files = []
+        for p in image_paths:
+            with open(p, "rb") as fh:
+                files.append(fh.read())
+        infos = [ops.jpeg_parse(f) for f in files]
+        decoded = {n: np.asarray(Image.open(io.BytesIO(f)).convert("RGB"), dtype=np.uint8) for n, (f, i) in enumerate(zip(files, infos))
+                   if not i["device"]}
+        shapes = [(i["h"], i["w"]) if i["device"] else decoded[n].shape[:2] for n, i in enumerate(infos)]
+        offsets = np.concatenate([[0], np.cumsum([sh[0] * sh[1] * 3 for sh in shapes])])
+        packed = torch.empty(int(offsets[-1]), dtype=torch.uint8, device="cuda")
+        on_device = [n for n, i in enumerate(infos) if i["device"]]
+        if on_device:
+            pack = ops.jpeg_decode_pack([files[n] for n in on_device], [infos[n] for n in on_device], [offsets[n] for n in on_device])
+            status = ops.jpeg_decode_packed(pack, out=packed)[2].cpu().numpy()          # waits
+            for j, n in enumerate(on_device):
+                if status[j] != 0:
+                    decoded[n] = np.asarray(Image.open(io.BytesIO(files[n])).convert("RGB"), dtype=np.uint8)
+        for n, arr in decoded.items():
+            packed[int(offsets[n]):int(offsets[n + 1])] = torch.from_numpy(np.array(arr, dtype=np.uint8).reshape(-1)).cuda()
+        return packed, int(offsets[-1]), shapes
 
     def _encode_overlays(self, buffer, total, shapes):
         """the overlays of a group, lying in a device buffer -> (their .jpg files' bytes, the raw overlays for the hook or None)"""
@@ -212,7 +262,11 @@ def parse_args(argv=None):
     ap.add_argument("--device_vis", action="store_true", help="draw the overlays on the GPU (same bytes as the host path before the JPEG encoder)")
     ap.add_argument("--batch_size", type=int, default=1, help="files of a folder per forward pass (sorted order; sizes may differ)")
     ap.add_argument("--device_jpeg", action="store_true", help="with --device_vis: encode the overlays on the GPU too (the same .jpg files)")
+    ap.add_argument("--device_decode", action="store_true",
+                    help="with --device_resize: decode baseline JPEG files on the GPU too (the same pixels; other files by Pillow)")
     args = ap.parse_args(argv)
+    if args.device_decode and not args.device_resize:
+        ap.error("--device_decode needs --device_resize: it decodes into the buffer the resize reads")
     if args.device_jpeg and not args.device_vis:
         ap.error("--device_jpeg needs --device_vis: it encodes the overlays where they are drawn")
     return args
@@ -223,7 +277,7 @@ def main(argv=None):
     manager = InferenceManager(model_name=args.model, use_cuda=torch.cuda.is_available() and not args.no_cuda,
                                save_visualisations=not args.no_save_vis, save_dir=args.save_dir, weights_path=args.weights,
                                device_resize=args.device_resize, device_vis=args.device_vis, batch_size=args.batch_size,
-                               device_jpeg=args.device_jpeg)
+                               device_jpeg=args.device_jpeg, device_decode=args.device_decode)
     manager.predict(image_path=args.image)
 
 

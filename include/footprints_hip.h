@@ -670,6 +670,36 @@ int64_t fp_jpeg_max_scan_bytes(int32_t B, int32_t max_h, int32_t max_w);
 int fp_jpeg_encode(const uint8_t* src, int64_t src_bytes, const void* samples, const uint32_t* tables, uint8_t* out, int64_t out_bytes,
                    int64_t* table, int32_t B, int32_t max_h, int32_t max_w, void* workspace, int64_t workspace_bytes, fp_stream_t stream);
 
+/* ---- baseline JPEG decoder (csrc/jpeg_decode.hip): PIL.Image.open(f).convert("RGB") of a baseline file, byte for byte ---- */
+typedef struct fp_jpeg_decode_sample {
+  int64_t scan_offset; /* of the entropy-coded segment (behind the SOS header, up to the EOI marker) in the scans buffer */
+  int64_t out_offset;  /* of the picture's first byte in the output; dense uint8 [h][w][3] */
+  int32_t scan_bytes;  /* of the segment, stuffed zero bytes included */
+  int32_t h, w;
+  int32_t ncomp;       /* 1: grey (the value three times), 3: YCbCr */
+  int32_t hs, vs;      /* luma sampling factors: 1x1, 2x1 or 2x2; the chroma components are 1x1 */
+  int32_t table_set;   /* index of the table block */
+  int32_t reserved;
+} fp_jpeg_decode_sample;
+int32_t fp_jpeg_decode_sample_bytes(void);
+/* words of one table block (uint32): [3][4] per component the quantisation table, the DC and the AC Huffman table it uses; at 16 [4][64]
+ * quantisation values in natural order; at 272 four Huffman tables (DC 0, DC 1, AC 0, AC 1) of 356 words: [256] length << 8 | symbol of
+ * the code 8 bits begin with (0: longer), [18] maxcode per length (-1: none), [18] valptr - mincode per length, [64] the symbols, four
+ * to a word.  Built by the caller from the file's own DQT / DHT segments; nothing of a table is compiled in. */
+int32_t fp_jpeg_decode_table_words(void);
+int64_t fp_jpeg_decode_workspace_bytes(int32_t B, int32_t max_h, int32_t max_w, int32_t max_scan_bytes, int32_t subseq_bits);
+/* Decodes B baseline scans (SOF0, 8 bits, one interleaved scan, no restart markers) into `out`, the packed layout fp_resize_u8,
+ * fp_vis_overlay and fp_jpeg_encode read.  samples: B records on the device; tables: n_table_sets table blocks on the device.  A scan is
+ * cut into subsequences of subseq_bits bits (32..2^20), one thread each, whose entry states are iterated to the serial decode's; the
+ * synchronisation kernel is launched max_rounds times (64 hops inside each launch; a launch is a no-op for a settled sample).
+ * status: int32 [B + 1] on the device, one per sample and their maximum: 0 decoded; 1 record turned down (sizes, an offset outside a
+ * buffer, an unknown table set, an output that does not fit); 2 not settled within max_rounds; 3 corrupt stream.  A sample with a
+ * non-zero status writes nothing into out.  The workspace begins with int32 [B][8] per sample: destuffed bytes, 1 + the last launch that
+ * moved an entry state (so the launches the sample needed), the most hops of a launch, blocks found.  Does not wait for the device. */
+int fp_jpeg_decode(const uint8_t* scans, int64_t scan_bytes, const void* samples, const uint32_t* tables, int32_t n_table_sets, uint8_t* out,
+                   int64_t out_bytes, int32_t* status, int32_t B, int32_t max_h, int32_t max_w, int32_t max_scan_bytes, int32_t subseq_bits,
+                   int32_t max_rounds, void* workspace, int64_t workspace_bytes, fp_stream_t stream);
+
 /* ---- pyramid pooling of the ground-segmentation network (footprints/preprocessing/segmentation/network.py:174-207) ---- */
 /* nn.AdaptiveAvgPool2d(P) (network.py:180,188): y[N][P][P][C] = window means of x[N][H][W][C]; windows floor(i*H/P) .. ceil((i+1)*H/P) */
 int fp_adaptive_avgpool_fwd(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t P, fp_stream_t stream);
