@@ -4,6 +4,7 @@
 #include <hip/hip_fp16.h>
 
 #include "fp_common.h"
+#include "infer_out.h"
 
 namespace {
 
@@ -365,10 +366,7 @@ extern "C" int fp_scale_rows(const float* w, const float* scale, float* out, int
 __global__ void __launch_bounds__(256) pack_pred_fp16_kernel(const float* __restrict__ pred, __half* __restrict__ out, size_t plane,
                                                              size_t total) {
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-    const int c = (int)((e / plane) & 3);
-    float v = pred[e];
-    if (c < 2) v = 1.f / (1.f + expf(-v));
-    out[e] = __float2half_rn(v);
+    out[e] = fp_pred_half(pred[e], (int)((e / plane) & 3));
   }
 }
 

@@ -19,6 +19,7 @@
 #include <hip/hip_fp16.h>
 
 #include "fp_common.h"
+#include "infer_out.h"      // fp_pack12 / fp_store12: 4 pixels -> the 12 bytes of an [..][3] row
 
 namespace {
 
@@ -45,30 +46,6 @@ __device__ __forceinline__ float sigmoid_exact(float x) {
 __device__ __forceinline__ unsigned int image_byte(float v) {
   const float c = fminf(fmaxf(v, 0.0f), 1.0f);      // a NaN gives 0
   return (unsigned int)(int)((double)c * 255.0);
-}
-
-// 4 pixels of 24 bits (r | g << 8 | b << 16) -> the 12 bytes they take in an [..][3] byte row
-__device__ __forceinline__ void pack12(const unsigned int c[4], unsigned int d[3]) {
-  d[0] = c[0] | (c[1] << 24);
-  d[1] = (c[1] >> 8) | (c[2] << 16);
-  d[2] = (c[2] >> 16) | (c[3] << 8);
-}
-
-__device__ __forceinline__ void store12(unsigned char* at, const unsigned int c[4], int n, bool vec) {
-  if (vec) {
-    unsigned int d[3];
-    pack12(c, d);
-    unsigned int* o = reinterpret_cast<unsigned int*>(at);
-    o[0] = d[0];
-    o[1] = d[1];
-    o[2] = d[2];
-  } else {
-    for (int j = 0; j < n; ++j) {
-      at[3 * j + 0] = (unsigned char)(c[j]);
-      at[3 * j + 1] = (unsigned char)(c[j] >> 8);
-      at[3 * j + 2] = (unsigned char)(c[j] >> 16);
-    }
-  }
 }
 
 // grid = (ceil(H * quads / 256), B)
@@ -137,8 +114,8 @@ __global__ void __launch_bounds__(256) seg_pack_kernel(const SegPackArgs a) {
     right[j] = colours[min(max(idx, 0), 255)];      // p is in [0, 1] (NaN logits convert to some index): never a read outside the table
   }
   unsigned char* row = a.picture + ((int64_t)b * a.H + y) * ((int64_t)a.W * 6);
-  store12(row + (int64_t)x0 * 3, left, n, (a.vec & SP_VEC_PICTURE) != 0);
-  store12(row + ((int64_t)a.W + x0) * 3, right, n, (a.vec & SP_VEC_PICTURE) != 0);
+  fp_store12(row + (int64_t)x0 * 3, left, n, (a.vec & SP_VEC_PICTURE) != 0);
+  fp_store12(row + ((int64_t)a.W + x0) * 3, right, n, (a.vec & SP_VEC_PICTURE) != 0);
 }
 
 }  // namespace

@@ -17,6 +17,7 @@
 //     sigmoid(logit) > 0.5 in fp32; that is the same predicate except for the positive logits so small (below about 1.2e-7) that the fp32
 //     sigmoid rounds to exactly 0.5, which the reference paints with colour 0 and this kernel with colour 1.
 #include "fp_common.h"
+#include "infer_out.h"
 
 namespace {
 
@@ -289,11 +290,8 @@ __global__ void __launch_bounds__(256) vis_side_by_side_kernel(const float* __re
   const size_t hw = (size_t)H * W, at = (size_t)y * W + x;
   unsigned char* row = out + ((size_t)b * H + y) * 2 * W * 3;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float v = image[((size_t)b * 3 + c) * hw + at] * 255.0f;
-    row[x * 3 + c] = (unsigned char)min(max((int)v, 0), 255);
-  }
-  const unsigned int col = pred[((size_t)b * 4 + 1) * hw + at] > 0.0f ? colour1 : colour0;
+  for (int c = 0; c < 3; ++c) row[x * 3 + c] = (unsigned char)fp_sbs_image_byte(image[((size_t)b * 3 + c) * hw + at]);
+  const unsigned int col = fp_sbs_colour(pred[((size_t)b * 4 + 1) * hw + at], colour0, colour1);
 #pragma unroll
   for (int c = 0; c < 3; ++c) row[(W + x) * 3 + c] = (unsigned char)(col >> (8 * c));
 }

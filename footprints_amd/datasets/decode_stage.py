@@ -1,0 +1,226 @@
+"""JPEG decoding for the inference pipelines, one batch ahead of the network.
+
+ops.jpeg_decode waits for the device's status before it returns, which is right for one call and wrong inside a pipeline whose calling
+thread never waits.  `DecodeStage` splits the call in two around a batch:
+
+  reader threads  `read_sample(path, device_decode)`: the file's bytes and ops.jpeg_parse.  A file the parser refuses (PNG, progressive,
+                  restart markers, ...) is decoded by Pillow at once, on that thread; for the others nothing is decoded on the host.
+  queue(s, samples)   lays the batch out in the slot's packed source buffer -- dense [h][w][3], one picture after the other, with the
+                  fp_resize_sample records ops.resize_pack writes; the sizes come from the headers -- copies the host-decoded frames into
+                  the pinned buffer at their offsets, queues their upload, the uploads of the scans and ops.jpeg_decode_packed into the
+                  same device buffer, a copy of the status into pinned memory, and records an event.  Waits for nothing.
+  finish(s)       waits for that event, decodes every sample whose status is not 0 with Pillow and uploads it to the sample's offset
+                  (whatever Pillow raises ends the run, with the file's path in the message), and returns what ops.resize_u8_packed needs.
+
+A pipeline calls queue(k + 1) before finish(k) and queues the rest of batch k after it, so the only device wait of the calling thread is
+for decode work queued a whole network pass earlier; with every status 0 the host decodes nothing.  Counters: `device` (decoded by the
+device), `host_parser` (refused by the parser), `host_status` (decoded again after a non-zero status)."""
+import ctypes as C
+import io
+import time
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+
+MAX_ROW_BYTES = 65528           # the resize stages one source row: max_w * 3 bytes (fp_resize_u8)
+
+
+def host_decode(data):
+    """`np.asarray(Image.open(f).convert("RGB"))` of a file's bytes: the decoder of every host reader of this package"""
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+def read_sample(path, device_decode, decode=host_decode):
+    """a reader thread's work for one file -> {'path', 'image': uint8 [h, w, 3]} (decoded on the host; 'refused': the parser's reason
+    when device decoding was asked for) or {'path', 'bytes', 'info'} (for the device)"""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if device_decode:
+        info = ops.jpeg_parse(data)
+        if info["device"]:
+            return {"path": path, "bytes": data, "info": info}
+        return {"path": path, "image": _decode_named(decode, data, path), "refused": info["reason"]}
+    return {"path": path, "image": _decode_named(decode, data, path)}
+
+
+def _decode_named(decode, data, path):
+    """decode(data); whatever it raises is raised again with the file's path in front of its message"""
+    try:
+        return decode(data)
+    except Exception as exc:
+        try:
+            named = type(exc)("%s: %s" % (path, exc))
+        except Exception:                                   # an exception class that does not take one string
+            named = RuntimeError("%s: %r" % (path, exc))
+        raise named from exc
+
+
+class DecodeStage:
+
+    SPIN = 0.0002               # seconds between two queries of the event
+
+    def __init__(self, batch_size, H, W, tables, device, decode=host_decode, stop=None):
+        """tables: the device's ops.resize_table_set; decode: bytes -> uint8 [h, w, 3] (Pillow; tests inject a recording one); stop: a
+        threading.Event the wait in `finish` looks at"""
+        self.batch_size, self.H, self.W = int(batch_size), int(H), int(W)
+        self.tables, self.device, self.decode, self.stop = tables, device, decode, stop
+        self.counters = dict(device=0, host_parser=0, host_status=0)
+
+    # ---- the slot's buffers -------------------------------------------------------------------------------------------------------------
+    def new_slot(self, s=None):
+        """the stage's part of a ring slot (a dict; a pipeline's own slot may be passed and gains the keys it lacks)"""
+        s = {} if s is None else s
+        rec_bytes = self.batch_size * C.sizeof(_lib.ResizeSample)
+        s.setdefault("src_cap", 0)
+        s.setdefault("h_src", None)
+        s.setdefault("d_src", None)
+        if "h_rec" not in s:
+            s["h_rec"] = self._pinned(rec_bytes, torch.uint8)
+            s["d_rec"] = self._empty(rec_bytes, torch.uint8)
+        s["h_status"] = self._pinned(self.batch_size + 1, torch.int32)
+        s["d_status"] = self._empty(self.batch_size + 1, torch.int32)
+        s["decoded"] = self._event()
+        s["batch"] = None
+        return s
+
+    def _pinned(self, n, dtype):
+        return torch.empty(n, dtype=dtype).pin_memory()
+
+    def _empty(self, n, dtype):
+        return torch.empty(n, dtype=dtype, device=self.device)
+
+    def _event(self):
+        return torch.cuda.Event()
+
+    def reserve(self, s, nbytes):
+        """the packed source buffers grow when a batch needs more than they hold (the slot's previous batch has left the device)"""
+        if nbytes > s["src_cap"]:
+            ops.release(s["d_src"], "decode_stage:src")
+            s["src_cap"] = nbytes + nbytes // 8
+            s["h_src"] = self._pinned(s["src_cap"], torch.uint8)
+            s["d_src"] = self._empty(s["src_cap"], torch.uint8)
+
+    # ---- host half ----------------------------------------------------------------------------------------------------------------------
+    def layout(self, samples):
+        """-> (shapes [(h, w)], offsets, total bytes, max_h, max_w) of the batch in the packed buffer, from the frames and the headers"""
+        n = len(samples)
+        if not 1 <= n <= self.batch_size:
+            raise ValueError("a batch holds 1 to %d frames" % self.batch_size)
+        shapes = []
+        for smp in samples:
+            if "image" in smp:
+                im = smp["image"]
+                if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+                    raise ValueError("%s: frames must be decoded RGB images, uint8 [h, w, 3]" % smp.get("path", "a sample"))
+                shapes.append((int(im.shape[0]), int(im.shape[1])))
+            else:
+                shapes.append((int(smp["info"]["h"]), int(smp["info"]["w"])))
+            if shapes[-1][1] * 3 > MAX_ROW_BYTES:
+                raise ValueError("%s: a frame of %d columns is wider than the resize's row buffer (%d bytes)"
+                                 % (smp.get("path", "a sample"), shapes[-1][1], MAX_ROW_BYTES))
+        offsets, at = [], 0
+        for h, w in shapes:
+            offsets.append(at)
+            at += h * w * 3
+        return shapes, offsets, at, max(h for h, _ in shapes), max(w for _, w in shapes)
+
+    def fill(self, s, samples):
+        """records and host-decoded frames into the slot's pinned buffers -> the batch's description (kept in s['batch'])"""
+        shapes, offsets, total, max_h, max_w = self.layout(samples)
+        self.reserve(s, total)
+        rec = (_lib.ResizeSample * len(samples))()
+        src = s["h_src"].numpy()
+        on_host, on_device = [], []
+        for b, (smp, (h, w), off) in enumerate(zip(samples, shapes, offsets)):
+            rec[b] = _lib.ResizeSample(off, h, w, self.tables.index(w, self.W, "lanczos"), self.tables.index(h, self.H, "lanczos"))
+            if "image" in smp:
+                src[off:off + h * w * 3] = smp["image"].reshape(-1)
+                on_host.append(b)
+                if "refused" in smp:
+                    self.counters["host_parser"] += 1
+            else:
+                on_device.append(b)
+        raw = np.frombuffer(bytes(rec), dtype=np.uint8)
+        s["h_rec"].numpy()[:raw.size] = raw
+        s["batch"] = dict(n=len(samples), samples=samples, shapes=shapes, offsets=offsets, total=total, max_h=max_h, max_w=max_w,
+                          on_host=on_host, on_device=on_device)
+        return s["batch"]
+
+    def pack(self, batch):
+        """ops.jpeg_decode_pack of the batch's device samples, every array in pinned memory, or None"""
+        idx = batch["on_device"]
+        if not idx:
+            return None
+        smp = batch["samples"]
+        pack = ops.jpeg_decode_pack([smp[b]["bytes"] for b in idx], [smp[b]["info"] for b in idx],
+                                    out_offsets=[batch["offsets"][b] for b in idx])
+        for key, np_type, dtype in (("scans", np.uint8, torch.uint8), ("records", np.uint8, torch.uint8), ("tables", np.int32, torch.int32)):
+            host = self._pinned(pack[key].size, dtype)
+            host.numpy()[:] = pack[key].view(np_type)
+            pack[key] = host
+        return pack
+
+    # ---- device half --------------------------------------------------------------------------------------------------------------------
+    def queue(self, s, samples):
+        """queue a batch's uploads and its decode on the current stream; waits for nothing"""
+        batch = self.fill(s, samples)
+        pack = self.pack(batch)
+        self._upload_records(s)
+        for b in batch["on_host"]:
+            self._upload(s, batch["offsets"][b], batch["shapes"][b])
+        if pack is not None:
+            self._decode(s, pack, batch)
+        s["decoded"].record()
+
+    def _upload_records(self, s):
+        s["d_rec"].copy_(s["h_rec"], non_blocking=True)
+
+    def _upload(self, s, off, shape):
+        nbytes = shape[0] * shape[1] * 3
+        s["d_src"][off:off + nbytes].copy_(s["h_src"][off:off + nbytes], non_blocking=True)
+
+    def _decode(self, s, pack, batch):
+        nd = len(batch["on_device"])
+        ops.jpeg_decode_packed(pack, out=s["d_src"], out_bytes=batch["total"], status=s["d_status"][:nd + 1], device=self.device)
+        s["h_status"][:nd + 1].copy_(s["d_status"][:nd + 1], non_blocking=True)
+
+    def _wait(self, s):
+        while not s["decoded"].query():
+            if self.stop is not None and self.stop.is_set():
+                raise RuntimeError("the inference pipeline was stopped while a batch was being decoded")
+            time.sleep(self.SPIN)
+
+    def _status(self, s, nd):
+        return s["h_status"].numpy()[:nd].copy()
+
+    def finish(self, s):
+        """wait for the batch's decode; Pillow decodes what the device turned down -> dict(src, total, records, n, max_h, max_w, status):
+        the arguments of ops.resize_u8_packed, and the device's status per sample (-1: decoded on the host from the start)"""
+        batch = s["batch"]
+        if batch is None:
+            raise RuntimeError("DecodeStage.finish: no batch was queued on this slot")
+        s["batch"] = None
+        if batch["on_device"]:                              # nothing to wait for when the host decoded every frame
+            self._wait(s)
+        status = [-1] * batch["n"]
+        device_status = self._status(s, len(batch["on_device"])) if batch["on_device"] else []
+        for b, st in zip(batch["on_device"], device_status):
+            status[b] = int(st)
+            smp = batch["samples"][b]
+            if status[b] == 0:
+                self.counters["device"] += 1
+                continue
+            frame = _decode_named(self.decode, smp["bytes"], smp.get("path", "sample %d" % b))
+            h, w = batch["shapes"][b]
+            if frame.shape != (h, w, 3):
+                raise ValueError("%s: the header says %d x %d, Pillow decoded %r" % (smp.get("path", "sample %d" % b), h, w, frame.shape))
+            off = batch["offsets"][b]
+            s["h_src"].numpy()[off:off + h * w * 3] = frame.reshape(-1)
+            self._upload(s, off, (h, w))
+            self.counters["host_status"] += 1
+        return dict(src=s["d_src"], total=batch["total"], records=s["d_rec"], n=batch["n"], max_h=batch["max_h"], max_w=batch["max_w"],
+                    status=status)

@@ -2,14 +2,41 @@
 
 The KITTI / Matterport dataset readers are outside this build's scope: training runs over any
 iterable of batches with the reference schema; with `--synthetic_steps N` it runs over the synthetic loader the benchmark
-uses.  Inference mode needs a loader of {'image', 'idx'} batches and is therefore only reachable programmatically
-(`footprints_amd.evaluation.inference.InferenceManager(...).run(loader)`)."""
+uses.  `--mode inference` is the reference's test-set program (footprints/evaluation/inference.py:31-96): the test split of
+`--inference_data_type` through the network, one .npy (and with --save_test_visualisations one .jpg) per frame -- the input of
+`evaluation/evaluate_model.py --predictions`."""
 from .options import Options
 from .parallel import DistContext
 from .training.train import SyntheticLoader, TrainManager
 
 
-def main(argv=None):
+def run_inference(opt, model_manager=None):
+    """the reference's InferenceManager.__init__ + create_dataloaders + run (evaluation/inference.py:36-96): the config file's
+    [inference_data_type]['dataset'], splits/<type>/test.txt relative to the working directory, and the save path --inference_save_path
+    or <load_path>/<type>_predictions"""
+    import os
+    import yaml
+    from .datasets.inference import get_inference_dataset_class
+    from .evaluation.inference import InferenceManager
+    print("In inference mode!")
+    with open(opt.config_path) as fh:
+        raw_data_path = yaml.safe_load(fh)[opt.inference_data_type]["dataset"]
+    with open(os.path.join("splits", opt.inference_data_type, "test.txt")) as fh:
+        test_files = fh.read().splitlines()
+    save_path = opt.inference_save_path
+    if save_path is None:
+        save_path = os.path.join(opt.load_path, "{}_predictions".format(opt.inference_data_type))
+    print("saving output to {}".format(save_path))
+    dataset = get_inference_dataset_class(opt.inference_data_type)(raw_data_path, test_files, opt.height, opt.width)
+    manager = InferenceManager(load_path=opt.load_path, model_manager=model_manager, save_path=save_path,
+                               save_test_visualisations=opt.save_test_visualisations, device_jpeg=getattr(opt, "device_jpeg", False))
+    print("running inference...")
+    counters = manager.run_dataset(dataset, opt.batch_size, num_workers=opt.num_workers, device_decode=getattr(opt, "device_decode", False))
+    print("finished testing!")
+    return manager, counters
+
+
+def main(argv=None, model_manager=None):
     opt = Options().parse(argv)
     if opt.mode == "train":
         # FIRST thing under a launcher (ADVICE r4): select this rank's GPU (LOCAL_RANK) and join the host group before ANY loader, assembler,
@@ -33,7 +60,7 @@ def main(argv=None):
         # per-GPU batch, --synthetic_steps the number of GLOBAL batches per epoch (each rank trains on every world-th one)
         TrainManager(opt, train_loader=train, val_loader=val, dist_context=ctx).train()
     elif opt.mode == "inference":
-        raise SystemExit("inference mode needs a dataset loader: use footprints_amd.evaluation.inference.InferenceManager")
+        return run_inference(opt, model_manager)[1]
     else:
         raise NotImplementedError
 

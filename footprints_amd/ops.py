@@ -1562,6 +1562,39 @@ def seg_pack(logits, image=None, want_f32=False, want_picture=False, out=None):
     return half, f32, picture
 
 
+# ---- output stage of the main network's test-set inference (csrc/infer_pack.hip) -------------------------------------------------------------
+def infer_pack(pred, image=None, want_picture=False, out=None):
+    """pack_pred_fp16 and vis_side_by_side in one launch over the logits: pred float32 [B, 4, H, W]; image float32 [B, 3, H, W] in
+    [0, 1], needed for the picture.  out = (half, picture): buffers to write into, each None or a contiguous tensor of the right shape
+    and type (a `[:n]` slice of a slot's buffer).
+    -> (float16 [B, 4, H, W], bit-equal to pack_pred_fp16; uint8 [B, H, 2 W, 3], byte-equal to vis_side_by_side, or None)"""
+    if pred.dim() != 4 or pred.shape[1] != 4 or not pred.is_cuda:
+        raise RuntimeError("footprints_amd.ops.infer_pack: pred must be the 4-channel network output [B, 4, H, W] on the device")
+    B, _, H, W = pred.shape
+    if min(B, H, W) < 1:
+        raise RuntimeError("footprints_amd.ops.infer_pack: empty prediction")
+    half, picture = out if out is not None else (None, None)
+    if half is None:
+        half = torch.empty((B, 4, H, W), dtype=torch.float16, device=pred.device)
+    if want_picture and picture is None:
+        picture = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8, device=pred.device)
+    if not want_picture:
+        picture = None
+    if half.dtype != torch.float16 or half.numel() != B * 4 * H * W or \
+            (picture is not None and (picture.dtype != torch.uint8 or picture.numel() != B * H * W * 6)):
+        raise RuntimeError("footprints_amd.ops.infer_pack: out buffers must be float16 [B, 4, H, W] and uint8 [B, H, 2 W, 3]")
+    if want_picture and (image is None or tuple(image.shape) != (B, 3, H, W)):
+        raise RuntimeError("footprints_amd.ops.infer_pack: the picture needs image float32 [B, 3, H, W]")
+    colours = _vis_luts.get("side_by_side")                 # the table's first and last colour as r | g << 8 | b << 16
+    if colours is None:
+        lut = vis_colour_table()
+        colours = _vis_luts["side_by_side"] = tuple(int(c[0]) | int(c[1]) << 8 | int(c[2]) << 16 for c in (lut[0], lut[255]))
+    _lib.check(_lib.load().fp_infer_pack(_f32(pred, "pred"), _f32(image, "image") if want_picture else None, _chk(half, "half"),
+                                         _chk(picture, "picture") if picture is not None else None, colours[0], colours[1],
+                                         B, H, W, stream()), "fp_infer_pack")
+    return half, picture
+
+
 # ---- baseline JPEG encoder (csrc/jpeg.hip) -------------------------------------------------------------------------------------------------
 class JpegTables:
     """what a file of the installed Pillow at one quality is made of, parsed from the bytes up to and including the SOS segment:
@@ -1957,8 +1990,12 @@ def jpeg_decode_packed(pack, out=None, out_bytes=None, subseq_bits=None, max_rou
     max_rounds = JPEG_DECODE_MAX_ROUNDS if max_rounds is None else int(max_rounds)
     scans = pack["scans"] if torch.is_tensor(pack["scans"]) else torch.from_numpy(pack["scans"])
     d_scans = scans.to(device, non_blocking=True)
-    d_rec = torch.from_numpy(pack["records"]).to(device)
-    d_tab = torch.from_numpy(pack["tables"].view("int32")).to(device)
+    if torch.is_tensor(pack["records"]):            # pinned by the caller (datasets/decode_stage.py): queued copies, no wait for the stream
+        d_rec = pack["records"].to(device, non_blocking=True)
+        d_tab = pack["tables"].to(device, non_blocking=True)
+    else:
+        d_rec = torch.from_numpy(pack["records"]).to(device)
+        d_tab = torch.from_numpy(pack["tables"].view("int32")).to(device)
     if out is None:
         out = torch.empty(pack["out_bytes"], dtype=torch.uint8, device=d_scans.device)
     out_bytes = out.numel() if out_bytes is None else int(out_bytes)

@@ -38,6 +38,13 @@ class Options:
         # this build
         p.add_argument("--synthetic_steps", type=int, default=0, help="batches per epoch of synthetic data (no dataset mounted)")
         p.add_argument("--device_augment", action="store_true", help="flip / colour jitter / label assembly on the GPU (row N3)")
+        # inference mode of this build (row N12).  Off unless given -- and absent from the namespace then (read them with getattr(opt,
+        # name, False)), so that a plain parse still yields the reference's flags and the two additions above, nothing else
+        p.add_argument("--device_decode", action="store_true", default=argparse.SUPPRESS,
+                       help="inference mode: decode baseline JPEG frames on the GPU, one batch ahead of the network (same files; "
+                            "what the decoder does not take goes to Pillow)")
+        p.add_argument("--device_jpeg", action="store_true", default=argparse.SUPPRESS,
+                       help="with --save_test_visualisations: encode the pictures on the GPU (same files as Pillow writes)")
 
     def parse(self, argv=None):
         self.options = self.parser.parse_args(argv)

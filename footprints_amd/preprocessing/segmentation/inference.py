@@ -2,17 +2,14 @@
 the bare step (:60-84): an already resized tensor through the network, the full resolution logit map through a sigmoid, as a float32
 numpy array [B,1,H,W].  `Tester` is the reference's program around it (`--mode inference`): the datasets of datasets/inference.py, the
 resize, the network's full-resolution head alone and the output stage (csrc/seg_infer.hip) on the device, file writing on a thread."""
-import collections
 import ctypes as C
 import os
-import queue
-import threading
-import time
 
 import numpy as np
 import torch
 
 from ... import _lib, ops
+from ...datasets.ring import RingPipeline
 from .network import Segmentor
 
 
@@ -29,7 +26,7 @@ class InferenceManager:
             return torch.sigmoid(preds[3][:, 0:1]).cpu().numpy()                          # "just take max resolution prediction"
 
 
-class Tester:
+class Tester(RingPipeline):
     """The reference's `Tester` (segmentation/inference.py:20-91): the trained Segmentor over every frame of the train and val splits, one
     float16 ground-probability map per frame under `<training_data>/<test_save_folder>/...` -- the files ground_truth_generation reads.
 
@@ -45,10 +42,11 @@ class Tester:
                there behind seg_pack (ops.jpeg_encode_packed: the files Pillow writes, byte for byte); only the table of the scans'
                lengths comes back with the batch, and the writer, which may wait, copies the bytes in use on a stream of its own.
     An exception in a reader or in the writer ends `test()` with that exception; every wait on a queue, a future or a slot has a timeout
-    after which the waiting thread looks at the error flag.  `has_gt`, tensorboard and data parallelism are not part of this mode."""
-
-    POLL = 0.05          # seconds between two looks at the error flag while a thread waits
-    SPIN = 0.0002        # seconds between two queries of a slot's `ready` event (a batch takes milliseconds)
+    after which the waiting thread looks at the error flag (the scaffolding is datasets/ring.py's, shared with the main network's
+    pipeline).  `has_gt`, tensorboard and data parallelism are not part of this mode.
+    With --device_decode the readers only read and parse the files (datasets/decode_stage.py): the frames the device decoder accepts are
+    decoded into the slot's packed buffer one batch ahead -- batch k + 1's decode is queued before batch k's status is looked at -- and
+    the calling thread's only wait is for that status; the files written are the same, byte for byte."""
 
     def __init__(self, options, model=None, dataset=None, save_path=None, slots=3):
         """model / dataset / save_path: injected (tests, benchmarks); then neither the config file nor the split files are read"""
@@ -59,6 +57,8 @@ class Tester:
         self.num_workers = min(max(int(getattr(options, "num_workers", 4) or 1), 1), 16)
         self.visualise = bool(options.save_test_visualisations)
         self.device_jpeg = self.visualise and bool(getattr(options, "device_jpeg", False))
+        self.device_decode = bool(getattr(options, "device_decode", False))
+        self.stage = None
         if dataset is None or save_path is None:
             import yaml
             with open(self.opt.config_path) as fh:
@@ -84,8 +84,7 @@ class Tester:
         self.dataset = dataset
         self.n_slots = max(int(slots), 1)
         self.slots = None
-        self._error = None
-        self._stop = threading.Event()
+        self._ring_init()
 
     # ---- device half ------------------------------------------------------------------------------------------------------------------
     def _make_slots(self):
@@ -113,6 +112,11 @@ class Tester:
             elif self.visualise:
                 s["h_pic"] = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8).pin_memory()
             slots.append(s)
+        if self.device_decode:
+            from ...datasets.decode_stage import DecodeStage
+            self.stage = DecodeStage(B, H, W, self.tables, self.device, stop=self._stop)
+            for s in slots:
+                self.stage.new_slot(s)
         if self.device_jpeg:
             # the pictures of a batch lie dense in d_pic: one set of records serves every slot, and its first n a batch of n
             self.jpeg_records = torch.from_numpy(ops.jpeg_records([(H, 2 * W)] * B)[0]).to(self.device)
@@ -139,10 +143,15 @@ class Tester:
         H, W = self.height, self.width
         self._reserve_src(s, sum(f.shape[0] * f.shape[1] * 3 for f in frames))
         _, _, total, _, max_h, max_w = ops.resize_pack(frames, H, W, self.tables, packed=s["h_src"].numpy(), records=s["h_rec"].numpy())
+        s["d_src"][:total].copy_(s["h_src"][:total], non_blocking=True)
+        s["d_rec"].copy_(s["h_rec"], non_blocking=True)
+        self._device_rest(s, n, total, max_h, max_w)
+
+    def _device_rest(self, s, n, total, max_h, max_w):
+        """a batch of n frames lies packed in the slot's d_src with its records in d_rec (uploaded, or decoded there): queue the rest"""
+        H, W = self.height, self.width
         self.model.eval()
         with torch.no_grad():
-            s["d_src"][:total].copy_(s["h_src"][:total], non_blocking=True)
-            s["d_rec"].copy_(s["h_rec"], non_blocking=True)
             u8 = ops.resize_u8_packed(s["d_src"], total, s["d_rec"], n, H, W, 3, max_h, max_w, self.tables, out=s["d_u8"][:n])
             image = ops.to_tensor_u8(u8)
             scales = getattr(self.model, "inference_scales", None)            # the model may be the caller's: its setting comes back
@@ -165,10 +174,7 @@ class Tester:
     def _wait_slot(self, s, n):
         """wait for the slot's results -> (float16 numpy [n, 1, H, W], uint8 numpy [n, H, 2 W, 3] or None): views of the pinned buffers;
         with device_jpeg the second is the list of the n .jpg files' bytes"""
-        while not s["ready"].query():                       # a wait with a timeout, like every other one: look at the stop flag in between
-            if self._stop.is_set():
-                raise RuntimeError("the inference pipeline was stopped while a batch was in flight")
-            time.sleep(self.SPIN)
+        self._wait_event(s["ready"])                        # a wait with a timeout, like every other one
         if self.device_jpeg:
             return s["h_half"].numpy()[:n], self._fetch_files(s, n)
         return s["h_half"].numpy()[:n], (s["h_pic"].numpy()[:n] if self.visualise else None)
@@ -176,15 +182,7 @@ class Tester:
     def _fetch_files(self, s, n):
         """the slot's batch is finished and its length table is on the host: copy the scans' bytes in use -- on a stream of this thread's
         own, which it waits for; the thread that queues batches never does -- and put headers and EOI around them"""
-        table = s["h_tab"].numpy()[:n + 1]
-        used = int(table[n][0])
-        if self.h_scan is None or self.h_scan.numel() < used:
-            self.h_scan = torch.empty(max(used + used // 4, 1 << 16), dtype=torch.uint8).pin_memory()
-        if used:
-            with torch.cuda.stream(self.copy_stream):
-                self.h_scan[:used].copy_(s["d_scan"][:used], non_blocking=True)
-            self.copy_stream.synchronize()
-        return ops.jpeg_files(self.h_scan.numpy()[:used], table, [(self.height, 2 * self.width)] * n, 95)
+        return self._fetch_jpeg_files(s, n, (self.height, 2 * self.width))
 
     def test_batch(self, frames):
         """frames: list of decoded RGB frames, uint8 [h, w, 3] of any (mixed) sizes -> (float16 numpy [B, 1, H, W], uint8 numpy
@@ -198,98 +196,35 @@ class Tester:
         return half.copy(), (pics.copy() if isinstance(pics, np.ndarray) else pics)
 
     # ---- the pipeline -----------------------------------------------------------------------------------------------------------------
-    def _fail(self, exc):
-        if self._error is None:
-            self._error = exc
-        self._stop.set()
-
-    def _check(self):
-        if self._error is not None:
-            raise self._error
-
     def _read(self, index):
-        if self._stop.is_set():
-            return None
-        return self.dataset[index]
+        if not self.device_decode:
+            return self.dataset[index]
+        from ...datasets.decode_stage import read_sample
+        sample = read_sample(self.dataset.image_path(index), True)
+        sample["idx"] = index
+        return sample
 
     def _writer(self, jobs, free):
-        try:
-            while True:
-                try:
-                    job = jobs.get(timeout=self.POLL)
-                except queue.Empty:
-                    if self._stop.is_set():
-                        return
-                    continue
-                if job is None:
-                    return
-                si, indices = job
-                half, pics = self._wait_slot(self.slots[si], len(indices))
-                for i, idx in enumerate(indices):
-                    self.dataset.save_result(idx, half[i], self.save_path, pics[i] if pics is not None else None)
-                free[si].set()                              # only now may the slot's pinned buffers be refilled
-        except BaseException as exc:                        # noqa: handed to the thread that called test()
-            self._fail(exc)
+        self._ring_writer(jobs, free, collect=lambda si, n: self._wait_slot(self.slots[si], n),
+                          save=lambda idx, results, i: self.dataset.save_result(idx, results[0][i], self.save_path,
+                                                                                results[1][i] if results[1] is not None else None))
 
-    def _wait(self, done):
-        """poll `done()` (True when what is waited for has happened), looking at the error flag in between"""
-        while not done(self.POLL):
-            self._check()
+    def _finish_decode(self, si, samples):
+        s = self.slots[si]
+        d = self.stage.finish(s)
+        self._device_rest(s, d["n"], d["total"], d["max_h"], d["max_w"])
 
     def test(self):
         """Run every frame of the dataset through the network and write its result"""
         print("running inference...")
-        from concurrent.futures import ThreadPoolExecutor, TimeoutError as FutureTimeout
         if self.slots is None:
             self.slots = self._make_slots()
-        self._error = None
-        self._stop.clear()
-        N, B = len(self.dataset), self.batch_size
-        jobs = queue.Queue()
-        free = [threading.Event() for _ in self.slots]
-        for ev in free:
-            ev.set()
-        writer = threading.Thread(target=self._writer, args=(jobs, free), name="seg-infer-writer", daemon=True)
-        readers = ThreadPoolExecutor(self.num_workers, thread_name_prefix="seg-infer-reader")
-        pending = collections.deque()
-        ahead = B * (len(self.slots) + 1)                   # frames decoded ahead of the batch being queued
-        submitted = 0
-
-        def result_of(fut):
-            def done(timeout):
-                try:
-                    fut.result(timeout=timeout)
-                    return True
-                except FutureTimeout:
-                    return False
-            self._wait(done)
-            return fut.result()
-
-        writer.start()
-        try:
-            n_batches = (N + B - 1) // B
-            for k in range(n_batches):
-                indices = list(range(k * B, min((k + 1) * B, N)))               # the last batch may be short
-                while submitted < min(N, k * B + ahead):
-                    pending.append(readers.submit(self._read, submitted))
-                    submitted += 1
-                samples = [result_of(pending.popleft()) for _ in indices]
-                si = k % len(self.slots)
-                self._wait(free[si].wait)                   # the writer is done with this slot's previous batch
-                free[si].clear()
-                self._device_half(self.slots[si], [smp["image"] for smp in samples])
-                jobs.put((si, [smp["idx"] for smp in samples]))
-            jobs.put(None)
-            self._wait(lambda timeout: (writer.join(timeout), not writer.is_alive())[1])
-            self._check()
-        except BaseException as exc:
-            self._fail(exc)
-            raise
-        finally:
-            self._stop.set()
-            for fut in pending:
-                fut.cancel()
-            readers.shutdown(wait=True)
-            while writer.is_alive():
-                writer.join(self.POLL)
+        if self.device_decode:
+            ahead = lambda si, samples: self.stage.queue(self.slots[si], samples)
+            rest = self._finish_decode
+        else:
+            ahead = None
+            rest = lambda si, samples: self._device_half(self.slots[si], [smp["image"] for smp in samples])
+        self.run_ring(len(self.dataset), self.batch_size, len(self.slots), self.num_workers, read=self._read, rest=rest, ahead=ahead,
+                      writer=self._writer, name="seg-infer")
         print("finished testing!")

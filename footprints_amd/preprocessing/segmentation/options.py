@@ -33,6 +33,9 @@ class SegmentationOptions:
         p.add_argument("--save_test_visualisations", action="store_true")
         p.add_argument("--device_jpeg", action="store_true",
                        help="with --save_test_visualisations: encode the pictures on the GPU (same files as Pillow writes)")
+        p.add_argument("--device_decode", action="store_true",
+                       help="inference mode: decode baseline JPEG frames on the GPU, one batch ahead of the network (same files; "
+                            "what the decoder does not take goes to Pillow)")
 
     def parse(self, args=None):
         self.options = self.parser.parse_args(args)

@@ -644,6 +644,15 @@ int fp_vis_side_by_side(const float* image, const float* pred, uint8_t* out, int
 int fp_seg_pack(const float* logits, int64_t logit_batch_stride, const float* image, void* prob_half, float* prob_f32, uint8_t* picture,
                 const uint8_t* lut, int32_t B, int32_t H, int32_t W, fp_stream_t stream);
 
+/* ---- output stage of the main network's test-set inference (footprints/evaluation/inference.py:105-119; csrc/infer_pack.hip) ---- */
+/* One launch over the logits pred float [B][4][H][W] that writes what fp_pack_pred_fp16 and fp_vis_side_by_side write in two, through the
+ * same device functions: out_half float16 [B][4][H][W], bit-equal to fp_pack_pred_fp16 (sigmoid on channels 0 and 1); picture (NULL ok;
+ * needs image float [B][3][H][W]) uint8 [B][H][2W][3], byte-equal to fp_vis_side_by_side (left half uint8(image * 255.0f), right half
+ * colour1 where pred[:,1] > 0, colour0 elsewhere; a colour = r | g << 8 | b << 16).  image may be NULL without a picture.  Any H, W,
+ * B >= 1; operands that are not aligned for wide accesses (W % 4 != 0, an offset base pointer) take a scalar path. */
+int fp_infer_pack(const float* pred, const float* image, void* out_half, uint8_t* picture, uint32_t colour0, uint32_t colour1, int32_t B,
+                  int32_t H, int32_t W, fp_stream_t stream);
+
 /* ---- baseline JPEG encoder (csrc/jpeg.hip): the scan Pillow's Image.save(quality=q) writes for an RGB picture, byte for byte ---- */
 typedef struct fp_jpeg_sample {
   int64_t offset; /* of the picture's first byte in `src`; dense uint8 [h][w][3] */

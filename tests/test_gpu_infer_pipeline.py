@@ -1,0 +1,384 @@
+"""GPU: test-set inference from the command line -- fp_infer_pack against the two launches it replaces, bit for
+bit; the decode stage alone; the main network's pipeline end to end against `test_batch` on Pillow's frames, with and without device
+decoding, also through `main(["--mode", "inference", ...])`; the segmentation Tester with --device_decode; and the order in which the
+calling thread queues a batch's parts."""
+import io
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import infer_pack_restatement as IR
+from tests.golden import make_golden_jpeg_decode as G
+from tests.test_gpu_jpeg_decode import noise_frame
+
+pytestmark = pytest.mark.gpu
+
+H, W, BS = 64, 96, 3
+
+
+# ---- 1. fp_infer_pack -------------------------------------------------------------------------------------------------------------------
+def _offset_view(host, offset, fill):
+    """the array in a larger flat device buffer, `offset` elements behind its start -> (flat, view)"""
+    t = torch.from_numpy(host)
+    flat = torch.full((offset + t.numel() + 16,), fill, dtype=t.dtype, device="cuda")
+    assert flat.data_ptr() % 16 == 0
+    view = flat[offset:offset + t.numel()].view(t.shape)
+    view.copy_(t.cuda())
+    return flat, view
+
+
+@pytest.mark.parametrize("B,Hh,Ww,offset", [(1, 1, 1, 0), (2, 3, 5, 0), (3, 8, 12, 0), (2, 5, 8, 1), (2, 64, 96, 0)],
+                         ids=["one_pixel", "scalar_2x3x5", "vector_3x8x12", "offset_bases_2x5x8", "2x64x96"])
+def test_infer_pack_equals_the_two_launches(B, Hh, Ww, offset):
+    from footprints_amd import ops
+    pred_host, image_host = IR.inputs(B, Hh, Ww, seed=B * 1000 + Hh * Ww)
+    _, pred = _offset_view(pred_host, offset, 1e30)
+    _, image = _offset_view(image_host, offset, -3.0)
+    n = B * Hh * Ww
+    want_half = ops.pack_pred_fp16(pred.clone()).cpu().numpy()
+    want_pic = ops.vis_side_by_side(image.clone(), pred.clone()).cpu().numpy()
+    half_flat = torch.full((offset + 4 * n + 16,), -7.0, dtype=torch.float16, device="cuda")
+    pic_flat = torch.full((offset + 6 * n + 16,), 0xA5, dtype=torch.uint8, device="cuda")
+    half, pic = ops.infer_pack(pred, image, want_picture=True, out=(half_flat[offset:offset + 4 * n].view(B, 4, Hh, Ww),
+                                                                    pic_flat[offset:offset + 6 * n].view(B, Hh, 2 * Ww, 3)))
+    torch.cuda.synchronize()
+    assert half.data_ptr() == half_flat.data_ptr() + 2 * offset and pic.data_ptr() == pic_flat.data_ptr() + offset
+    got_half, got_pic = half.cpu().numpy(), pic.cpu().numpy()
+    assert np.array_equal(got_half.view(np.uint16), want_half.view(np.uint16))
+    assert np.array_equal(got_pic, want_pic)
+    assert np.array_equal(pred.cpu().numpy().view(np.uint32), pred_host.view(np.uint32))              # the inputs are only read
+    # nothing outside the outputs was written
+    hf, pf = half_flat.cpu(), pic_flat.cpu()
+    assert (hf[:offset] == -7.0).all() and (hf[offset + 4 * n:] == -7.0).all()
+    assert (pf[:offset] == 0xA5).all() and (pf[offset + 6 * n:] == 0xA5).all()
+    # what both launches must satisfy: the restatement's picture; the float16 files within one float16 step of the float64 sigmoid
+    # rounded once (the device's float32 sigmoid carries an error of a few float32 ulp, which can move a rounding by one step at most);
+    # the depth channels, which no arithmetic touches, exactly
+    lut = ops.vis_colour_table()
+    r_half, r_pic = IR.pack(pred_host, image_host, lut[0], lut[255])
+    assert np.array_equal(got_pic, r_pic)
+    assert np.array_equal(got_half[:, 2:].view(np.uint16), r_half[:, 2:].view(np.uint16))
+    steps = np.abs(got_half[:, :2].view(np.int16).astype(np.int32) - r_half[:, :2].view(np.int16).astype(np.int32))
+    assert steps.max() <= 1
+    # the planted logits: +-1e-8 and the zeros give exactly 0.5 and the colour of their sign; saturation; float16 subnormals
+    if n >= IR.PLANTED.size:
+        ground, right = pred_host[:, 1].reshape(-1), got_pic[:, :, Ww:].reshape(-1, 3)
+        for v, colour in ((1e-8, lut[255]), (-1e-8, lut[0])):
+            at = np.flatnonzero(ground == np.float32(v))
+            assert at.size >= 1 and (right[at] == colour).all() and (got_half[:, 1].reshape(-1)[at] == np.float16(0.5)).all()
+        assert (right[ground == 0] == lut[0]).all() and (ground == 0).sum() >= 2
+        for v, h in ((20.0, 1.0), (88.0, 1.0), (104.0, 1.0), (-20.0, 0.0), (-88.0, 0.0), (-104.0, 0.0)):
+            at = pred_host[:, :2] == np.float32(v)
+            assert at.sum() >= 2 and (got_half[:, :2][at] == np.float16(h)).all()
+        sub = (got_half[:, :2] > 0) & (got_half[:, :2] < np.float16(6.104e-5))
+        assert sub.sum() >= 5
+    # without the picture, and without the image altogether: the same halves, the picture buffer untouched
+    for img in (image, None):
+        pic_flat.fill_(0x5A)
+        h2, p2 = ops.infer_pack(pred, img, want_picture=False, out=(None, pic_flat[offset:offset + 6 * n].view(B, Hh, 2 * Ww, 3)))
+        assert p2 is None and np.array_equal(h2.cpu().numpy().view(np.uint16), want_half.view(np.uint16))
+        assert (pic_flat == 0x5A).all()
+    h3, p3 = ops.infer_pack(pred, image, want_picture=True)
+    assert np.array_equal(h3.cpu().numpy().view(np.uint16), want_half.view(np.uint16)) and np.array_equal(p3.cpu().numpy(), want_pic)
+
+
+def test_infer_pack_into_slices_of_a_slot_and_bad_arguments():
+    """a short batch: n < B samples into `[:n]` of buffers for B, the rest keeps the sentinel"""
+    from footprints_amd import ops
+    B, n, Hh, Ww = 3, 2, 8, 12
+    pred_host, image_host = IR.inputs(n, Hh, Ww, seed=77)
+    pred, image = torch.from_numpy(pred_host).cuda(), torch.from_numpy(image_host).cuda()
+    d_half = torch.full((B, 4, Hh, Ww), -7.0, dtype=torch.float16, device="cuda")
+    d_pic = torch.full((B, Hh, 2 * Ww, 3), 0xA5, dtype=torch.uint8, device="cuda")
+    half, pic = ops.infer_pack(pred, image, want_picture=True, out=(d_half[:n], d_pic[:n]))
+    assert half.data_ptr() == d_half.data_ptr() and pic.data_ptr() == d_pic.data_ptr()
+    assert torch.equal(d_half[:n], ops.pack_pred_fp16(pred)) and torch.equal(d_pic[:n], ops.vis_side_by_side(image, pred))
+    assert (d_half[n:] == -7.0).all() and (d_pic[n:] == 0xA5).all()
+    with pytest.raises(RuntimeError):
+        ops.infer_pack(pred, None, want_picture=True)                              # the picture needs the image
+    with pytest.raises(RuntimeError):
+        ops.infer_pack(pred[:, :3].contiguous())                                   # not the 4-channel output
+    with pytest.raises(RuntimeError):
+        ops.infer_pack(pred, out=(d_half, None))                                   # a buffer for another batch size
+    with pytest.raises(RuntimeError):
+        ops.infer_pack(pred.cpu())
+
+
+# ---- the files ---------------------------------------------------------------------------------------------------------------------------
+def _progressive(frame):
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(frame).save(buf, format="JPEG", progressive=True)
+    return buf.getvalue()
+
+
+def _grey(frame, quality):
+    from PIL import Image
+    return G.write(np.asarray(Image.fromarray(frame).convert("L")), quality)
+
+
+def _files_below(root):
+    out = {}
+    for folder, _, names in os.walk(str(root)):
+        for name in names:
+            with open(os.path.join(folder, name), "rb") as fh:
+                out[os.path.relpath(os.path.join(folder, name), str(root))] = fh.read()
+    return out
+
+
+@pytest.fixture(scope="module")
+def kitti(tmp_path_factory):
+    """7 files in the KITTI layout, mixed sizes: five the device decodes (4:2:0, 4:4:4, 4:2:2, grey), a progressive one (the parser
+    sends it to Pillow) and the noise frame (status 2 at the default budget) -> (root, names, files, Pillow-decoded frames)"""
+    root = tmp_path_factory.mktemp("kitti_raw")
+    files = [G.write(G.photo(70, 231, 11), 95, 2), G.write(G.photo(75, 248, 12), 90, 0), _progressive(G.photo(70, 231, 13)),
+             G.write(G.photo(75, 248, 14), 85, 1), noise_frame(), _grey(G.photo(70, 231, 15), 90), G.write(G.photo(75, 248, 16), 95, 2)]
+    names = ["2011_09_26/drive_%d %d %s" % (i // 4, 10 * i + 3, "l" if i % 3 else "r") for i in range(7)]
+    for name, data in zip(names, files):
+        seq, frame, side = name.split(" ")
+        folder = root / seq / ("image_02" if side == "l" else "image_03") / "data"
+        folder.mkdir(parents=True, exist_ok=True)
+        (folder / ("%010d.jpg" % int(frame))).write_bytes(data)
+    return str(root), names, files, [G.pillow_decode(f) for f in files]
+
+
+def _model_manager():
+    from footprints_amd.model_manager import ModelManager
+    torch.manual_seed(5)
+    return ModelManager(is_inference=True)
+
+
+def _pillow_inputs(frames):
+    """the reference reader's tensors: Pillow's LANCZOS resize and ToTensor on the host"""
+    from PIL import Image
+    resized = np.stack([np.asarray(Image.fromarray(f).resize((W, H), Image.LANCZOS)) for f in frames])
+    return torch.from_numpy(resized).permute(0, 3, 1, 2).contiguous().float().div(255)
+
+
+# ---- 2. the decode stage alone -----------------------------------------------------------------------------------------------------------
+def test_decode_stage_alone(tmp_path):
+    from footprints_amd import ops
+    from footprints_amd.datasets.decode_stage import DecodeStage, read_sample
+    files = [G.write(G.photo(70, 231, s), 95, 2) for s in (1, 2, 3)] + [G.write(G.photo(75, 248, 4), 90, 0), G.write(G.photo(70, 231, 5), 85, 1),
+                                                                      _grey(G.photo(75, 248, 6), 90), _progressive(G.photo(70, 231, 7)), noise_frame()]
+    paths = []
+    for i, f in enumerate(files):
+        paths.append(str(tmp_path / ("%d.jpg" % i)))
+        with open(paths[-1], "wb") as fh:
+            fh.write(f)
+    device = torch.device("cuda", torch.cuda.current_device())
+    stage = DecodeStage(8, H, W, ops.resize_table_set(device), device)
+    s = stage.new_slot()
+    samples = [read_sample(p, True) for p in paths]
+    assert ["image" in smp for smp in samples] == [False] * 6 + [True, False]
+    stage.queue(s, samples)
+    d = stage.finish(s)
+    torch.cuda.synchronize()
+    frames = [G.pillow_decode(f) for f in files]
+    want = np.concatenate([f.reshape(-1) for f in frames])
+    assert d["total"] == want.size and d["n"] == 8 and (d["max_h"], d["max_w"]) == (96, 248)
+    assert np.array_equal(d["src"][:d["total"]].cpu().numpy(), want)                     # the packed buffer, byte for byte
+    print("status", d["status"], "counters", stage.counters)
+    assert d["status"] == [0] * 6 + [-1, 2]
+    assert stage.counters == dict(device=6, host_parser=1, host_status=1)                # the fallback hides no decoder failure
+    # the records are resize_pack's: the resize reads the buffer as it reads an uploaded batch
+    u8 = ops.resize_u8_packed(d["src"], d["total"], d["records"], 8, H, W, 3, d["max_h"], d["max_w"], stage.tables)
+    assert torch.equal(u8, ops.resize_u8(frames, H, W))
+    # a second batch on the same slot, short, all on the device
+    stage.queue(s, samples[:2])
+    d = stage.finish(s)
+    assert d["status"] == [0, 0] and stage.counters == dict(device=8, host_parser=1, host_status=1)
+    assert np.array_equal(d["src"][:d["total"]].cpu().numpy(), want[:d["total"]])
+
+
+# ---- 3. the main network's pipeline ------------------------------------------------------------------------------------------------------
+def _expected_arrays(im, frames):
+    out = []
+    for k in range(0, len(frames), BS):
+        out += list(im.test_batch({"image": _pillow_inputs(frames[k:k + BS])}))
+    return out
+
+
+def test_run_dataset_end_to_end(tmp_path, kitti):
+    from footprints_amd.datasets.inference import KITTIInferenceDataset, MatterportInferenceDataset
+    from footprints_amd.evaluation.inference import InferenceManager
+    root, names, files, frames = kitti
+    mm = _model_manager()
+    dataset = KITTIInferenceDataset(root, names, H, W)
+    written, expected = {}, None
+    for pictures in (False, True):
+        for device_decode in (False, True):
+            save = tmp_path / ("p%d_d%d" % (pictures, device_decode))
+            im = InferenceManager(model_manager=mm, save_path=str(save), save_test_visualisations=pictures, device_jpeg=pictures)
+            mm.model.inference_scales = None
+            counters = im.run_dataset(dataset, BS, num_workers=2, slots=2, device_decode=device_decode)
+            assert mm.model.inference_scales is None                              # handed back as it was
+            mm.model.inference_scales = ("1/1",)
+            print("pictures", pictures, "device_decode", device_decode, counters)
+            assert counters == (dict(device=5, host_parser=1, host_status=1) if device_decode else dict(device=0, host_parser=0, host_status=0))
+            written[pictures, device_decode] = _files_below(save)
+            if expected is None:
+                expected = _expected_arrays(im, frames)
+    for pictures in (False, True):
+        host, dev = written[pictures, False], written[pictures, True]
+        assert sorted(host) == sorted("%03d.%s" % (i, e) for i in range(7) for e in (("npy", "jpg") if pictures else ("npy",)))
+        assert host == dev                                                        # .npy and .jpg, byte for byte
+        for i in range(7):
+            got = np.load(os.path.join(str(tmp_path), "p%d_d1" % pictures, "%03d.npy" % i))
+            assert got.dtype == np.float16 and got.shape == (4, H, W)
+            assert np.array_equal(got.view(np.uint16), expected[i].view(np.uint16)), i
+    assert all(written[True, True]["%03d.npy" % i] == written[False, True]["%03d.npy" % i] for i in range(7))
+    # the pictures: what the blocking path draws and Pillow encodes
+    from PIL import Image
+    im = InferenceManager(model_manager=mm, save_test_visualisations=True)
+    _, vis = im._test_batch({"image": _pillow_inputs(frames[:BS])}, True)
+    for i in range(BS):
+        buf = io.BytesIO()
+        Image.fromarray(vis[i]).save(buf, format="JPEG", quality=95)
+        assert written[True, True]["%03d.jpg" % i] == buf.getvalue()
+    # the Matterport class, one batch
+    mp_root = tmp_path / "mp_raw"
+    lines = []
+    for i in (0, 1):
+        folder = mp_root / "scanA" / "scanA" / "matterport_color_images"
+        folder.mkdir(parents=True, exist_ok=True)
+        (folder / ("pos%d_i1_2.jpg" % i)).write_bytes(files[i])
+        lines.append("scanA pos%d 1 2" % i)
+    im = InferenceManager(model_manager=mm, save_path=str(tmp_path / "mp_out"))
+    assert im.run_dataset(MatterportInferenceDataset(str(mp_root), lines, H, W), BS, num_workers=1, slots=2, device_decode=True)["device"] == 2
+    want = im.test_batch({"image": _pillow_inputs(frames[:2])})
+    for i in (0, 1):
+        got = np.load(tmp_path / "mp_out" / "scanA" / ("pos%d_1_2.npy" % i))
+        assert np.array_equal(got.view(np.uint16), want[i].view(np.uint16))
+    with pytest.raises(ValueError, match="2 slots"):
+        im.run_dataset(dataset, BS, slots=1, device_decode=True)
+
+
+def test_main_inference_mode(tmp_path, kitti, monkeypatch):
+    from footprints_amd.evaluation.inference import InferenceManager
+    from footprints_amd.main import main
+    root, names, files, frames = kitti
+    monkeypatch.chdir(tmp_path)
+    (tmp_path / "paths.yaml").write_text("kitti:\n  dataset: %s\nmatterport:\n  dataset: /nowhere\n" % root)
+    (tmp_path / "splits" / "kitti").mkdir(parents=True)
+    (tmp_path / "splits" / "kitti" / "test.txt").write_text("\n".join(names) + "\n")
+    mm = _model_manager()
+    common = ["--mode", "inference", "--inference_data_type", "kitti", "--height", str(H), "--width", str(W), "--batch_size", str(BS),
+              "--num_workers", "2", "--config_path", str(tmp_path / "paths.yaml")]
+    assert main(common + ["--inference_save_path", str(tmp_path / "host")], model_manager=mm) == dict(device=0, host_parser=0, host_status=0)
+    # the default save path, the pictures encoded by Pillow, the frames decoded on the device
+    (tmp_path / "weights").mkdir()
+    counters = main(common + ["--load_path", str(tmp_path / "weights"), "--device_decode", "--save_test_visualisations"], model_manager=mm)
+    assert counters == dict(device=5, host_parser=1, host_status=1)
+    host, dev = _files_below(tmp_path / "host"), _files_below(tmp_path / "weights" / "kitti_predictions")
+    assert sorted(host) == ["%03d.npy" % i for i in range(7)] and sorted(dev) == sorted(list(host) + ["%03d.jpg" % i for i in range(7)])
+    assert all(dev[k] == v for k, v in host.items())
+    im = InferenceManager(model_manager=mm)
+    expected = _expected_arrays(im, frames)
+    for i in range(7):
+        assert np.array_equal(np.load(tmp_path / "host" / ("%03d.npy" % i)).view(np.uint16), expected[i].view(np.uint16))
+    # --device_jpeg writes the files Pillow writes
+    main(common + ["--inference_save_path", str(tmp_path / "dev_jpeg"), "--device_decode", "--save_test_visualisations", "--device_jpeg"],
+         model_manager=mm)
+    assert _files_below(tmp_path / "dev_jpeg") == dev
+
+
+# ---- 4. the segmentation Tester ----------------------------------------------------------------------------------------------------------
+def test_segmentation_tester_with_device_decode(tmp_path, kitti):
+    from footprints_amd import ops
+    from footprints_amd.preprocessing.segmentation.datasets.inference import KITTIInferenceDataset
+    from footprints_amd.preprocessing.segmentation.inference import Tester
+    from footprints_amd.preprocessing.segmentation.network import Segmentor
+    from footprints_amd.preprocessing.segmentation.options import SegmentationOptions
+    from oracle import restatement as R
+    root, names, files, frames = kitti
+    P, Bf = R.make_seg_state(True, tag="g9.psp")
+    model = Segmentor(pretrained=False, use_PSP=True)
+    model.load_state_dict({**P, **Bf})
+    model.cuda()
+    written = {}
+    for pictures in (False, True):
+        for flag in (False, True):
+            opt = SegmentationOptions().parse(["--mode", "inference", "--height", str(H), "--width", str(W), "--batch_size", str(BS), "--num_workers", "2"]
+                                              + (["--save_test_visualisations", "--device_jpeg"] if pictures else [])
+                                              + (["--device_decode"] if flag else []))
+            save = tmp_path / ("p%d_d%d" % (pictures, flag))
+            tester = Tester(opt, model=model, dataset=KITTIInferenceDataset(root, names, H, W), save_path=str(save), slots=2)
+            tester.test()
+            assert model.inference_scales is None
+            written[pictures, flag] = _files_below(save)
+            if flag:
+                print("pictures", pictures, tester.stage.counters)
+                assert tester.stage.counters == dict(device=5, host_parser=1, host_status=1)
+            else:
+                assert tester.stage is None
+        assert len(written[pictures, True]) == (14 if pictures else 7) and written[pictures, True] == written[pictures, False]
+    # without the flag: what test_gpu_seg_infer.py pins -- seg_pack of the plain all-heads network on Pillow's frames, in the Tester's batches
+    model.eval()
+    dataset = KITTIInferenceDataset(root, names, H, W)
+    image = _pillow_inputs(frames)
+    for k in range(0, 7, BS):
+        with torch.no_grad():
+            half, _, _ = ops.seg_pack(model(image[k:k + BS].cuda())[3])
+        half = half.cpu().numpy()
+        for j in range(half.shape[0]):
+            seq, frame, side = dataset._parse_index(k + j)
+            got = np.load(os.path.join(str(tmp_path), "p0_d0", seq, side, "data", "%010d.npy" % int(frame)))
+            assert got.shape == (1, H, W) and np.array_equal(got.view(np.uint16), half[j].view(np.uint16))
+
+
+# ---- 5. the ordering ---------------------------------------------------------------------------------------------------------------------
+def test_decode_runs_one_batch_ahead_and_the_host_decodes_nothing(tmp_path, monkeypatch):
+    from PIL import Image
+    from footprints_amd.datasets.inference import KITTIInferenceDataset
+    from footprints_amd.evaluation.inference import InferenceManager
+    names = ["seq %d l" % i for i in range(8)]
+    folder = tmp_path / "raw" / "seq" / "image_02" / "data"
+    folder.mkdir(parents=True)
+    for i in range(8):
+        h, w = ((70, 231), (75, 248))[i % 2]
+        (folder / ("%010d.jpg" % i)).write_bytes(G.write(G.photo(h, w, 40 + i), (95, 90, 85)[i % 3], (2, 0, 1)[i % 3]))
+    dataset = KITTIInferenceDataset(str(tmp_path / "raw"), names, H, W)
+    im = InferenceManager(model_manager=_model_manager(), save_path=str(tmp_path / "out"))
+    im.run_dataset(dataset, BS, num_workers=2, slots=2, device_decode=True)              # builds the ring and its stage
+    events, opened = [], []
+    stage, queue, finish, network, open_ = im.stage, im.stage.queue, im.stage.finish, im._network, Image.open
+
+    def rec_queue(s, samples):
+        events.append(("queue", samples[0]["idx"] // BS))
+        return queue(s, samples)
+
+    def rec_finish(s):
+        events.append(("finish", s["batch"]["samples"][0]["idx"] // BS))
+        return finish(s)
+
+    def rec_network(image):
+        events.append(("network", sum(1 for e in events if e[0] == "network")))
+        return network(image)
+
+    def rec_open(*args, **kwargs):
+        opened.append(args)
+        return open_(*args, **kwargs)
+
+    def rec_decode(data):
+        opened.append("stage.decode")
+        return stage_decode(data)
+
+    stage_decode = stage.decode
+    monkeypatch.setattr(stage, "queue", rec_queue)
+    monkeypatch.setattr(stage, "finish", rec_finish)
+    monkeypatch.setattr(stage, "decode", rec_decode)
+    monkeypatch.setattr(im, "_network", rec_network)
+    monkeypatch.setattr(Image, "open", rec_open)
+    counters = im.run_dataset(dataset, BS, num_workers=2, slots=2, device_decode=True)
+    assert im.stage is stage and counters == dict(device=8, host_parser=0, host_status=0)
+    assert opened == []                                                            # every status 0: the host decoded nothing
+    last = 2
+    at = {e: i for i, e in enumerate(events)}
+    assert len(events) == 9 and len(at) == 9
+    for k in range(last):
+        assert at["queue", k + 1] < at["finish", k] < at["network", k], events
+    assert at["finish", last] < at["network", last] and at["network", last - 1] < at["finish", last]
+    assert sorted(os.listdir(tmp_path / "out")) == ["%03d.npy" % i for i in range(8)]
