@@ -3,5 +3,5 @@
 `raw_images` / `filter_depth_mask` options; csrc/reader.hip); for the training readers file decoding and the cv2 resizes of the label
 maps stay host-side dataset plumbing.  The test-set readers of the main network (inference.py) and the two inference pipelines decode
 baseline JPEG frames on the device when asked to (decode_stage.py: one batch ahead of the network); ring.py is
-the thread / slot / writer scaffolding those pipelines share."""
+what those pipelines share: the thread / slot / writer scaffolding and the device side of the ring."""
 from .device_path import AugParams, DeviceBatchAssembler, DeviceLoader, SyntheticSampleSource, draw_augmentation  # noqa: F401

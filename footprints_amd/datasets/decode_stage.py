@@ -9,11 +9,15 @@ thread never waits.  `DecodeStage` splits the call in two around a batch:
                   fp_resize_sample records ops.resize_pack writes; the sizes come from the headers -- copies the host-decoded frames into
                   the pinned buffer at their offsets, queues their upload, the uploads of the scans and ops.jpeg_decode_packed into the
                   same device buffer, a copy of the status into pinned memory, and records an event.  Waits for nothing.
+                  A batch the host decoded entirely -- every batch without --device_decode -- is one upload of the bytes in use.
   finish(s)       waits for that event, decodes every sample whose status is not 0 with Pillow and uploads it to the sample's offset
-                  (whatever Pillow raises ends the run, with the file's path in the message), and returns what ops.resize_u8_packed needs.
+                  (whatever Pillow raises ends the run, with the file's path in the message), and returns what ops.resize_u8_packed
+                  needs, with the frames' shapes.
 
-A pipeline calls queue(k + 1) before finish(k) and queues the rest of batch k after it, so the only device wait of the calling thread is
-for decode work queued a whole network pass earlier; with every status 0 the host decodes nothing.  Counters: `device` (decoded by the
+Every user goes through the stage, with or without device decoding: the two pipelines' device side (datasets/ring.py::DeviceRing), and
+predict_simple, which calls queue and finish back to back.  A pipeline that decodes on the device calls queue(k + 1) before finish(k) and
+queues the rest of batch k after it, so the only device wait of the calling thread is for decode work queued a whole network pass
+earlier; with every status 0 the host decodes nothing.  Counters: `device` (decoded by the
 device), `host_parser` (refused by the parser), `host_status` (decoded again after a non-zero status)."""
 import ctypes as C
 import io
@@ -25,6 +29,15 @@ import torch
 from .. import _lib, ops
 
 MAX_ROW_BYTES = 65528           # the resize stages one source row: max_w * 3 bytes (fp_resize_u8)
+SPIN = 0.0002                   # seconds between two queries of a device event (a batch takes milliseconds)
+
+
+def wait_event(event, stop, doing):
+    """wait for a device event as the pipelines' threads wait for everything: looking at the `stop` flag (may be None) in between"""
+    while not event.query():
+        if stop is not None and stop.is_set():
+            raise RuntimeError("the inference pipeline was stopped while a batch was %s" % doing)
+        time.sleep(SPIN)
 
 
 def host_decode(data):
@@ -61,8 +74,6 @@ def _decode_named(decode, data, path):
 
 class DecodeStage:
 
-    SPIN = 0.0002               # seconds between two queries of the event
-
     def __init__(self, batch_size, H, W, tables, device, decode=host_decode, stop=None):
         """tables: the device's ops.resize_table_set; decode: bytes -> uint8 [h, w, 3] (Pillow; tests inject a recording one); stop: a
         threading.Event the wait in `finish` looks at"""
@@ -71,21 +82,12 @@ class DecodeStage:
         self.counters = dict(device=0, host_parser=0, host_status=0)
 
     # ---- the slot's buffers -------------------------------------------------------------------------------------------------------------
-    def new_slot(self, s=None):
-        """the stage's part of a ring slot (a dict; a pipeline's own slot may be passed and gains the keys it lacks)"""
-        s = {} if s is None else s
+    def new_slot(self):
+        """the stage's part of a ring slot: a dict, to which a pipeline adds its own buffers"""
         rec_bytes = self.batch_size * C.sizeof(_lib.ResizeSample)
-        s.setdefault("src_cap", 0)
-        s.setdefault("h_src", None)
-        s.setdefault("d_src", None)
-        if "h_rec" not in s:
-            s["h_rec"] = self._pinned(rec_bytes, torch.uint8)
-            s["d_rec"] = self._empty(rec_bytes, torch.uint8)
-        s["h_status"] = self._pinned(self.batch_size + 1, torch.int32)
-        s["d_status"] = self._empty(self.batch_size + 1, torch.int32)
-        s["decoded"] = self._event()
-        s["batch"] = None
-        return s
+        return dict(src_cap=0, h_src=None, d_src=None, h_rec=self._pinned(rec_bytes, torch.uint8), d_rec=self._empty(rec_bytes, torch.uint8),
+                    h_status=self._pinned(self.batch_size + 1, torch.int32), d_status=self._empty(self.batch_size + 1, torch.int32),
+                    decoded=self._event(), batch=None)
 
     def _pinned(self, n, dtype):
         return torch.empty(n, dtype=dtype).pin_memory()
@@ -170,17 +172,19 @@ class DecodeStage:
         batch = self.fill(s, samples)
         pack = self.pack(batch)
         self._upload_records(s)
+        if pack is None:                                    # the host decoded every frame: they lie dense from 0, one copy
+            self._upload(s, 0, batch["total"])
+            return
         for b in batch["on_host"]:
-            self._upload(s, batch["offsets"][b], batch["shapes"][b])
-        if pack is not None:
-            self._decode(s, pack, batch)
+            h, w = batch["shapes"][b]
+            self._upload(s, batch["offsets"][b], h * w * 3)
+        self._decode(s, pack, batch)
         s["decoded"].record()
 
     def _upload_records(self, s):
         s["d_rec"].copy_(s["h_rec"], non_blocking=True)
 
-    def _upload(self, s, off, shape):
-        nbytes = shape[0] * shape[1] * 3
+    def _upload(self, s, off, nbytes):
         s["d_src"][off:off + nbytes].copy_(s["h_src"][off:off + nbytes], non_blocking=True)
 
     def _decode(self, s, pack, batch):
@@ -188,24 +192,19 @@ class DecodeStage:
         ops.jpeg_decode_packed(pack, out=s["d_src"], out_bytes=batch["total"], status=s["d_status"][:nd + 1], device=self.device)
         s["h_status"][:nd + 1].copy_(s["d_status"][:nd + 1], non_blocking=True)
 
-    def _wait(self, s):
-        while not s["decoded"].query():
-            if self.stop is not None and self.stop.is_set():
-                raise RuntimeError("the inference pipeline was stopped while a batch was being decoded")
-            time.sleep(self.SPIN)
-
     def _status(self, s, nd):
         return s["h_status"].numpy()[:nd].copy()
 
     def finish(self, s):
-        """wait for the batch's decode; Pillow decodes what the device turned down -> dict(src, total, records, n, max_h, max_w, status):
-        the arguments of ops.resize_u8_packed, and the device's status per sample (-1: decoded on the host from the start)"""
+        """wait for the batch's decode; Pillow decodes what the device turned down -> dict(src, total, records, n, max_h, max_w, shapes,
+        status): the arguments of ops.resize_u8_packed, the frames' (h, w) in the buffer's order, and the device's status per sample
+        (-1: decoded on the host from the start)"""
         batch = s["batch"]
         if batch is None:
             raise RuntimeError("DecodeStage.finish: no batch was queued on this slot")
         s["batch"] = None
         if batch["on_device"]:                              # nothing to wait for when the host decoded every frame
-            self._wait(s)
+            wait_event(s["decoded"], self.stop, "being decoded")
         status = [-1] * batch["n"]
         device_status = self._status(s, len(batch["on_device"])) if batch["on_device"] else []
         for b, st in zip(batch["on_device"], device_status):
@@ -220,7 +219,7 @@ class DecodeStage:
                 raise ValueError("%s: the header says %d x %d, Pillow decoded %r" % (smp.get("path", "sample %d" % b), h, w, frame.shape))
             off = batch["offsets"][b]
             s["h_src"].numpy()[off:off + h * w * 3] = frame.reshape(-1)
-            self._upload(s, off, (h, w))
+            self._upload(s, off, h * w * 3)
             self.counters["host_status"] += 1
         return dict(src=s["d_src"], total=batch["total"], records=s["d_rec"], n=batch["n"], max_h=batch["max_h"], max_w=batch["max_w"],
-                    status=status)
+                    shapes=batch["shapes"], status=status)

@@ -6,10 +6,11 @@ fp32 to the CPU and lets every `save_result` cast to float16.  Here the network 
 (`inference_scales`), the encoder BatchNorm is folded into the convolutions, and one kernel (`fp_pack_pred_fp16`) applies the
 sigmoid and rounds to float16 on the device, so the D2H copy is half the bytes and `save_result` writes the array as is.
 `run(loader)` is the blocking loop over a loader of resized tensors; `run_dataset(dataset, ...)` is the test-set program the command line
-runs (`main.py --mode inference`): the readers of datasets/inference.py, reader threads, a ring of pinned slots and a writer thread as in
-the segmentation Tester (datasets/ring.py), Resize + ToTensor on the device, one output launch (`fp_infer_pack`: the float16 array and the
-picture from one pass over the logits), and with `device_decode=True` the frames decoded on the device one batch ahead
-(datasets/decode_stage.py); PNG and what else the decoder does not take stays with Pillow.  In `test_batch` the reader's `Image.resize((W, H), LANCZOS)` + ToTensor
+runs (`main.py --mode inference`): the readers of datasets/inference.py, and the pipeline of datasets/ring.py that the segmentation
+Tester runs too -- reader threads, a ring of pinned slots, a writer thread (`RingPipeline`) and the whole device side (`DeviceRing`: the
+decode stage, Resize + ToTensor, network, output kernel, copies back, JPEG encoder); this class brings `_network` and one output launch
+(`fp_infer_pack`: the float16 array and the picture from one pass over the logits).  With `device_decode=True` the frames are decoded on
+the device one batch ahead (datasets/decode_stage.py); PNG and what else the decoder does not take stays with Pillow.  In `test_batch` the reader's `Image.resize((W, H), LANCZOS)` + ToTensor
 (datasets/inference_dataset.py:26,48) can run on the device: `InferenceManager(..., device_resize=True, height_width=(H, W))` takes
 `inputs['raw_image']`, the decoded uint8 frames at their native sizes, uploads them once and produces the same input tensor bit for bit.
 With `save_test_visualisations=True` (the reference's --save_test_visualisations, inference.py:110-119) `run` also writes <stem>.jpg: the
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..datasets.ring import RingPipeline
+from ..datasets.ring import DeviceRing, RingPipeline, full_resolution_heads
 from ..model_manager import ModelManager
 
 
@@ -46,7 +47,7 @@ class InferenceManager(RingPipeline):
         self.save_test_visualisations = bool(save_test_visualisations)
         self.device_jpeg = bool(device_jpeg)
         self.stage = None                               # run_dataset's decode stage: its counters are read by tests and benchmarks
-        self._ring = None
+        self.ring = None                                # run_dataset's device side (datasets/ring.py::DeviceRing)
         self._ring_init()
 
     @classmethod
@@ -104,108 +105,31 @@ class InferenceManager(RingPipeline):
                     Image.fromarray(vis[i]).save(os.path.join(self.savepath, "{}.jpg".format(inputs["idx"][i])), quality=95)
 
     # ---- the test-set pipeline ------------------------------------------------------------------------------------------------------------
-    def _make_ring(self, B, H, W, n_slots, visualise):
-        """the ring of run_dataset: per slot the decode stage's buffers (packed frames, records, status), the device outputs and the pinned
-        buffers the results come back through"""
-        from ..datasets.decode_stage import DecodeStage
-        if not torch.cuda.is_available():
-            raise RuntimeError("test-set inference has no CPU compute path: it needs a MI355X")
-        device = torch.device("cuda", torch.cuda.current_device())
-        device_jpeg = visualise and self.device_jpeg
-        key = (B, H, W, n_slots, visualise, device_jpeg, device)
-        if self._ring is not None and self._ring["key"] == key:
-            return self._ring
-        tables = ops.resize_table_set(device)
-        stage = DecodeStage(B, H, W, tables, device, stop=self._stop)
-        slots = []
-        for _ in range(n_slots):
-            s = stage.new_slot()
-            s.update(ready=torch.cuda.Event(), d_u8=torch.empty((B, H, W, 3), dtype=torch.uint8, device=device),
-                     d_half=torch.empty((B, 4, H, W), dtype=torch.float16, device=device),
-                     h_half=torch.empty((B, 4, H, W), dtype=torch.float16).pin_memory(), d_pic=None, h_pic=None)
-            if visualise:
-                s["d_pic"] = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8, device=device)
-            if device_jpeg:
-                s["d_scan"] = torch.empty(ops.jpeg_max_scan_bytes(B, H, 2 * W), dtype=torch.uint8, device=device)
-                s["d_tab"] = torch.empty((B + 1, 2), dtype=torch.int64, device=device)
-                s["h_tab"] = torch.empty((B + 1, 2), dtype=torch.int64).pin_memory()
-            elif visualise:
-                s["h_pic"] = torch.empty((B, H, 2 * W, 3), dtype=torch.uint8).pin_memory()
-            slots.append(s)
-        ring = dict(key=key, B=B, H=H, W=W, tables=tables, stage=stage, slots=slots, visualise=visualise, device_jpeg=device_jpeg)
-        if device_jpeg:
-            # the pictures of a batch lie dense in d_pic: one set of records serves every slot, and its first n a batch of n
-            ring["jpeg_records"] = torch.from_numpy(ops.jpeg_records([(H, 2 * W)] * B)[0]).to(device)
-            self.copy_stream = torch.cuda.Stream(device)
-            self.h_scan = None                      # the writer's pinned buffer for the bytes in use; grows
-        self._ring, self.stage = ring, stage
-        return ring
-
     def _network(self, image):
         """the logits [n, 4, H, W] of the full-resolution heads"""
         return self.model(image)["1/1"]
-
-    def _queue_rest(self, s, d):
-        """the batch lies packed in the slot's d_src (decode_stage.finish -> d): queue resize, ToTensor, network, fp_infer_pack and the
-        copies back into the slot's pinned buffers, and record the slot's `ready` event; nothing here waits for the device"""
-        r = self._ring
-        n, H, W = d["n"], r["H"], r["W"]
-        self.model.eval()
-        with torch.no_grad():
-            u8 = ops.resize_u8_packed(d["src"], d["total"], d["records"], n, H, W, 3, d["max_h"], d["max_w"], r["tables"], out=s["d_u8"][:n])
-            image = ops.to_tensor_u8(u8)
-            pred = self._network(image).contiguous()
-            ops.infer_pack(pred, image if r["visualise"] else None, want_picture=r["visualise"],
-                           out=(s["d_half"][:n], s["d_pic"][:n] if r["visualise"] else None))
-            s["h_half"][:n].copy_(s["d_half"][:n], non_blocking=True)
-            if r["device_jpeg"]:
-                ops.jpeg_encode_packed(s["d_pic"].view(-1), n * H * 2 * W * 3, r["jpeg_records"], n, 95, out=s["d_scan"], max_h=H, max_w=2 * W,
-                                       table=s["d_tab"][:n + 1])
-                s["h_tab"][:n + 1].copy_(s["d_tab"][:n + 1], non_blocking=True)
-            elif r["visualise"]:
-                s["h_pic"][:n].copy_(s["d_pic"][:n], non_blocking=True)
-            s["ready"].record()
-
-    def _collect(self, si, n):
-        """writer thread: wait for the slot's results -> (float16 numpy [n, 4, H, W], the n pictures -- uint8 [n, H, 2 W, 3], or the .jpg
-        files' bytes with device_jpeg -- or None)"""
-        r = self._ring
-        s = r["slots"][si]
-        self._wait_event(s["ready"])
-        if r["device_jpeg"]:
-            return s["h_half"].numpy()[:n], self._fetch_jpeg_files(s, n, (r["H"], 2 * r["W"]))
-        return s["h_half"].numpy()[:n], (s["h_pic"].numpy()[:n] if r["visualise"] else None)
 
     def run_dataset(self, dataset, batch_size, num_workers=4, slots=3, device_decode=False):
         """Every frame of `dataset` (datasets/inference.py) through the network at (dataset.height, dataset.width); its `save_result`
         writes <name>.npy, float16 [4, H, W], and with save_test_visualisations <name>.jpg, under self.savepath.  num_workers reader
         threads (at most 16) read ahead -- with device_decode only the bytes and the headers: baseline JPEG frames are decoded on the
         device one batch ahead (needs slots >= 2) -- the calling thread queues the batches on a ring of `slots` pinned slots, one writer
-        thread saves.  The files are the same with and without device_decode, byte for byte."""
+        thread saves.  The files are the same with and without device_decode, byte for byte.  -> the decode stage's counters"""
         B, H, W = int(batch_size), int(dataset.height), int(dataset.width)
         if B < 1:
             raise ValueError("batch_size must be at least 1")
         num_workers = min(max(int(num_workers or 1), 1), 16)
-        ring = self._make_ring(B, H, W, max(int(slots), 1), self.save_test_visualisations)
-        stage, ring_slots = ring["stage"], ring["slots"]
-        for key in stage.counters:
-            stage.counters[key] = 0
-        device_decode = bool(device_decode)
-
-        def both_parts(si, samples):
-            stage.queue(ring_slots[si], samples)
-            self._queue_rest(ring_slots[si], stage.finish(ring_slots[si]))
-
-        scales = getattr(self.model, "inference_scales", None)            # the model may be the caller's: its setting comes back
-        self.model.inference_scales = ("1/1",)
-        try:
-            self.run_ring(len(dataset), B, len(ring_slots), num_workers, read=lambda index: dataset.read(index, device_decode),
-                          ahead=(lambda si, samples: stage.queue(ring_slots[si], samples)) if device_decode else None,
-                          rest=(lambda si, samples: self._queue_rest(ring_slots[si], stage.finish(ring_slots[si]))) if device_decode else both_parts,
-                          collect=self._collect,
-                          save=lambda idx, results, i: dataset.save_result(idx, results[0][i], self.savepath,
-                                                                           results[1][i] if results[1] is not None else None),
-                          name="infer")
-        finally:
-            self.model.inference_scales = scales
-        return dict(stage.counters)
+        shape = (B, H, W, max(int(slots), 1), self.save_test_visualisations, self.save_test_visualisations and self.device_jpeg)
+        if self.ring is None or not self.ring.fits(*shape):             # a second run of the same shape reuses the ring and its stage
+            self.ring = DeviceRing(*shape[:4], channels=4, network=lambda image: self._network(image).contiguous(),
+                                   pack=lambda logits, image, want, half, pic: ops.infer_pack(logits, image, want_picture=want, out=(half, pic)),
+                                   visualise=shape[4], device_jpeg=shape[5], stop=self._stop)
+            self.stage = self.ring.stage
+        ring, device_decode = self.ring, bool(device_decode)
+        for key in self.stage.counters:
+            self.stage.counters[key] = 0
+        with full_resolution_heads(self.model):
+            self.run_ring(len(dataset), B, len(ring.slots), num_workers, read=lambda index: dataset.read(index, device_decode),
+                          ahead=ring.ahead, rest=ring.rest, collect=ring.collect,
+                          save=lambda idx, array, pic: dataset.save_result(idx, array, self.savepath, pic), one_ahead=device_decode, name="infer")
+        return dict(self.stage.counters)

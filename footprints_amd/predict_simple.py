@@ -18,7 +18,8 @@ on the host unless `--device_jpeg` (needs --device_vis) is given too: then a gro
 (with --device_vis) one overlay call and one copy of the overlays per group; the photos of a group may differ in size, and the same
 files are written under the same names.  `--device_decode` (needs --device_resize) reads the files' bytes and decodes the baseline
 JPEGs among them on the GPU (csrc/jpeg_decode.hip), straight into the packed buffer the resize and the overlay share -- the bytes Pillow
-decodes; every other file (PNG, progressive JPEG, ...) is decoded by Pillow and copied into the same buffer.  A batched forward pass
+decodes; every other file (PNG, progressive JPEG, ...) is decoded by Pillow and copied into the same buffer: the inference pipelines'
+decode stage (datasets/decode_stage.py), used blockingly on one slot.  A batched forward pass
 differs from per-image passes at fp32 round-off -- the small
 convolutions split their K loop by a rule that depends on the batch size -- so a .npy of a batched run is within the contract's 1e-4 of
 its channel maximum of the per-image one, not bit-equal; every overlay still equals `visualise` of its own .npy.
@@ -86,6 +87,7 @@ class InferenceManager:
         self.device_decode = bool(device_decode)
         if self.device_decode and not self.device_resize:
             raise ValueError("device_decode decodes into the buffer device_resize reads: it needs device_resize")
+        self._stage = self._slot = None                 # device_decode: the decode stage and its one slot, built at first use
         self.overlay_hook = None       # callable(file stem, uint8 [h, w, 3]): sees every overlay before it is encoded
         self.save_dir = save_dir
         os.makedirs(os.path.join(save_dir, "outputs"), exist_ok=True)
@@ -135,11 +137,10 @@ class InferenceManager:
         packed = None
         originals = None if self.device_decode else [pil_loader(p) for p in image_paths]
         if self.device_decode:
-            packed, total, shapes = self._decode_packed(image_paths)
-            originals = _LazyOriginals(packed, shapes)
-            tables = ops.resize_table_set("cuda")
-            records, _, max_h, max_w = ops.resize_records(shapes, h, w, tables)
-            x = ops.to_tensor_u8(ops.resize_u8_packed(packed, total, torch.from_numpy(records).cuda(), len(shapes), h, w, 3, max_h, max_w, tables))
+            d = self._decode_packed(image_paths)
+            packed = d["src"][:d["total"]]
+            originals = _LazyOriginals(packed, d["shapes"])
+            x = ops.to_tensor_u8(ops.resize_u8_packed(packed, d["total"], d["records"], d["n"], h, w, 3, d["max_h"], d["max_w"], self._stage.tables))
         elif self.device_resize:
             arrays = [np.asarray(o, dtype=np.uint8) for o in originals]
             tables = ops.resize_table_set("cuda")
@@ -171,30 +172,17 @@ class InferenceManager:
         return preds
 
     def _decode_packed(self, image_paths):
-        """the photos of a group, decoded into one device buffer, one after the other -> (buffer, bytes, shapes): baseline JPEGs on the
-        device from the files' bytes, everything else -- and a JPEG the device did not take -- by Pillow"""
-        import io
+        """the photos of a group, decoded into one device buffer, one after the other -> what DecodeStage.finish returns: baseline JPEGs
+        on the device from the files' bytes, everything else -- and a JPEG the device did not take -- by Pillow.  The decode stage of the
+        pipelines (datasets/decode_stage.py), on one slot the manager keeps, used blockingly"""
         from . import ops
-        files = []
-        for p in image_paths:
-            with open(p, "rb") as fh:
-                files.append(fh.read())
-        infos = [ops.jpeg_parse(f) for f in files]
-        decoded = {n: np.asarray(Image.open(io.BytesIO(f)).convert("RGB"), dtype=np.uint8) for n, (f, i) in enumerate(zip(files, infos))
-                   if not i["device"]}
-        shapes = [(i["h"], i["w"]) if i["device"] else decoded[n].shape[:2] for n, i in enumerate(infos)]
-        offsets = np.concatenate([[0], np.cumsum([sh[0] * sh[1] * 3 for sh in shapes])])
-        packed = torch.empty(int(offsets[-1]), dtype=torch.uint8, device="cuda")
-        on_device = [n for n, i in enumerate(infos) if i["device"]]
-        if on_device:
-            pack = ops.jpeg_decode_pack([files[n] for n in on_device], [infos[n] for n in on_device], [offsets[n] for n in on_device])
-            status = ops.jpeg_decode_packed(pack, out=packed)[2].cpu().numpy()          # waits
-            for j, n in enumerate(on_device):
-                if status[j] != 0:
-                    decoded[n] = np.asarray(Image.open(io.BytesIO(files[n])).convert("RGB"), dtype=np.uint8)
-        for n, arr in decoded.items():
-            packed[int(offsets[n]):int(offsets[n + 1])] = torch.from_numpy(np.array(arr, dtype=np.uint8).reshape(-1)).cuda()
-        return packed, int(offsets[-1]), shapes
+        from .datasets.decode_stage import DecodeStage, read_sample
+        if self._stage is None or len(image_paths) > self._stage.batch_size:
+            device = torch.device("cuda", torch.cuda.current_device())
+            self._stage = DecodeStage(max(len(image_paths), self.batch_size), *self.height_width, ops.resize_table_set(device), device)
+            self._slot = self._stage.new_slot()
+        self._stage.queue(self._slot, [read_sample(p, True) for p in image_paths])
+        return self._stage.finish(self._slot)
 
     def _encode_overlays(self, buffer, total, shapes):
         """the overlays of a group, lying in a device buffer -> (their .jpg files' bytes, the raw overlays for the hook or None)"""

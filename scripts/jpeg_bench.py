@@ -139,9 +139,8 @@ def main():
                 t.test()
                 t.dataset = MemoryKITTI(pool, args.frames)
             t = testers["pictures"]
-            t._device_half(t.slots[0], pool[:B])
-            torch.cuda.synchronize()
-            result["seg_pictures"] = encoder_alone(t.slots[0]["d_pic"].view(-1), B * H * 2 * W * 3, [(H, 2 * W)] * B, args.iters, args.rounds)
+            t.test_batch(pool[:B])
+            result["seg_pictures"] = encoder_alone(t.ring.slots[0]["d_pic"].view(-1), B * H * 2 * W * 3, [(H, 2 * W)] * B, args.iters, args.rounds)
             fps = {k: [] for k in testers}
             for _ in range(args.rounds):
                 for k, t in testers.items():

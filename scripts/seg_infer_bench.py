@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from footprints_amd import ops
+from footprints_amd.datasets.ring import full_resolution_heads
 from footprints_amd.preprocessing.segmentation.datasets.inference import KITTIInferenceDataset
 from footprints_amd.preprocessing.segmentation.inference import InferenceManager, Tester
 from footprints_amd.preprocessing.segmentation.network import Segmentor
@@ -53,10 +54,13 @@ def parent_route(manager, frames):
 
 
 def device_half_route(tester, frames):
-    for k in range(0, len(frames), B):
-        s = tester.slots[(k // B) % len(tester.slots)]
-        s["ready"].synchronize()              # as in test(): a slot's pinned buffers are refilled only after its copies have landed
-        tester._device_half(s, frames[k:k + B])
+    ring = tester.ring
+    with full_resolution_heads(tester.model):
+        for k in range(0, len(frames), B):
+            si = (k // B) % len(ring.slots)
+            ring.slots[si]["ready"].synchronize()              # as in test(): a slot's pinned buffers are refilled only after its copies have landed
+            ring.ahead(si, [{"image": f} for f in frames[k:k + B]])
+            ring.rest(si)
     torch.cuda.synchronize()
 
 

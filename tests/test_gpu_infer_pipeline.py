@@ -313,7 +313,7 @@ def test_segmentation_tester_with_device_decode(tmp_path, kitti):
                 print("pictures", pictures, tester.stage.counters)
                 assert tester.stage.counters == dict(device=5, host_parser=1, host_status=1)
             else:
-                assert tester.stage is None
+                assert tester.stage.counters == dict(device=0, host_parser=0, host_status=0)
         assert len(written[pictures, True]) == (14 if pictures else 7) and written[pictures, True] == written[pictures, False]
     # without the flag: what test_gpu_seg_infer.py pins -- seg_pack of the plain all-heads network on Pillow's frames, in the Tester's batches
     model.eval()

@@ -127,9 +127,9 @@ def _fake_stage(B, H, W, decode, status):
         def _event(self):
             return _Event()
 
-        def _upload(self, s, off, shape):
-            self.uploads.append((off, shape))
-            super()._upload(s, off, shape)
+        def _upload(self, s, off, nbytes):
+            self.uploads.append((off, nbytes))
+            super()._upload(s, off, nbytes)
 
         def _decode(self, s, pack, batch):
             self.launches.append(pack)
@@ -185,7 +185,7 @@ def test_decode_stage_host_half(tmp_path):
         off = batch["offsets"][b]
         assert np.array_equal(s["h_src"].numpy()[off:off + frames[b].size], frames[b].reshape(-1))
         assert np.array_equal(s["d_src"].numpy()[off:off + frames[b].size], frames[b].reshape(-1))
-    assert stage.uploads == [(batch["offsets"][2], (33, 45)), (batch["offsets"][3], (21, 17))]
+    assert stage.uploads == [(batch["offsets"][2], 33 * 45 * 3), (batch["offsets"][3], 21 * 17 * 3)]
     assert len(stage.launches) == 1
     pack = stage.launches[0]
     assert pack["B"] == 2 and pack["shapes"] == [(70, 231), (75, 248)]
@@ -196,10 +196,11 @@ def test_decode_stage_host_half(tmp_path):
     d = stage.finish(s)
     assert d["status"] == [0, 2, -1, -1] and calls[2:] == [files[1]]
     assert stage.counters == dict(device=1, host_parser=2, host_status=1)
-    assert stage.uploads[2:] == [(batch["offsets"][1], (75, 248))]
+    assert stage.uploads[2:] == [(batch["offsets"][1], 75 * 248 * 3)]
     off = batch["offsets"][1]
     assert np.array_equal(s["d_src"].numpy()[off:off + frames[1].size], frames[1].reshape(-1))
     assert (d["total"], d["n"], d["max_h"], d["max_w"]) == (total, 4, max_h, max_w) and d["src"] is s["d_src"] and d["records"] is s["d_rec"]
+    assert d["shapes"] == [f.shape[:2] for f in frames]
     with pytest.raises(RuntimeError):
         stage.finish(s)                                               # nothing queued
     # every status 0: the host decodes nothing more
@@ -208,6 +209,18 @@ def test_decode_stage_host_half(tmp_path):
     stage2.queue(s2, samples[:2])
     before = len(calls)
     assert stage2.finish(s2)["status"] == [0, 0] and len(calls) == before and stage2.counters == dict(device=2, host_parser=0, host_status=0)
+    # every frame decoded by the host, as without --device_decode: ONE upload of the bytes in use, no launch, nothing counted
+    stage3 = _fake_stage(4, H, W, decode, status=[])
+    s3 = stage3.new_slot()
+    stage3.queue(s3, [{"image": f} for f in frames])
+    assert stage3.uploads == [(0, total)] and stage3.launches == [] and s3["batch"]["on_device"] == []
+    assert np.array_equal(s3["h_rec"].numpy()[:records.size], records)
+    for f, off in zip(frames, s3["batch"]["offsets"]):
+        assert np.array_equal(s3["d_src"].numpy()[off:off + f.size], f.reshape(-1))
+    assert np.array_equal(s3["d_src"].numpy()[:total], packed[:total])
+    d3 = stage3.finish(s3)
+    assert d3["status"] == [-1] * 4 and (d3["total"], d3["n"], d3["max_h"], d3["max_w"]) == (total, 4, max_h, max_w)
+    assert stage3.uploads == [(0, total)] and len(calls) == before and stage3.counters == dict(device=0, host_parser=0, host_status=0)
 
 
 def test_decode_stage_limits_and_errors(tmp_path):

@@ -1,6 +1,6 @@
 """The segmentation network's inference mode without a GPU: the NumPy restatement of fp_seg_pack against what the reference's own
 Tester.test_batch, save_result and matplotlib wrote (tests/golden/g17_seg_infer.npz), the inference datasets' parsing and file layout,
-the command line's way into Tester, and the pipeline's bookkeeping with a stub in place of the device half."""
+the command line's way into Tester, and the pipeline's bookkeeping with a stub in place of the device side, in both schedules."""
 import argparse
 import os
 import threading
@@ -148,40 +148,51 @@ class _MemoryDataset:
             self.saved.append((index, np.array(prediction), None if visualisation is None else np.array(visualisation), savepath))
 
 
-def _stub_tester(dataset, batch_size=3, slots=2, visualise=True, num_workers=3):
+class _StubRing:
+    """the device side echoes a function of the frame into the slot's buffers; a slot refilled while the writer still owns it trips"""
+
+    def __init__(self, owner):
+        self.owner, self.stage = owner, None
+        self.slots = [dict(half=np.zeros((owner.batch_size, 1, 2, 3), np.float16), pic=np.zeros((owner.batch_size, 2, 6, 3), np.uint8), frames=None)
+                      for _ in range(owner.n_slots)]
+
+    def ahead(self, si, samples):
+        if self.owner.busy[si]:
+            self.owner.trips.append(si)
+        self.owner.busy[si] = True
+        self.slots[si]["frames"] = [smp["image"] for smp in samples]
+
+    def rest(self, si):
+        s = self.slots[si]
+        for j, f in enumerate(s["frames"]):
+            s["half"][j] = np.float16(f[0, 0, 0]) / np.float16(256)
+            s["pic"][j] = f[0, 0, 0]
+        s["frames"] = None
+
+    def collect(self, si, n):
+        s = self.slots[si]
+        return s["half"][:n], (s["pic"][:n] if self.owner.visualise else None)
+
+
+def _stub_tester(dataset, batch_size=3, slots=2, visualise=True, num_workers=3, one_ahead=False):
+    """one_ahead: the two-part schedule of --device_decode (batch k + 1's `ahead` before batch k's `rest`), on the same in-memory frames"""
     from footprints_amd.preprocessing.segmentation.inference import Tester
 
     class StubTester(Tester):
-        """the device half echoes a function of the frame into the slot's buffers; a slot refilled while the writer still owns it trips"""
-
-        def _make_slots(self):
+        def _new_ring(self):
             self.busy = [False] * self.n_slots
             self.trips = []
-            return [dict(i=i, half=np.zeros((self.batch_size, 1, 2, 3), np.float16), pic=np.zeros((self.batch_size, 2, 6, 3), np.uint8))
-                    for i in range(self.n_slots)]
+            return _StubRing(self)
 
-        def _device_half(self, s, frames):
-            if self.busy[s["i"]]:
-                self.trips.append(s["i"])
-            self.busy[s["i"]] = True
-            for j, f in enumerate(frames):
-                s["half"][j] = np.float16(f[0, 0, 0]) / np.float16(256)
-                s["pic"][j] = f[0, 0, 0]
+        def _read(self, index):
+            return self.dataset[index]
 
-        def _wait_slot(self, s, n):
-            return s["half"][:n], (s["pic"][:n] if self.visualise else None)
+        def _release(self, free, si):         # the slot stops being busy exactly where the real writer hands it back
+            self.busy[si] = False
+            super()._release(free, si)
 
-        def _writer(self, jobs, free):
-            class Free:                       # the slot stops being busy exactly where the real writer hands it back
-                def __init__(self, ev, owner, i):
-                    self.ev, self.owner, self.i = ev, owner, i
-
-                def set(self):
-                    self.owner.busy[self.i] = False
-                    self.ev.set()
-            super()._writer(jobs, [Free(ev, self, i) for i, ev in enumerate(free)])
-
-    opt = argparse.Namespace(height=2, width=3, batch_size=batch_size, num_workers=num_workers, save_test_visualisations=visualise)
+    opt = argparse.Namespace(height=2, width=3, batch_size=batch_size, num_workers=num_workers, save_test_visualisations=visualise,
+                             device_decode=one_ahead)
 
     class Model:
         def eval(self):
@@ -189,10 +200,10 @@ def _stub_tester(dataset, batch_size=3, slots=2, visualise=True, num_workers=3):
     return StubTester(opt, model=Model(), dataset=dataset, save_path="/nowhere", slots=slots)
 
 
-def test_pipeline_writes_every_index_once_with_its_own_data():
+def test_pipeline_writes_every_index_once_with_its_own_data(one_ahead=False):
     """5 batches of 3 and a tail of 1 through 2 slots, the writer slower than the device half"""
     ds = _MemoryDataset(16, slow_save=0.002)
-    t = _stub_tester(ds)
+    t = _stub_tester(ds, one_ahead=one_ahead)
     t.test()
     assert sorted(s[0] for s in ds.saved) == list(range(16)) and t.trips == []
     for index, pred, vis, savepath in ds.saved:
@@ -202,30 +213,39 @@ def test_pipeline_writes_every_index_once_with_its_own_data():
     assert not [th for th in threading.enumerate() if th.name.startswith("seg-infer")]
 
 
-def test_pipeline_without_pictures_and_workers_clamped():
+def test_pipeline_without_pictures_and_workers_clamped(one_ahead=False):
+    """the smallest ring: 1 slot, or the 2 slots that decoding one batch ahead needs"""
     ds = _MemoryDataset(4)
-    t = _stub_tester(ds, batch_size=3, slots=1, visualise=False, num_workers=999)
+    t = _stub_tester(ds, batch_size=3, slots=2 if one_ahead else 1, visualise=False, num_workers=999, one_ahead=one_ahead)
     assert t.num_workers == 16
     t.test()
     assert sorted(s[0] for s in ds.saved) == [0, 1, 2, 3] and all(s[2] is None for s in ds.saved)
 
 
-def test_pipeline_reader_error_ends_test():
+def test_pipeline_reader_error_ends_test(one_ahead=False):
     ds = _MemoryDataset(16, fail_at=7)
-    t = _stub_tester(ds)
+    t = _stub_tester(ds, one_ahead=one_ahead)
     with pytest.raises(OSError, match="frame 7"):
         t.test()
     assert not [th for th in threading.enumerate() if th.name.startswith("seg-infer")]          # nothing is left waiting
     assert all(s[0] < 6 for s in ds.saved)                                                      # batches in front of the failing one only
 
 
-def test_pipeline_writer_error_ends_test():
+def test_pipeline_writer_error_ends_test(one_ahead=False):
     ds = _MemoryDataset(16)
 
     def save_result(index, prediction, savepath, visualisation=None):
         raise OSError("disk full")
     ds.save_result = save_result
-    t = _stub_tester(ds)
+    t = _stub_tester(ds, one_ahead=one_ahead)
     with pytest.raises(OSError, match="disk full"):
         t.test()
     assert not [th for th in threading.enumerate() if th.name.startswith("seg-infer")]
+
+
+@pytest.mark.parametrize("check", [test_pipeline_writes_every_index_once_with_its_own_data, test_pipeline_without_pictures_and_workers_clamped,
+                                   test_pipeline_reader_error_ends_test, test_pipeline_writer_error_ends_test],
+                         ids=lambda check: check.__name__[len("test_pipeline_"):])
+def test_pipeline_one_ahead(check):
+    """the same four with the schedule both pipelines take with --device_decode: batch k + 1's `ahead` before batch k's `rest`"""
+    check(one_ahead=True)
