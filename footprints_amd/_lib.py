@@ -220,6 +220,10 @@ SIGNATURES = {
     "fp_gt_plane_score": (C.c_int, [_P, _P, _D, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "fp_gt_flatten_splat": (C.c_int, [_P, _P, _D, _P, _P, _I32, _I32, _P, _I64, _P, _P]),
     "fp_gt_depth_mask": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "fp_baseline_hull": (C.c_int, [_P, _I32, _D, _P, _I32, _P, _I32, _D, _I32, _I32, _I32, _P, _P, _P]),
+    "fp_baseline_mask_counts": (C.c_int, [_P, _I32, _D, _I32, _I32, _I32, _P, _P]),
+    "fp_baseline_plane_fit": (C.c_int, [_P, _P, _P, _I32, _D, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "fp_baseline_plane_depth": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
     "fp_pack_pred_fp16": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "fp_colsum_workspace": (_I64, [_I64, _I32]),
     "fp_colsum": (C.c_int, [_P, _I64, _I32, _P, C.c_int, _P, _I64, _P]),

@@ -5,7 +5,8 @@ reductions (`fp_eval_mask_counts`: integer confusion counts, `fp_eval_depth_sums
 and the host turns them into the same per-image dictionaries (`iou / precision / recall / f1`, `a1 / abs_rel / sq_rel / rmse`,
 nan where the reference returns nan) and the same nan-means.  Thresholds and dtypes follow the reference: float16 predictions
 (the inference pass's file format) are thresholded and converted to depth in float16 like numpy does.
-Ground-truth download and the Matterport convex-hull pre-processing stay outside this build.
+A KITTI folder may hold a baseline's `<n>_ground_mask.png` files (footprints_amd/baselines/) in place of `<n:03d>.npy`; they are read
+as the reference reads them.  Ground-truth download stays outside this build.
 """
 import os
 
@@ -114,17 +115,24 @@ def evaluate(pred_folder, datatype, metric, ground_truth_dir, split_file="splits
     all_scores = []
     for i in range(0, len(names), batch):
         P, G, F = [], [], []
+        masks = False
         for name in names[i:i + batch]:
             if datatype == "kitti":
                 d = os.path.join(ground_truth_dir, "kitti_ground_truth", "kitti_ground_truth")
                 G.append(_load_mask(os.path.join(d, "{:05d}_combined.png".format(name))))
                 F.append(_load_mask(os.path.join(d, "{:05d}_ground.png".format(name))))
-                P.append(np.load(os.path.join(pred_folder, "{:03d}.npy".format(name))))
+                try:
+                    P.append(np.load(os.path.join(pred_folder, "{:03d}.npy".format(name))))
+                except FileNotFoundError:               # a baseline's mask (evaluate_model.py:152-157)
+                    P.append(_load_mask(os.path.join(pred_folder, "{:d}_ground_mask.png".format(name))).astype(np.float32))
+                    masks = True
             else:
                 d = os.path.join(ground_truth_dir, "matterport_ground_truth", "matterport_ground_truth")
                 G.append(np.load(os.path.join(d, "{}_{}_{}_{}_groundtruth.npy".format(*name))))
                 F.append(np.load(os.path.join(d, "{}_{}_{}_{}_freespace.npy".format(*name))) > 0.5)
                 P.append(np.load(os.path.join(pred_folder, "{}".format(name[0]), "{}_{}_{}.npy".format(*name[1:]))))
+        if masks:                                       # a batch that mixes both kinds: the hidden-ground channel of the arrays
+            P = [p[HIDDEN_GROUND] if p.ndim == 3 else p for p in P]
         scores, _ = evaluate_arrays(np.stack(P), np.stack(G), np.stack(F), metric, batch=batch)
         all_scores += scores
     return summarise(all_scores, metric)

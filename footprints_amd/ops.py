@@ -1012,6 +1012,92 @@ def gt_depth_mask(keys, depth, ground_seg, want_projection=False):
     return (mask.view(torch.bool), proj) if want_projection else mask.view(torch.bool)
 
 
+# ---- the paper's comparison baselines (csrc/baselines.hip; semantics in include/footprints_hip.h) --------------------------------------
+_BASELINE_DTYPES = {torch.uint8: 0, torch.bool: 0, torch.float16: 1, torch.float32: 2}
+
+
+def _baseline_mask(t, threshold, name, shape=None):
+    """-> (pointer, dtype code, threshold) of a [B,H,W] mask: uint8 / bool (non-zero is set) or float16 / float32 with a threshold"""
+    if t.dtype not in _BASELINE_DTYPES:
+        raise RuntimeError("footprints_amd.ops: %s must be uint8, bool, float16 or float32" % name)
+    if t.dim() != 3 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError("footprints_amd.ops: %s must be [B, H, W]%s" % (name, "" if shape is None else " = %s" % (tuple(shape),)))
+    code = _BASELINE_DTYPES[t.dtype]
+    if code and threshold is None:
+        raise RuntimeError("footprints_amd.ops: a floating-point %s needs a threshold" % name)
+    return _chk(t, name), code, float(threshold) if code else 0.0
+
+
+def convex_hull_mask(x, threshold=None, remove=None, keep=None):
+    """x [B,H,W] uint8 / bool, or float16 / float32 with `threshold` (x > threshold in x's dtype) -> uint8 [B,H,W], each frame
+    skimage.morphology.convex_hull_image of its mask (zeros for an empty one), exact.  BoundingBox's epilogue in the same pass:
+    pixels with `remove` < 0.5 are cleared, then pixels set in `keep` (a mask like x, same threshold) are set."""
+    xp, xd, xt = _baseline_mask(x, threshold, "mask")
+    B, H, W = x.shape
+    rp = rd = kp = kd = 0
+    kt = 0.0
+    if remove is not None:
+        rp, rd, _ = _baseline_mask(remove, 0.5, "remove", x.shape)
+    if keep is not None:
+        kp, kd, kt = _baseline_mask(keep, threshold, "keep", x.shape)
+    spans = torch.empty((B, H, 2), dtype=torch.int32, device=x.device)
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().fp_baseline_hull(xp, xd, xt, rp or None, rd, kp or None, kd, kt, B, H, W, _chk(spans), _chk(out), stream()),
+               "fp_baseline_hull")
+    return out
+
+
+def baseline_mask_counts(x, threshold=None):
+    """set pixels of every frame of the mask x [B,H,W] -> int32 [B] on the device"""
+    xp, xd, xt = _baseline_mask(x, threshold, "mask")
+    B, H, W = x.shape
+    counts = torch.empty(B, dtype=torch.int32, device=x.device)
+    _lib.check(_lib.load().fp_baseline_mask_counts(xp, xd, xt, B, H, W, _chk(counts), stream()), "fp_baseline_mask_counts")
+    return counts
+
+
+def _baseline_frames(depth, inv_K):
+    B, H, W = depth.shape
+    if tuple(inv_K.shape) != (B, 3, 3):
+        raise RuntimeError("footprints_amd.ops: inv_K must be float64 [%d, 3, 3]" % B)
+    return _f32(depth, "depth"), _typed(inv_K, torch.float64, "inv_K"), B, H, W
+
+
+def baseline_plane_fit(depth, inv_K, mask, samples, threshold=0.5):
+    """ransac.run_ransac over a batch: depth float32 [B,H,W], inv_K float64 [B,3,3], mask [B,H,W] (see convex_hull_mask), samples int32
+    [B,C,3] = ranks into each frame's masked pixels in raster order -> dict of sample_pix [B,C,3], planes float64 [B,C,4] (unit 4-vectors),
+    counts int32 [B,C], best int32 [B,2] = (index, count) and best_plane float64 [B,4]"""
+    d, iK, B, H, W = _baseline_frames(depth, inv_K)
+    mp, md, mt = _baseline_mask(mask, threshold, "mask", depth.shape)
+    if samples.dim() != 3 or samples.shape[0] != B or samples.shape[2] != 3:
+        raise RuntimeError("footprints_amd.ops.baseline_plane_fit: samples must be int32 [B, C, 3]")
+    s = _typed(samples, torch.int32, "samples")
+    C_, dev = samples.shape[1], depth.device
+    out = {"sample_pix": torch.empty((B, C_, 3), dtype=torch.int32, device=dev), "planes": torch.empty((B, C_, 4), dtype=torch.float64, device=dev),
+           "counts": torch.empty((B, C_), dtype=torch.int32, device=dev), "best": torch.empty((B, 2), dtype=torch.int32, device=dev),
+           "best_plane": torch.empty((B, 4), dtype=torch.float64, device=dev)}
+    _lib.check(_lib.load().fp_baseline_plane_fit(d, iK, mp, md, mt, s, C_, B, H, W, _chk(out["sample_pix"]), _chk(out["planes"]), _chk(out["counts"]),
+                                                 _chk(out["best_plane"]), _chk(out["best"]), stream()), "fp_baseline_plane_fit")
+    return out
+
+
+def baseline_plane_depth(depth, inv_K, best_plane, passthrough=None):
+    """depth of the plane along every pixel's ray (footprint_baseline.ransac_depth_inpaint): float64 [B,H,W]; frames with a non-zero
+    `passthrough` (uint8 / bool [B]) get their input depth"""
+    d, iK, B, H, W = _baseline_frames(depth, inv_K)
+    if tuple(best_plane.shape) != (B, 4):
+        raise RuntimeError("footprints_amd.ops.baseline_plane_depth: best_plane must be float64 [B, 4]")
+    pl = _typed(best_plane, torch.float64, "best_plane")
+    pt = None
+    if passthrough is not None:
+        if passthrough.dtype not in (torch.uint8, torch.bool) or tuple(passthrough.shape) != (B,):
+            raise RuntimeError("footprints_amd.ops.baseline_plane_depth: passthrough must be uint8 or bool [B]")
+        pt = _chk(passthrough, "passthrough")
+    out = torch.empty((B, H, W), dtype=torch.float64, device=depth.device)
+    _lib.check(_lib.load().fp_baseline_plane_depth(d, iK, pl, pt, B, H, W, _chk(out), stream()), "fp_baseline_plane_depth")
+    return out
+
+
 # ---- reader work on the device: Pillow's 8-bit resize (csrc/resample_u8.hip) and filter_depth_mask (csrc/reader.hip) ------------------
 RESIZE_FILTERS = {"lanczos": _lib.RESIZE_LANCZOS, "bilinear": _lib.RESIZE_BILINEAR, "bicubic": _lib.RESIZE_BICUBIC, "box": _lib.RESIZE_BOX}
 _resize_host_tables = {}

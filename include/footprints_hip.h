@@ -420,6 +420,34 @@ int fp_gt_flatten_splat(const float* world, const float* ground_seg, double thre
 int fp_gt_depth_mask(const uint64_t* keys, const float* depth, const float* ground_seg, int32_t H, int32_t W, uint8_t* mask,
                      float* projection, fp_stream_t stream);
 
+/* ---- the paper's comparison baselines (csrc/baselines.hip; reference footprints/baselines/) ----------
+ * A mask argument is a pointer with a dtype code: 0 = uint8 (non-zero is set), 1 = float16, 2 = float32 (value > threshold, compared
+ * in the mask's own dtype as numpy compares an array with a Python scalar).  All arrays are [B][H][W] unless stated.
+ * fp_baseline_hull: out uint8 = skimage.morphology.convex_hull_image(mask) with its defaults for every frame (zeros for an empty mask),
+ * in exact integer arithmetic on doubled coordinates; then, in the same pass, pixels with remove < 0.5 (optional, any dtype code) are
+ * cleared and pixels set in keep (optional mask with its own threshold) are set -- BoundingBox.frame_predict's order.  spans int32
+ * [B][H][2] is caller-owned scratch that receives each row's inclusive column span {lo, hi} of the hull (lo > hi: empty row).
+ * H <= 2040, W <= 32768.  Three launches for any B.
+ * fp_baseline_mask_counts: counts int32 [B] = set pixels per frame.
+ * fp_baseline_plane_fit: points are depth * (inv_K . (x, y, 1)) in float64 (depth fp32, inv_K float64 [B][3][3]); samples int32
+ * [B][C][3], C <= 100, are ranks into the frame's masked pixels in raster order (the host draws them); sample_pix [B][C][3] receives
+ * their pixel indices (-1: out of range), planes float64 [B][C][4] the unit 4-vectors spanning the null space of the three augmented
+ * sample points (ransac.estimate up to sign; all zero for a sample that repeats a rank, has a rank out of range or whose minors are
+ * all zero -- such a candidate scores 0), counts [B][C] the masked points with |m . (p, 1)| < 0.05, best [B][2] = {index, count} of the
+ * first candidate with the strictly largest count ({-1, 0} when every count is 0) and best_plane [B][4] its vector.  Three launches.
+ * fp_baseline_plane_depth: out float64 = depth - (m . (p, 1)) / (rhat . m[:3]) at EVERY pixel, rhat the normalised ray, m =
+ * best_plane[b]; a frame with passthrough[b] != 0 (optional uint8 [B]; the host sets it for fewer than 20 masked pixels) gets its depth. */
+int fp_baseline_hull(const void* x, int32_t dtype, double threshold, const void* remove, int32_t remove_dtype, const void* keep,
+                     int32_t keep_dtype, double keep_threshold, int32_t B, int32_t H, int32_t W, int32_t* spans, uint8_t* out,
+                     fp_stream_t stream);
+int fp_baseline_mask_counts(const void* x, int32_t dtype, double threshold, int32_t B, int32_t H, int32_t W, int32_t* counts,
+                            fp_stream_t stream);
+int fp_baseline_plane_fit(const float* depth, const double* inv_K, const void* mask, int32_t dtype, double threshold,
+                          const int32_t* samples, int32_t C, int32_t B, int32_t H, int32_t W, int32_t* sample_pix, double* planes,
+                          int32_t* counts, double* best_plane, int32_t* best, fp_stream_t stream);
+int fp_baseline_plane_depth(const float* depth, const double* inv_K, const double* best_plane, const uint8_t* passthrough, int32_t B,
+                            int32_t H, int32_t W, double* out, fp_stream_t stream);
+
 /* ---- maxpool 3x3 stride 2 pad 1 (encoder.maxpool, network.py:41) ---------- */
 int fp_maxpool_fwd(const float* x, float* y, uint8_t* argmax, int32_t N, int32_t H, int32_t W, int32_t C,
                    const fp_aux* aux, fp_stream_t stream);
