@@ -64,6 +64,22 @@ class ResizeSample(C.Structure):
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("table_h", C.c_int32), ("table_v", C.c_int32)]
 
 
+LABEL_U8, LABEL_F16, LABEL_F32, LABEL_F64 = range(4)        # FP_LABEL_*: stored dtype of a label map
+LABEL_ZERO, LABEL_NEAREST, LABEL_AREA = range(3)            # FP_LABEL_*: resize method
+LABEL_MAX_ENTRIES = 12                                      # FP_LABEL_MAX_ENTRIES
+
+
+class LabelSample(C.Structure):
+    """fp_label_sample (include/footprints_hip.h)"""
+    _fields_ = [("offset", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "dtype", "method", "flip", "table_x", "table_y", "pad")] + [
+        ("multiplier", C.c_double)]
+
+
+class LabelTable(C.Structure):
+    """fp_label_table (include/footprints_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("in_size", "out_size", "max_count", "n_entries", "bounds_off", "entries_off")]
+
+
 JPEG_TABLE_WORDS = 672            # fp_jpeg_table_words()
 
 
@@ -138,6 +154,11 @@ SIGNATURES = {
     "fp_seg_labels": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _I64, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _P]),
     "fp_filter_depth_mask_workspace": (_I64, [_I32, _I32, _I32]),
     "fp_filter_depth_mask": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_label_sample_bytes": (_I32, []),
+    "fp_label_table_bytes": (_I32, []),
+    "fp_label_max_entries": (_I32, []),
+    "fp_area_table": (_I32, [_I32, _I32, _P, _P, _P, _I32]),
+    "fp_label_resize": (C.c_int, [_P, _I64, _P, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _I32, _P, _P]),
     "fp_resize_coeffs_f64": (C.c_int, [_I32, _I32, _I32, _P, _P, _I32]),
     "fp_vis_overlay_workspace": (_I64, [_I32, _I32, _I32, _I32, _I32]),
     "fp_vis_overlay_status_offset": (_I64, [_I32, _I32, _I32, _I32, _I32]),

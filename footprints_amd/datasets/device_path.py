@@ -9,8 +9,12 @@ host only hands over what the file readers produce -- the resized uint8 image an
 Two more pieces of the reader can run on the device, both opt-in (csrc/reader.hip): with `raw_images=True` a sample's image is the DECODED
 frame at its native size (KITTI frames come in several) and `Image.resize((W, H), LANCZOS)` (footprint_dataset.py:73-80) runs in front of
 the flip and the jitter, in the reference's order and byte for byte Pillow's 8-bit path; with `filter_depth_mask=True` the depth mask
-arrives unfiltered and the connected-components filter (footprint_dataset.py:96-105) runs in front of the label algebra.  The cv2 resizes
-of the label maps (INTER_AREA / INTER_NEAREST on float64, footprint_dataset.py:82-94) stay on the host: no cv2 was at hand to pin them.
+arrives unfiltered and the connected-components filter (footprint_dataset.py:96-105) runs in front of the label algebra.  With
+`raw_maps=True` a sample's label maps are the arrays as `np.load` returns them -- native size, stored dtype, not flipped -- and the cv2
+resizes (INTER_AREA / INTER_NEAREST on float64, footprint_dataset.py:82-94, with the fliplr in front and the disparity multiplier behind)
+run in one launch in front of the filter (csrc/label_resize.hip).  No cv2 was at hand to pin them: the kernel equals, bit for bit, a
+restatement of OpenCV's algorithm (tests/label_resize_restatement.py), which is anchored on the exact area average; INTER_AREA is built
+for shrinking or equal sizes only -- where it would enlarge an axis cv2 switches to a linear kernel, and the pack refuses the map.
 
 Random decisions stay on the host and consume Python's `random` exactly like the reference does (flip draw, colour-aug draw, then
 torchvision 0.4.2's ColorJitter.get_params: four uniforms in the order brightness, contrast, saturation, hue and one shuffle), so a
@@ -28,6 +32,10 @@ BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
 JITTER_RANGES = ((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.1, 0.1))          # footprint_dataset.py:37-40
 MAP_KEYS = {"kitti": ("visible_ground", "ground_depth", "depth_mask", "disparity", "moving_objects"),
             "matterport": ("visible_ground", "ground_depth", "depth_mask", "depth_raw")}
+# cv2.resize's interpolation per map in the reference (kitti_dataset.py:67-105, matterport_dataset.py:57-82); Matterport's raw depth arrives
+# at the target size (Pillow's NEAREST on the reader thread) and is copied
+MAP_METHODS = {"visible_ground": "area", "ground_depth": "area", "depth_mask": "nearest", "disparity": "area", "moving_objects": "nearest",
+               "depth_raw": "nearest"}
 OUT_KEYS = ("visible_ground", "depth", "ground_depth", "moving_object_mask", "depth_mask", "all_ground")
 
 
@@ -141,16 +149,27 @@ class DeviceBatchAssembler(SlotAssembler):
 
     raw_images=True: the image of a sample is the decoded frame uint8 [h,w,3] at its native size, any h <= max_src_hw[0] and
     w <= max_src_hw[1] (they size the staging buffers), and is resized with Pillow's LANCZOS on the device.  filter_depth_mask=True:
-    the depth mask of a sample is the unfiltered one (zeros and ones)."""
+    the depth mask of a sample is the unfiltered one (zeros and ones).  raw_maps=True (needs map_dtype float64): the maps of a sample are
+    the arrays as loaded -- any h <= max_map_hw[0] and w <= max_map_hw[1], uint8 / bool / float16 / float32 / float64 (anything else is
+    converted to float64 first), None for a missing depth mask -- and are resized on the device with cv2's INTER_AREA / INTER_NEAREST per
+    MAP_METHODS; every other map must be present (a KeyError names a missing one).  max_map_itemsize (8 = float64 maps) is the stored
+    element the staging buffers are sized for at the start; a batch that needs more makes its slot's buffers grow."""
 
     def __init__(self, batch_size, height, width, dataset="kitti", map_dtype=np.float64, slots=3, no_depth_mask=False,
                  project_down_baseline=False, moving_objects_method="ours", footprint_threshold=0.75, baseline=0.54,
-                 depth_scaling=0.25e-3, device="cuda", stream=None, raw_images=False, max_src_hw=None, filter_depth_mask=False):
+                 depth_scaling=0.25e-3, device="cuda", stream=None, raw_images=False, max_src_hw=None, filter_depth_mask=False,
+                 raw_maps=False, max_map_hw=None, max_map_itemsize=8, check=False):
         if dataset not in MAP_KEYS:
             raise ValueError("dataset must be 'kitti' or 'matterport'")
         if raw_images and (max_src_hw is None or min(max_src_hw) <= 0):
             raise ValueError("raw_images=True needs max_src_hw=(largest source height, largest source width)")
-        self.raw_images, self.filter_mask = bool(raw_images), bool(filter_depth_mask)
+        if raw_maps and (max_map_hw is None or min(max_map_hw) <= 0):
+            raise ValueError("raw_maps=True needs max_map_hw=(largest map height, largest map width)")
+        if raw_maps and np.dtype(map_dtype) != np.dtype(np.float64):
+            raise ValueError("raw_maps=True needs map_dtype=float64: the device resize restates cv2's float64 arithmetic")
+        self.raw_images, self.filter_mask, self.raw_maps = bool(raw_images), bool(filter_depth_mask), bool(raw_maps)
+        self.max_map_hw = tuple(int(v) for v in max_map_hw) if raw_maps else None
+        self.check = bool(check)          # read fp_label_resize's status word after every launch (this WAITS for the stream): tests, debugging
         self.max_src_hw = tuple(int(v) for v in max_src_hw) if raw_images else None
         _lib.load()
         assert _lib.load().fp_aug_params_bytes() == C.sizeof(AugParams)
@@ -170,13 +189,18 @@ class DeviceBatchAssembler(SlotAssembler):
         npx = batch_size * height * width
         tdt = torch.float64 if self.map_dtype == np.float64 else torch.float32
         self.tables = ops.resize_table_set(self.device) if self.raw_images else None
+        self.map_tables = ops.label_table_set(self.device) if self.raw_maps else None
+        if self.raw_maps:
+            lib = _lib.load()
+            assert lib.fp_label_sample_bytes() == C.sizeof(_lib.LabelSample) and lib.fp_label_table_bytes() == C.sizeof(_lib.LabelTable)
         for _ in range(slots):
             h_img = torch.empty((batch_size, height, width, 3), dtype=torch.uint8).pin_memory()
-            h_maps = torch.empty((len(self.keys), batch_size, height, width), dtype=tdt).pin_memory()
+            h_maps = torch.empty((0 if self.raw_maps else len(self.keys), batch_size, height, width), dtype=tdt).pin_memory()
             h_par = torch.empty(batch_size * C.sizeof(AugParams), dtype=torch.uint8).pin_memory()
             self._add_slot(
                 h_img=h_img, h_maps=h_maps, h_par=h_par,
-                d_img=torch.empty_like(h_img, device=self.device), d_maps=torch.empty_like(h_maps, device=self.device),
+                d_img=torch.empty_like(h_img, device=self.device),
+                d_maps=torch.empty((len(self.keys), batch_size, height, width), dtype=tdt, device=self.device),
                 d_par=torch.empty_like(h_par, device=self.device), sums=torch.zeros(batch_size, dtype=torch.int64, device=self.device),
                 image=torch.empty((batch_size, 3, height, width), device=self.device),
                 out=torch.empty((len(OUT_KEYS), batch_size, height, width), device=self.device))
@@ -185,12 +209,21 @@ class DeviceBatchAssembler(SlotAssembler):
                 h_rec = torch.empty(batch_size * C.sizeof(_lib.ResizeSample), dtype=torch.uint8).pin_memory()
                 self.slots[-1].update(h_src=h_src, h_rec=h_rec, d_src=torch.empty_like(h_src, device=self.device),
                                       d_rec=torch.empty_like(h_rec, device=self.device), src_bytes=0)
+            if self.raw_maps:               # the packed native-size maps and their fp_label_sample records
+                n = len(self.keys) * batch_size
+                per_map = (self.max_map_hw[0] * self.max_map_hw[1] * int(max_map_itemsize) + 7) // 8 * 8
+                h_msrc = torch.empty(n * per_map, dtype=torch.uint8).pin_memory()
+                h_mrec = torch.empty(n * C.sizeof(_lib.LabelSample), dtype=torch.uint8).pin_memory()
+                self.slots[-1].update(h_msrc=h_msrc, h_mrec=h_mrec, d_msrc=torch.empty_like(h_msrc, device=self.device),
+                                      d_mrec=torch.empty_like(h_mrec, device=self.device), msrc_bytes=0,
+                                      status=torch.zeros(1, dtype=torch.int32, device=self.device))
         assert npx > 0
 
     def fill(self, samples, params):
         """host half of staging one batch: copy the samples and augmentation draws into the next slot's pinned buffers (60 MB of numpy
-        copies for a KITTI batch with float64 maps -- DeviceLoader runs this in a worker thread).  Waits only for the slot's previous
-        H2D copies.  Returns the slot index for launch()."""
+        copies for a KITTI batch with float64 maps at the target size; with raw_maps the maps as stored at their native size, 78 MB for
+        float32 maps of 375 x 1242, plus their records and, once per distinct size, the INTER_AREA tables -- DeviceLoader runs this in a
+        worker thread).  Waits only for the slot's previous H2D copies.  Returns the slot index for launch()."""
         if len(samples) != self.B or len(params) != self.B:
             raise ValueError("expected %d samples" % self.B)
         i, s = self._take_slot()
@@ -203,8 +236,29 @@ class DeviceBatchAssembler(SlotAssembler):
         for b, (img, maps) in enumerate(samples):
             if not self.raw_images:
                 img_np[b] = img
-            for k, key in enumerate(self.keys):
-                maps_np[k, b] = maps[key]
+            if not self.raw_maps:
+                for k, key in enumerate(self.keys):
+                    maps_np[k, b] = maps[key]
+        if self.raw_maps:                   # map-major, like d_maps; a flipped sample's maps are read and stored mirrored
+            raw, methods, flips, mults = [], [], [], []
+            for key in self.keys:
+                off = key == "moving_objects" and not self.use_moving
+                for (_, maps), p in zip(samples, params):
+                    # None only where the reference has no file either: a missing depth mask, moving objects with the masking off
+                    m = None if off else maps[key]
+                    if m is None and key not in ("depth_mask", "moving_objects"):
+                        raise ValueError("the map %r of a sample is None: only depth_mask (and moving_objects) may be missing" % key)
+                    raw.append(m)
+                    methods.append("zero" if m is None else MAP_METHODS[key])
+                    flips.append(bool(p.flip))
+                    mults.append(self.W / m.shape[1] if key == "disparity" and m is not None else 1.0)     # footprint_dataset.py:92
+            need = ops.label_pack_bytes(raw)
+            if need > s["h_msrc"].numel():  # wider stored dtypes than max_map_itemsize foresaw: the slot's pair grows, as the segmentation assembler's do
+                ops.release(s["d_msrc"], "assembler:label maps")
+                s["h_msrc"] = torch.empty(need + need // 4, dtype=torch.uint8).pin_memory()
+                s["d_msrc"] = torch.empty_like(s["h_msrc"], device=self.device)
+            s["msrc_bytes"] = ops.label_resize_pack(raw, self.H, self.W, methods, flips, mults, tables=self.map_tables, packed=s["h_msrc"].numpy(),
+                                                    records=s["h_mrec"].numpy(), max_map_hw=self.max_map_hw)[2]
         arr = (AugParams * self.B)(*params)
         s["h_par"].numpy()[:] = np.frombuffer(bytes(arr), dtype=np.uint8)
         return i
@@ -218,7 +272,14 @@ class DeviceBatchAssembler(SlotAssembler):
                                  out=s["d_img"])
         else:
             s["d_img"].copy_(s["h_img"], non_blocking=True)
-        s["d_maps"].copy_(s["h_maps"], non_blocking=True)
+        if self.raw_maps:                   # cv2.resize of every map, straight into d_maps
+            n = s["msrc_bytes"]
+            s["d_msrc"][:n].copy_(s["h_msrc"][:n], non_blocking=True)
+            s["d_mrec"].copy_(s["h_mrec"], non_blocking=True)
+            ops.label_resize_packed(s["d_msrc"], n, s["d_mrec"], len(self.keys) * self.B, self.H, self.W, self.map_tables, out=s["d_maps"],
+                                    status=s["status"], check=self.check)
+        else:
+            s["d_maps"].copy_(s["h_maps"], non_blocking=True)
         s["d_par"].copy_(s["h_par"], non_blocking=True)
         if self.filter_mask:                # filter_depth_mask in place, in front of the label algebra
             ops.filter_depth_mask(s["d_maps"][2], out=s["d_maps"][2])

@@ -1,10 +1,11 @@
 """Entry point -- counterpart of footprints/main.py:8-26: `python -m footprints_amd.main --mode train ...`.
 
-The KITTI / Matterport dataset readers are outside this build's scope: training runs over any
-iterable of batches with the reference schema; with `--synthetic_steps N` it runs over the synthetic loader the benchmark
-uses.  `--mode inference` is the reference's test-set program (footprints/evaluation/inference.py:31-96): the test split of
-`--inference_data_type` through the network, one .npy (and with --save_test_visualisations one .jpg) per frame -- the input of
-`evaluation/evaluate_model.py --predictions`."""
+`--mode train` trains from the folders the config file names, like the reference: `--config_path`'s [training_dataset]['dataset' |
+'training_data'] and splits/<dataset>/{train,val}.txt relative to the working directory (datasets/training.py: the file readers on a pool
+of threads; the frame's resize, the label maps' cv2 resizes, the depth-mask filter, flip, jitter and label algebra on the device).  With
+`--synthetic_steps N` it runs over the synthetic loader the benchmark uses instead, and no file is read.  `--mode inference` is the
+reference's test-set program (footprints/evaluation/inference.py:31-96): the test split of `--inference_data_type` through the network, one
+.npy (and with --save_test_visualisations one .jpg) per frame -- the input of `evaluation/evaluate_model.py --predictions`."""
 from .options import Options
 from .parallel import DistContext
 from .training.train import SyntheticLoader, TrainManager
@@ -45,8 +46,10 @@ def main(argv=None, model_manager=None):
         if ctx.is_main:
             print("In training mode!")
         if opt.synthetic_steps <= 0:
-            raise SystemExit("no dataset readers in this build: pass --synthetic_steps N, or construct TrainManager(options, "
-                             "train_loader=..., val_loader=...) with your own loaders")
+            # the reference's create_dataloaders over the device path; under a data-parallel launch TrainManager shards the train source
+            from .datasets.training import create_dataloaders
+            train, val = create_dataloaders(opt)
+            return TrainManager(opt, train_loader=train, val_loader=val, dist_context=ctx).train()
         if opt.device_augment and opt.training_dataset == "kitti":
             # row N3: host samples as the file readers deliver them -> pinned double-buffered H2D -> flip / jitter / label kernels
             from .datasets import DeviceBatchAssembler, DeviceLoader, SyntheticSampleSource

@@ -1285,6 +1285,201 @@ def filter_depth_mask(mask, out=None):
     return out
 
 
+# ---- reader work on the device: the cv2 resizes of the label maps (csrc/label_resize.hip) ------------------------------------------------
+LABEL_METHODS = {"zero": _lib.LABEL_ZERO, "nearest": _lib.LABEL_NEAREST, "area": _lib.LABEL_AREA}
+_area_host_tables = {}
+
+
+def area_table(in_size, out_size):
+    """OpenCV's INTER_AREA table of one axis (computeResizeAreaTab), built by the library on the host (no GPU needed) and cached per
+    (in, out) -> (bounds int32 [out, 2] = first entry and entry count of every output index, index int32 [n], weight float32 [n])"""
+    import numpy as np
+    key = (int(in_size), int(out_size))
+    t = _area_host_tables.get(key)
+    if t is None:
+        lib = _lib.load()
+        if key[0] <= 0 or key[1] <= 0 or key[1] > key[0]:
+            raise ValueError("footprints_amd.ops.area_table: %d -> %d: sizes must be positive and INTER_AREA must not enlarge" % key)
+        cap = key[0] + 2 * key[1]
+        bounds, index, weight = np.empty((key[1], 2), np.int32), np.empty(cap, np.int32), np.empty(cap, np.float32)
+        n = lib.fp_area_table(key[0], key[1], bounds.ctypes.data, index.ctypes.data, weight.ctypes.data, cap)
+        if n < 0:
+            _lib.check(-1, "fp_area_table")
+        index, weight = index[:n].copy(), weight[:n].copy()
+        for a in (bounds, index, weight):
+            a.setflags(write=False)
+        t = _area_host_tables[key] = (bounds, index, weight)
+    return t
+
+
+class LabelTableSet(ResizeTableSet):
+    """ResizeTableSet over INTER_AREA's tables: fp_label_table records over one buffer of 8-byte elements (uploaded as int64, bit for bit),
+    a table's bounds one element per output index, its entries (int32 source index, float32 weight) one each"""
+
+    def index(self, in_size, out_size):
+        import numpy as np
+        key = (int(in_size), int(out_size))
+        with self.lock:
+            i = self.keys.get(key)
+            if i is None:
+                bounds, idx, weight = area_table(*key)
+                if int(bounds[:, 1].max()) > _lib.LABEL_MAX_ENTRIES:
+                    raise ValueError("footprints_amd.ops: INTER_AREA %d -> %d needs %d entries per output, the kernel stages %d"
+                                     % (key[0], key[1], int(bounds[:, 1].max()), _lib.LABEL_MAX_ENTRIES))
+                entries = np.empty((idx.size, 2), np.int32)
+                entries[:, 0] = idx
+                entries[:, 1] = weight.view(np.int32)
+                i = self.keys[key] = len(self.records)
+                self.records.append(_lib.LabelTable(key[0], key[1], int(bounds[:, 1].max()), idx.size, self.length, self.length + key[1]))
+                self.coeffs += [bounds.view(np.int64).reshape(-1), entries.view(np.int64).reshape(-1)]
+                self.length += key[1] + idx.size
+        return i
+
+
+_label_table_sets = {}
+
+
+def label_table_set(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    s = _label_table_sets.get(device)
+    if s is None:
+        s = _label_table_sets[device] = LabelTableSet(device)
+    return s
+
+
+def _label_source(m):
+    """a map as it is uploaded: the stored dtype when the kernel reads it (bool as uint8), float64 otherwise (.astype(float)) -> (array, FP_LABEL_*)"""
+    import numpy as np
+    m = np.asarray(m)
+    if m.ndim != 2 or m.size == 0:
+        raise ValueError("footprints_amd.ops.label_resize_pack: a map must be a non-empty [h, w] array, got shape %r" % (m.shape,))
+    if m.dtype == np.bool_:
+        m = m.view(np.uint8)
+    code = {np.dtype(np.uint8): _lib.LABEL_U8, np.dtype(np.float16): _lib.LABEL_F16, np.dtype(np.float32): _lib.LABEL_F32,
+            np.dtype(np.float64): _lib.LABEL_F64}.get(m.dtype)
+    if code is None:
+        m, code = m.astype(np.float64), _lib.LABEL_F64
+    return m, code
+
+
+def label_source_itemsize(m):
+    """bytes per element a map takes in the packed source buffer"""
+    import numpy as np
+    dt = np.asarray(m).dtype
+    return dt.itemsize if dt in (np.dtype(np.bool_), np.dtype(np.uint8), np.dtype(np.float16), np.dtype(np.float32)) else 8
+
+
+def label_pack_bytes(maps):
+    """bytes the maps (None = none) take in the packed source buffer, each padded to 8"""
+    import numpy as np
+    return sum((np.asarray(m).size * label_source_itemsize(m) + 7) // 8 * 8 for m in maps if m is not None)
+
+
+def _per_map(v, n, name):
+    if isinstance(v, (str, bool, int, float)) or getattr(v, "ndim", 1) == 0:
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError("footprints_amd.ops.label_resize_pack: %s must be one value or one per map" % name)
+    return v
+
+
+def label_area_fast(h, w, H, W):
+    """whether cv2's INTER_AREA takes its integer path: both scales, computed as 1 / (out / in) in double, within DBL_EPSILON of an integer"""
+    sx, sy = 1.0 / (float(W) / w), 1.0 / (float(H) / h)
+    eps = 2.220446049250313e-16
+    return abs(sx - round(sx)) < eps and abs(sy - round(sy)) < eps
+
+
+def label_resize_pack(maps, H, W, method, flip=False, multiplier=1.0, tables=None, packed=None, records=None, max_map_hw=None):
+    """host half of fp_label_resize: the maps ([h, w] arrays in the dtype the .npy holds; None = a map of zeros) one after the other at
+    8-byte-aligned offsets of `packed` (a uint8 numpy buffer, e.g. pinned; allocated when None) and their fp_label_sample records in
+    `records` (uint8 numpy view, allocated when None).  method ('zero' / 'nearest' / 'area'), flip and multiplier: one value, or one per
+    map.  tables: the LabelTableSet of the device (label_table_set).  INTER_AREA that would enlarge an axis is refused (cv2 switches to a
+    linear kernel there, which is not provided), and so is a map larger than max_map_hw when that is given.
+    -> (packed, records, bytes used, tables)"""
+    import numpy as np
+    n = len(maps)
+    methods, flips, mults = _per_map(method, n, "method"), _per_map(flip, n, "flip"), _per_map(multiplier, n, "multiplier")
+    if tables is None:
+        tables = label_table_set("cuda")
+    srcs, total = [], 0
+    rec = (_lib.LabelSample * n)()
+    for j, m in enumerate(maps):
+        meth = LABEL_METHODS.get(methods[j], methods[j]) if isinstance(methods[j], str) else int(methods[j])
+        if meth not in LABEL_METHODS.values():
+            raise ValueError("footprints_amd.ops.label_resize_pack: method must be one of %s" % sorted(LABEL_METHODS))
+        if m is None or meth == _lib.LABEL_ZERO:
+            rec[j] = _lib.LabelSample(0, 0, 0, 0, _lib.LABEL_ZERO, 0, -1, -1, 0, 1.0)
+            srcs.append(None)
+            continue
+        m, code = _label_source(m)
+        h, w = m.shape
+        if max_map_hw is not None and (h > max_map_hw[0] or w > max_map_hw[1]):
+            raise ValueError("footprints_amd.ops.label_resize_pack: map %d is %d x %d, larger than max_map_hw = %r" % (j, h, w, tuple(max_map_hw)))
+        tx = ty = -1
+        if meth == _lib.LABEL_AREA and (h, w) != (H, W):
+            if h < H or w < W:
+                raise ValueError("footprints_amd.ops.label_resize_pack: map %d: INTER_AREA from %d x %d up to %d x %d is not provided "
+                                 "(cv2 uses a linear kernel when it enlarges)" % (j, h, w, H, W))
+            if not label_area_fast(h, w, H, W):
+                tx, ty = tables.index(w, W), tables.index(h, H)
+        rec[j] = _lib.LabelSample(total, h, w, code, meth, int(bool(flips[j])), tx, ty, 0, float(mults[j]))
+        srcs.append(m)
+        total += (m.nbytes + 7) // 8 * 8
+    if packed is None:
+        packed = np.empty(max(total, 8), np.uint8)
+    if total > packed.size:
+        raise ValueError("footprints_amd.ops.label_resize_pack: the maps need %d source bytes, the buffer holds %d" % (total, packed.size))
+    for r, m in zip(rec, srcs):
+        if m is not None:
+            np.copyto(packed[r.offset:r.offset + m.nbytes].view(m.dtype).reshape(m.shape), m)
+    raw = np.frombuffer(bytes(rec), dtype=np.uint8)
+    if records is None:
+        records = raw.copy()
+    else:
+        records[:raw.size] = raw
+    return packed, records, total, tables
+
+
+def label_resize_packed(src, src_bytes, samples, n, H, W, tables, out=None, status=None, check=False):
+    """device half: `src` (uint8 device buffer holding the packed maps), `samples` (uint8 device buffer holding n fp_label_sample records)
+    -> float64 [n, H, W] (with n = K * B in map-major order: the [K, B, H, W] buffer fp_assemble_labels reads) on the current launch
+    stream.  The kernel turns down a record that points outside the buffer or names a table that does not fit its sizes and leaves that
+    map unwritten; check=True reads the status word afterwards (this WAITS for the stream) and raises ValueError then."""
+    lib = _lib.load()
+    d_tables, n_tables, d_entries = tables.device_buffers()
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.float64, device=src.device)
+    if out.numel() != n * H * W or out.dtype != torch.float64 or src.dtype != torch.uint8 or src.numel() < src_bytes:
+        raise RuntimeError("footprints_amd.ops.label_resize_packed: out must be float64 with n * H * W elements and src hold src_bytes bytes")
+    if samples.numel() * samples.element_size() < n * C.sizeof(_lib.LabelSample):
+        raise RuntimeError("footprints_amd.ops.label_resize_packed: fewer than n sample records")
+    if status is None:
+        status = workspace(4, src.device, "label_resize_status")[:4].view(torch.int32)
+    _lib.check(lib.fp_label_resize(_chk(src, "src"), int(src_bytes), _chk(samples, "samples"), n, _chk(d_tables) if n_tables else None, n_tables,
+                                   _chk(d_entries) if n_tables else None, d_entries.numel() if n_tables else 0,
+                                   max((r.max_count for r in tables.records[:n_tables]), default=0), _chk(out, "out"), H, W,
+                                   _chk(status, "status"), stream()), "fp_label_resize")
+    if check and int(status.item()) != 0:
+        raise ValueError("footprints_amd.ops.label_resize_packed: a sample or table record was turned down on the device; its map is unwritten")
+    return out
+
+
+def label_resize(maps, H, W, method, flip=False, multiplier=1.0, device="cuda"):
+    """cv2.resize(m.astype(float), (W, H), interpolation=INTER_AREA | INTER_NEAREST) * multiplier of a list of maps of any (mixed) sizes
+    and stored dtypes, bit for bit on float64, in one library call -> float64 device tensor [n, H, W].  With flip the result is
+    cv2.resize(np.fliplr(m)) mirrored back -- what the assembler's own flip expects."""
+    tables = label_table_set(device)
+    assert _lib.load().fp_label_sample_bytes() == C.sizeof(_lib.LabelSample) and _lib.load().fp_label_table_bytes() == C.sizeof(_lib.LabelTable)
+    packed, records, total, _ = label_resize_pack(maps, H, W, method, flip, multiplier, tables)
+    src = torch.from_numpy(packed).to(tables.device)
+    rec = torch.from_numpy(records).to(tables.device)
+    return label_resize_packed(src, total, rec, len(maps), H, W, tables, check=True)
+
+
 def to_tensor_u8(images_hwc):
     """ToTensor on the device: uint8 [B, H, W, 3] -> float32 [B, 3, H, W] in [0, 1] (fp_assemble_images without flip or jitter)"""
     B, H, W, Cn = images_hwc.shape

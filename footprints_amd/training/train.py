@@ -1,5 +1,6 @@
 """The training hot loop -- drop-in counterpart of footprints/training/train.py:145-227 (`run_epoch` /
-`process_batch`), without the dataset / tensorboard plumbing that is out of scope.
+`process_batch`), without the tensorboard plumbing that is out of scope; the loaders over the KITTI / Matterport
+folders are datasets/training.py::create_dataloaders, which main.py hands in.
 
 `TrainStep` is the MI355X fast path of `process_batch` + `zero_grad` + `backward` + `optimiser.step`
 (train.py:150-156): it drives the HIP engine's explicit forward / loss / backward / Adam schedule on static
@@ -281,7 +282,7 @@ def synthetic_batch(B, H, W, device, seed=SEED):
 
 class SyntheticLoader:
     """`steps` batches per epoch with the reference schema (datasets/footprint_dataset.py:55-65): a small pool of synthetic
-    batches resident on the device, cycled.  Stands in for the KITTI / Matterport DataLoaders, which are out of scope."""
+    batches resident on the device, cycled.  Stands in for the KITTI / Matterport loaders (datasets/training.py) where no files are at hand."""
 
     def __init__(self, batch_size, height, width, steps, seed=SEED, pool=2, device="cuda"):
         self.steps, self.first, self.stride = steps, 0, 1

@@ -564,6 +564,64 @@ int64_t fp_filter_depth_mask_workspace(int32_t B, int32_t H, int32_t W);
 int fp_filter_depth_mask(const void* mask, int32_t is_double, void* out, int32_t B, int32_t H, int32_t W, void* workspace,
                          int64_t workspace_bytes, fp_stream_t stream);
 
+/* ---- device-side reader work: the cv2 resizes of the label maps (footprint_dataset.py:82-94; csrc/label_resize.hip) ---- */
+#define FP_LABEL_U8 0 /* stored dtype of a map: uint8 or bool */
+#define FP_LABEL_F16 1
+#define FP_LABEL_F32 2
+#define FP_LABEL_F64 3
+#define FP_LABEL_ZERO 0    /* the map is 0.0 everywhere (a missing depth mask); nothing is read */
+#define FP_LABEL_NEAREST 1 /* cv2.INTER_NEAREST */
+#define FP_LABEL_AREA 2    /* cv2.INTER_AREA, shrinking or equal on both axes; its upscaling branch (a linear kernel) is not provided */
+#define FP_LABEL_MAX_ENTRIES 12 /* most entries of one output index in an area table that a launch stages: non-integer shrink factors up to 10 */
+/* one map of the batch; fp_label_sample_bytes() == sizeof(fp_label_sample) */
+typedef struct fp_label_sample {
+  int64_t offset;  /* of its first byte in the packed source buffer, a multiple of 8; the map is dense [h][w] of `dtype` */
+  int32_t h, w;
+  int32_t dtype;   /* FP_LABEL_U8 .. FP_LABEL_F64 */
+  int32_t method;  /* FP_LABEL_ZERO / NEAREST / AREA */
+  int32_t flip;    /* read the source mirrored and store mirrored */
+  int32_t table_x; /* index of its (w -> W) area table; read only on INTER_AREA's general path */
+  int32_t table_y; /* index of its (h -> H) area table */
+  int32_t pad;
+  double multiplier; /* the resized value is multiplied by it (the KITTI disparity: W / w; 1.0 elsewhere) */
+} fp_label_sample;
+/* one axis table of INTER_AREA inside the entry buffer (8-byte elements; offsets count elements): bounds = one element per output index
+ * (two int32: first entry relative to the table's entries, entry count), entries = (int32 source index, float weight);
+ * fp_label_table_bytes() == sizeof(fp_label_table) */
+typedef struct fp_label_table {
+  int32_t in_size, out_size;
+  int32_t max_count; /* most entries of one output index, <= FP_LABEL_MAX_ENTRIES */
+  int32_t n_entries;
+  int32_t bounds_off;
+  int32_t entries_off;
+} fp_label_table;
+int32_t fp_label_sample_bytes(void);
+int32_t fp_label_table_bytes(void);
+int32_t fp_label_max_entries(void);
+/* HOST function (no GPU needed): OpenCV's computeResizeAreaTab of one axis, out_size <= in_size.  With scale = 1 / ((double)out / in), for
+ * every output index d: f1 = d * scale, f2 = f1 + scale, cw = min(scale, in - f1), s1 = ceil(f1), s2 = min(floor(f2), in - 1), s1 = min(s1, s2);
+ * a leading partial cell (s1 - 1, (s1 - f1) / cw) when s1 - f1 > 1e-3, whole cells (s, 1 / cw) for s1 <= s < s2, a trailing partial cell
+ * (s2, min(min(f2 - s2, 1), cw) / cw) when f2 - s2 > 1e-3; every weight rounded to float.  bounds int32 [out][2] = first entry and count,
+ * index int32 / weight float [capacity].  Returns the number of entries (at most in + 2 * out), -1 on bad arguments or when they do not
+ * fit; with bounds, index and weight NULL it only counts. */
+int32_t fp_area_table(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* index, float* weight, int32_t capacity);
+/* n_records maps of mixed sizes and stored dtypes, packed in `src` (device, 8-byte aligned, src_bytes long) and described by `samples`
+ * (device, n_records fp_label_sample), -> out double [n_records][H][W], bit for bit what
+ * cv2.resize(m.astype(float), (W, H), interpolation) * multiplier gives on float64 data, restated from OpenCV's algorithm: equal sizes are
+ * copied; NEAREST reads min(floor(d * scale), in - 1) per axis with scale = 1 / ((double)out / in); AREA with both scales integer (within
+ * DBL_EPSILON) sums the block in row-major order in double and multiplies by (double)(1.f / (float)area); AREA otherwise walks the two
+ * axis tables: per y entry buf = 0.0, buf = buf + S[sy][sx] * alpha over the x entries, sum = beta * buf for the first y entry and
+ * sum = sum + beta * buf after it, the float weights widened to double, no fused multiply-add.  A flipped record gives
+ * cv2.resize(np.fliplr(m)) mirrored, so that the flip of fp_assemble_labels undoes the mirroring.  tables: n_tables fp_label_table records
+ * over `entries` (device, entries_len 8-byte elements).  A record that points outside the packed buffer, asks AREA to enlarge, or whose
+ * table does not fit its sizes leaves that map unwritten and sets *status (one int32 on the device) to 1; every call clears it first; read
+ * it after the stream has finished.  max_entries: the largest max_count of the tables (0 without tables, at most FP_LABEL_MAX_ENTRIES); it
+ * sizes the launch's LDS (2 * max_entries * 2 KiB per workgroup), and a table with a longer row is turned down like any other that does not
+ * fit.  One kernel, one thread per output element, no workspace. */
+int fp_label_resize(const void* src, int64_t src_bytes, const void* samples, int32_t n_records, const void* tables, int32_t n_tables,
+                    const void* entries, int64_t entries_len, int32_t max_entries, double* out, int32_t H, int32_t W, int32_t* status,
+                    fp_stream_t stream);
+
 /* ---- device-side reader work of the segmentation trainer (footprints/preprocessing/segmentation/datasets;
  * csrc/resample_u8.hip, csrc/seg_reader.hip) ---- */
 /* HOST function (no GPU needed): rows first .. first + count - 1 of fp_resize_coeffs' tables (bounds int32 [count][2], kk int32
