@@ -80,6 +80,21 @@ class LabelTable(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("in_size", "out_size", "max_count", "n_entries", "bounds_off", "entries_off")]
 
 
+GT_F16, GT_F32, GT_F64, GT_U16 = range(4)                   # FP_GT_*: stored dtype of a source map of the label generators
+GT_LINEAR, GT_NEAREST, GT_AREA2 = range(3)                  # FP_GT_*: resize method
+
+
+class GtFrame(C.Structure):
+    """fp_gt_frame (include/footprints_hip.h)"""
+    _fields_ = [("offset", C.c_int64), ("dst", C.c_int64)] + [(n, C.c_int32) for n in (
+        "h", "w", "dtype", "method", "table_x", "table_y", "threshold", "pad")] + [(n, C.c_double) for n in ("pre", "post_num", "post_den", "thr")]
+
+
+class GtTable(C.Structure):
+    """fp_gt_table (include/footprints_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("in_size", "out_size", "clamp", "offset")]
+
+
 JPEG_TABLE_WORDS = 672            # fp_jpeg_table_words()
 
 
@@ -159,6 +174,12 @@ SIGNATURES = {
     "fp_label_max_entries": (_I32, []),
     "fp_area_table": (_I32, [_I32, _I32, _P, _P, _P, _I32]),
     "fp_label_resize": (C.c_int, [_P, _I64, _P, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _I32, _P, _P]),
+    "fp_gt_frame_bytes": (_I32, []),
+    "fp_gt_table_bytes": (_I32, []),
+    "fp_linear_table": (C.c_int, [_I32, _I32, _I32, _P, _P]),
+    "fp_gt_frame_check": (C.c_int, [_P, _I32, _I64, _P, _I32, _I64, _I64, _I32, _I32]),
+    "fp_gt_frame_resize": (C.c_int, [_P, _I64, _P, _P, _I32, _P, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _P]),
+    "fp_gt_gather_frames": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),
     "fp_resize_coeffs_f64": (C.c_int, [_I32, _I32, _I32, _P, _P, _I32]),
     "fp_vis_overlay_workspace": (_I64, [_I32, _I32, _I32, _I32, _I32]),
     "fp_vis_overlay_status_offset": (_I64, [_I32, _I32, _I32, _I32, _I32]),

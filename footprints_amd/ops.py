@@ -1480,6 +1480,211 @@ def label_resize(maps, H, W, method, flip=False, multiplier=1.0, device="cuda"):
     return label_resize_packed(src, total, rec, len(maps), H, W, tables, check=True)
 
 
+# ---- loader work of the training-label generators on the device: cv2's resizes into a frame cache, batches out of it (csrc/gt_frames.hip) --
+GT_METHODS = {"linear": _lib.GT_LINEAR, "nearest": _lib.GT_NEAREST, "area2": _lib.GT_AREA2}
+_linear_host_tables = {}
+
+
+def linear_table(in_size, out_size, clamp):
+    """cv2's INTER_LINEAR offsets and float coefficients of one axis (fp_linear_table), built by the library on the host (no GPU needed)
+    and cached per (in, out, clamp) -> (offsets int32 [out], coefficients float32 [out, 2]); clamp = the horizontal form"""
+    import numpy as np
+    key = (int(in_size), int(out_size), int(bool(clamp)))
+    t = _linear_host_tables.get(key)
+    if t is None:
+        if key[0] <= 0 or key[1] <= 0:
+            raise ValueError("footprints_amd.ops.linear_table: %d -> %d: sizes must be positive" % key[:2])
+        offsets, coeffs = np.empty(key[1], np.int32), np.empty((key[1], 2), np.float32)
+        _lib.check(_lib.load().fp_linear_table(key[0], key[1], key[2], offsets.ctypes.data, coeffs.ctypes.data), "fp_linear_table")
+        for a in (offsets, coeffs):
+            a.setflags(write=False)
+        t = _linear_host_tables[key] = (offsets, coeffs)
+    return t
+
+
+class LinearTableSet(ResizeTableSet):
+    """ResizeTableSet over INTER_LINEAR's tables: fp_gt_table records over one int32 buffer, a table's offsets first, then its coefficient bits"""
+
+    def index(self, in_size, out_size, clamp):
+        key = (int(in_size), int(out_size), int(bool(clamp)))
+        with self.lock:
+            i = self.keys.get(key)
+            if i is None:
+                import numpy as np
+                offsets, coeffs = linear_table(*key)
+                i = self.keys[key] = len(self.records)
+                self.records.append(_lib.GtTable(key[0], key[1], key[2], self.length))
+                self.coeffs += [offsets, coeffs.view(np.int32).reshape(-1)]
+                self.length += 3 * key[1]
+        return i
+
+    def host_records(self):
+        """(ctypes array of the fp_gt_table records or None, their count, length of the word buffer): what the host half validates against"""
+        with self.lock:
+            n = len(self.records)
+            return ((_lib.GtTable * n)(*self.records) if n else None), n, self.length
+
+
+_linear_table_sets = {}
+
+
+def linear_table_set(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    s = _linear_table_sets.get(device)
+    if s is None:
+        assert _lib.load().fp_gt_frame_bytes() == C.sizeof(_lib.GtFrame) and _lib.load().fp_gt_table_bytes() == C.sizeof(_lib.GtTable)
+        s = _linear_table_sets[device] = LinearTableSet(device)
+    return s
+
+
+def _gt_source(m, pre, j):
+    """a map as it is uploaded and its pre-scale as the kernel takes it: rounded to the stored dtype, like numpy's in-place `m *= pre`"""
+    import numpy as np
+    m = np.asarray(m)
+    if m.ndim != 2 or m.size == 0:
+        raise ValueError("footprints_amd.ops.gt_frame_pack: map %d must be a non-empty [h, w] array, got shape %r" % (j, m.shape))
+    code = {np.dtype(np.float16): _lib.GT_F16, np.dtype(np.float32): _lib.GT_F32, np.dtype(np.float64): _lib.GT_F64,
+            np.dtype(np.uint16): _lib.GT_U16}.get(m.dtype)
+    if code is None:
+        if m.dtype.kind not in "bui" or m.dtype.itemsize > 4:
+            raise ValueError("footprints_amd.ops.gt_frame_pack: map %d: dtype %s is not provided" % (j, m.dtype))
+        m, code = m.astype(np.float64), _lib.GT_F64                # .astype(float) is exact for these; numpy refuses to pre-scale them in place
+        if float(pre) != 1.0:
+            raise ValueError("footprints_amd.ops.gt_frame_pack: map %d: an integer map takes no pre-scale" % j)
+    if code == _lib.GT_U16:
+        if float(pre) != 1.0:
+            raise ValueError("footprints_amd.ops.gt_frame_pack: map %d: an integer map takes no pre-scale" % j)
+        return m, code, 1.0
+    return m, code, float(m.dtype.type(pre))
+
+
+def gt_frame_pack_bytes(maps):
+    """bytes that `maps` and their records take in the packed buffer of gt_frame_pack"""
+    import numpy as np
+    total = 0
+    for m in maps:
+        m = np.asarray(m)
+        item = m.dtype.itemsize if m.dtype in (np.dtype(np.float16), np.dtype(np.float32), np.dtype(np.uint16)) else 8
+        total += (m.size * item + 7) // 8 * 8
+    return total + len(maps) * C.sizeof(_lib.GtFrame)
+
+
+class GtFramePack:
+    """what gt_frame_pack hands to gt_frame_resize: `packed` (uint8 numpy buffer, possibly pinned) holds the maps in [0, src_bytes) and the
+    n fp_gt_frame records in [records_offset, total); `records` is the validated host copy of the latter"""
+
+    def __init__(self, packed, src_bytes, records_offset, total, records, n, H, W, cache_elems, tables):
+        self.packed, self.src_bytes, self.records_offset, self.total = packed, src_bytes, records_offset, total
+        self.records, self.n, self.H, self.W, self.cache_elems, self.tables = records, n, H, W, cache_elems, tables
+
+
+def gt_frame_pack(maps, H, W, dst, cache_elems, method="linear", pre=1.0, post=1.0, threshold=None, tables=None, packed=None):
+    """host half of fp_gt_frame_resize (no GPU needed): the maps ([h, w] arrays in the dtype the .npy holds: float16 / float32 / float64 /
+    uint16) one after the other at 8-byte-aligned offsets of `packed` (a uint8 numpy buffer, e.g. pinned; allocated when None), their
+    fp_gt_frame records behind them, and the records validated against the packed bytes, a cache of `cache_elems` float32 elements and the
+    tables (ValueError names the first bad one).  dst: each map's element offset into the cache (slot * H * W).  method ('linear' /
+    'nearest' / 'area2'), pre, post (a factor, or (numerator, denominator): the value is (v * numerator) / denominator) and threshold (None
+    = none): one value, or one per map.  'linear' at exactly twice the target on both axes is dispatched to 'area2', as cv::resize does.
+    tables: the LinearTableSet of the device.  -> GtFramePack"""
+    import numpy as np
+    n = len(maps)
+    if n == 0:
+        raise ValueError("footprints_amd.ops.gt_frame_pack: no maps")
+    lib = _lib.load()
+    per = lambda v, name: [v] * n if (v is None or isinstance(v, (str, int, float, tuple)) or getattr(v, "ndim", 1) == 0) else _per_map(v, n, name)
+    methods, pres, posts, thrs, dsts = per(method, "method"), per(pre, "pre"), per(post, "post"), per(threshold, "threshold"), _per_map(dst, n, "dst")
+    if tables is None:
+        tables = linear_table_set("cuda")
+    rec = (_lib.GtFrame * n)()
+    srcs, total = [], 0
+    for j, m in enumerate(maps):
+        meth = GT_METHODS.get(methods[j], methods[j]) if isinstance(methods[j], str) else int(methods[j])
+        if meth not in GT_METHODS.values():
+            raise ValueError("footprints_amd.ops.gt_frame_pack: method must be one of %s" % sorted(GT_METHODS))
+        m, code, p = _gt_source(m, pres[j], j)
+        h, w = m.shape
+        if meth == _lib.GT_LINEAR and label_area_fast(h, w, H, W) and round(1.0 / (float(W) / w)) == 2 and round(1.0 / (float(H) / h)) == 2:
+            meth = _lib.GT_AREA2                                     # cv::resize: INTER_LINEAR with both integer scales 2 becomes INTER_AREA
+        tx = ty = -1
+        if meth == _lib.GT_LINEAR:
+            tx, ty = tables.index(w, W, True), tables.index(h, H, False)
+        num, den = posts[j] if isinstance(posts[j], tuple) else (posts[j], 1.0)
+        thr = thrs[j]
+        rec[j] = _lib.GtFrame(total, int(dsts[j]), h, w, code, meth, tx, ty, int(thr is not None), 0, p, float(num), float(den),
+                              0.0 if thr is None else float(thr))
+        srcs.append(m)
+        total += (m.nbytes + 7) // 8 * 8
+    src_bytes, total = total, total + n * C.sizeof(_lib.GtFrame)
+    t_rec, n_tables, words_len = tables.host_records()
+    if lib.fp_gt_frame_check(C.addressof(rec), n, src_bytes, C.addressof(t_rec) if n_tables else None, n_tables, words_len, int(cache_elems), H, W):
+        msg = lib.fp_last_error_string()
+        raise ValueError("footprints_amd.ops.gt_frame_pack: %s" % (msg.decode() if msg else "?"))
+    if packed is None:
+        packed = np.empty(total, np.uint8)
+    if total > packed.size:
+        raise ValueError("footprints_amd.ops.gt_frame_pack: the maps and records need %d bytes, the buffer holds %d" % (total, packed.size))
+    for r, m in zip(rec, srcs):
+        np.copyto(packed[r.offset:r.offset + m.nbytes].view(m.dtype).reshape(m.shape), m)
+    packed[src_bytes:total] = np.frombuffer(bytes(rec), dtype=np.uint8)
+    return GtFramePack(packed, src_bytes, src_bytes, total, rec, n, H, W, int(cache_elems), tables)
+
+
+def gt_frame_resize(pack, d_packed, cache):
+    """device half: d_packed (uint8 device buffer holding pack.packed[:pack.total]) -> every map resized into its slot of `cache` (float32
+    device tensor of pack.cache_elems elements) on the current launch stream, one launch.  The library validates pack.records once more
+    before it launches; Python sees ValueError."""
+    lib = _lib.load()
+    if d_packed.dtype != torch.uint8 or d_packed.numel() < pack.total or cache.dtype != torch.float32 or cache.numel() != pack.cache_elems:
+        raise RuntimeError("footprints_amd.ops.gt_frame_resize: d_packed must be uint8 and hold pack.total bytes, cache float32 of pack.cache_elems elements")
+    d_tables, n_tables, d_words = pack.tables.device_buffers()
+    t_rec, n_host, words_len = pack.tables.host_records()
+    n_tables = min(n_tables, n_host)
+    base = _chk(d_packed, "d_packed")
+    rc = lib.fp_gt_frame_resize(base, pack.src_bytes, C.addressof(pack.records), base + pack.records_offset, pack.n,
+                                C.addressof(t_rec) if n_tables else None, _chk(d_tables) if n_tables else None, n_tables,
+                                _chk(d_words) if n_tables else None, d_words.numel() if n_tables else 0, _f32(cache, "cache"), cache.numel(),
+                                pack.H, pack.W, stream())
+    if rc == -1:                                                     # FP_EINVAL: a record was turned down, nothing was launched
+        msg = lib.fp_last_error_string()
+        raise ValueError("footprints_amd.ops.gt_frame_resize: %s" % (msg.decode() if msg else "?"))
+    _lib.check(rc, "fp_gt_frame_resize")
+    return cache
+
+
+def gt_frames(maps, H, W, method="linear", pre=1.0, post=1.0, threshold=None, device="cuda"):
+    """the resizes of the label generators' loader for a list of maps of any (mixed) sizes and stored dtypes, in one library call -> float32
+    device tensor [n, H, W] (a cache of its own, map j in slot j)"""
+    tables = linear_table_set(device)
+    cache = torch.empty((len(maps), H, W), dtype=torch.float32, device=tables.device)
+    pack = gt_frame_pack(maps, H, W, [j * H * W for j in range(len(maps))], cache.numel(), method, pre, post, threshold, tables)
+    return gt_frame_resize(pack, torch.from_numpy(pack.packed[:pack.total]).to(tables.device), cache)
+
+
+def gt_gather_frames(cache, depth_slots, seg_slots, fb=None):
+    """the batch of one target frame out of a frame cache (float32 [n_slots, H, W]): depths[b] = fb / cache[depth_slots[b]] (IEEE float32
+    division; fb = the float32 fx * baseline) or, with fb None, the slot itself; ground_segs[b] = cache[seg_slots[b]].  Slots may repeat and
+    come in any order; one outside the cache raises ValueError before anything is launched.  -> (depths, ground_segs) float32 [B, H, W]"""
+    import numpy as np
+    if cache.dim() != 3:
+        raise RuntimeError("footprints_amd.ops.gt_gather_frames: the cache must be [n_slots, H, W]")
+    n_slots, H, W = cache.shape
+    slots = np.ascontiguousarray(np.stack([np.asarray(depth_slots, np.int64).reshape(-1), np.asarray(seg_slots, np.int64).reshape(-1)]))
+    B = slots.shape[1]
+    if B == 0 or slots.min() < 0 or slots.max() >= n_slots:
+        raise ValueError("footprints_amd.ops.gt_gather_frames: %d frames with slots %s .. %s, the cache holds %d slots"
+                         % (B, slots.min() if B else None, slots.max() if B else None, n_slots))
+    slots = slots.astype(np.int32)
+    c = _f32(cache, "cache")
+    d_slots = torch.from_numpy(slots).to(cache.device)
+    depths = torch.empty((B, H, W), dtype=torch.float32, device=cache.device)
+    ground_segs = torch.empty((B, H, W), dtype=torch.float32, device=cache.device)
+    _lib.check(_lib.load().fp_gt_gather_frames(c, n_slots, slots.ctypes.data, _chk(d_slots), B, H, W, int(fb is not None),
+                                               0.0 if fb is None else float(fb), _chk(depths), _chk(ground_segs), stream()), "fp_gt_gather_frames")
+    return depths, ground_segs
+
+
 def to_tensor_u8(images_hwc):
     """ToTensor on the device: uint8 [B, H, W, 3] -> float32 [B, 3, H, W] in [0, 1] (fp_assemble_images without flip or jitter)"""
     B, H, W, Cn = images_hwc.shape

@@ -1,25 +1,35 @@
 """Generators of the training labels (reference preprocessing/ground_truth_generation/ground_truth_generator.py): hidden ground depth
 (warp every source frame into the target camera, splat, per-pixel median), moving-object masks and depth masks.
 
-The compute between "frames loaded" and "label saved" runs in HIP kernels (csrc/gt_gen.hip).  The file readers are out of scope, so
-each generator takes a `loader` instead of constructing one.  A loader has what the reference's KITTILoader / MatterportLoader have:
+The compute between "frames loaded" and "label saved" runs in HIP kernels (csrc/gt_gen.hip), and so does what lies between the files and
+"frames loaded" (data_loader.py, csrc/gt_frames.hip).  A generator's constructor takes a `loader`; `from_options` builds the one that reads
+the folders the config file names, and `main` is the reference's command line:
 
-* ``load_data(...)`` -> dict with ``depths`` and ``ground_segs`` [B,H,W] float32 tensors, ``poses`` / ``intrinsics`` /
-  ``inv_intrinsics`` [B,4,4] float32 tensors (camera-to-world poses), on the host, and for KITTI ``sides`` (list of 'image_02' / 'image_03');
-* ``load_frame_data(...)`` -> for KITTI a dict with ``pose`` (4x4 array), ``disparity`` and ``ground_seg`` [H,W] float32 arrays and, with
-  ``load_flow=True``, ``flow`` [2,H,W]; ``None`` for a frame that does not exist; for Matterport the tuple
+    python -m footprints_amd.preprocessing.ground_truth_generation.ground_truth_generator --data_type kitti --type hidden_depths \
+        --textfile splits/kitti/train.txt --config_path paths.yaml
+
+A loader has what the reference's KITTILoader / MatterportLoader have:
+
+* ``load_data(...)`` -> dict with ``depths`` and ``ground_segs`` [B,H,W] float32 tensors (on the device from data_loader's loaders, on the
+  host from any other), ``poses`` / ``intrinsics`` / ``inv_intrinsics`` [B,4,4] float32 tensors (camera-to-world poses), on the host, and
+  for KITTI ``sides`` (list of 'image_02' / 'image_03');
+* ``load_frame_data(...)`` -> for KITTI a dict with ``pose`` (4x4 array), ``disparity`` and ``ground_seg`` [H,W] float32 (device tensors or
+  arrays) and, with ``load_flow=True``, ``flow`` [2,H,W]; ``None`` for a frame that does not exist; for Matterport the tuple
   ``(ground_seg, depth, pose, K)``;
-* KITTI: ``K`` / ``invK`` (4x4 arrays), ``stereo_baseline``, ``buffer`` and ``purge_buffer()``; Matterport: ``pose_tracker``.
+* KITTI: ``K`` / ``invK`` (4x4 arrays), ``stereo_baseline``, ``buffer`` and ``purge_buffer()``; Matterport: ``pose_tracker`` and, optionally,
+  ``gather_frames(indices)`` (the close cameras' frames as one gather instead of a product over the whole scan).
 
 `process_data` takes arrays (uploaded as the reference uploads them) or CUDA tensors; CPU tensors are refused: there is no CPU path.
 """
 import argparse
 import os
+import time
 
 import numpy as np
 import torch
 
 from ... import ops
+from .data_loader import KITTILoader, MatterportLoader
 from .geometry import BatchProjector, draw_samples, require_cuda
 
 
@@ -48,6 +58,17 @@ class GroundTruthGenerator:
     """Generates the ground truth depths of both visible and hidden ground"""
 
     height, width = None, None
+    data_key, loader_class = None, None       # the config file's section and the loader `from_options` builds
+
+    @classmethod
+    def from_options(cls, opts):
+        """the generator over the folders that `opts.config_path` names under [data_key]: 'dataset' and 'training_data'"""
+        import yaml
+        with open(opts.config_path) as fh:
+            section = yaml.safe_load(fh)[cls.data_key]
+        loader = cls.loader_class(section["dataset"], section["training_data"], cls.height, cls.width,
+                                  footprint_threshold=opts.footprint_threshold)
+        return cls(opts, loader, training_datapath=section["training_data"])
 
     def __init__(self, opts, loader, training_datapath=None):
         self.opts = opts
@@ -99,10 +120,20 @@ class GroundTruthGenerator:
         return ops.gt_aggregate(keys, self.height, self.width, robust_aggregation).cpu().numpy()
 
     def run(self):
+        time_before_batch = time.time()
+        print("running ground truth generation on {} files...".format(len(self.filenames)))
         for i, filename in enumerate(self.filenames):
+            if i % 25 == 0:
+                print("computing image {} of {}".format(i, len(self.filenames)))
+                if i != 0:
+                    print("average time per image: {}".format((time.time() - time_before_batch) / 25))
+                    time_before_batch = time.time()
+                    buffer = getattr(self.loader, "buffer", None)
+                    if buffer is not None:
+                        print("buffer size {}".format(len(buffer)))
             data = self.load_data(i, filename)
             result = self.process_data(data, robust_aggregation=self.robust_aggregation)
-            self.save_result(result, filename)
+            self.save_result(result, filename, save_viz=getattr(self.opts, "save_visualisations", False))
 
 
 def _side(side):
@@ -112,6 +143,7 @@ def _side(side):
 class KITTIGroundTruthGenerator(GroundTruthGenerator):
 
     height, width = 192, 640
+    data_key, loader_class = "kitti", KITTILoader
 
     def __init__(self, opts, loader, training_datapath=None):
         super().__init__(opts, loader, training_datapath)
@@ -218,6 +250,7 @@ class KITTIDepthMaskingGenerator(_DepthMasking, KITTIGroundTruthGenerator):
 class MatterportGroundTruthGenerator(GroundTruthGenerator):
 
     height, width = 480, 640
+    data_key, loader_class = "matterport", MatterportLoader
 
     def __init__(self, opts, loader, training_datapath=None):
         super().__init__(opts, loader, training_datapath)
@@ -226,7 +259,6 @@ class MatterportGroundTruthGenerator(GroundTruthGenerator):
     def load_data(self, idx, filename):
         scan, pos, height, direction = filename.split()
         data = self.loader.load_data(scan, pos, height, direction)
-        depths = data["depths"] * data["ground_segs"]
         # only the cameras close to the target one
         base_pose = self.loader.pose_tracker[(pos, height, direction)]
         inv_pose = torch.from_numpy(np.linalg.pinv(base_pose)).float().unsqueeze(0)
@@ -234,9 +266,15 @@ class MatterportGroundTruthGenerator(GroundTruthGenerator):
         poses = data["poses"]
         close = (torch.abs(base_pose[:, 0, 3] - poses[:, 0, 3]) < 10) * (torch.abs(base_pose[:, 1, 3] - poses[:, 1, 3]) < 10) * \
                 (torch.abs(base_pose[:, 2, 3] - poses[:, 2, 3]) < 1)
+        gather = getattr(self.loader, "gather_frames", None)
+        if gather is not None:                  # a device-resident scan: the close frames are an index gather out of its cache
+            depths, ground_segs = gather(torch.nonzero(close).reshape(-1).tolist())
+            depths = depths * ground_segs
+        else:
+            depths = (data["depths"] * data["ground_segs"])[close]
         dev = _device()
         out = dict(data)
-        out.update(depths=depths[close].float().to(dev), poses=torch.matmul(inv_pose, poses[close]).to(dev),
+        out.update(depths=depths.float().to(dev), poses=torch.matmul(inv_pose, poses[close]).to(dev),
                    intrinsics=data["intrinsics"][close].float().to(dev), inv_intrinsics=data["inv_intrinsics"][close].float().to(dev))
         return out
 
@@ -258,7 +296,8 @@ class MatterportDepthMaskingGenerator(_DepthMasking, MatterportGroundTruthGenera
     def load_data(self, idx, filename):
         scan, pos, height, direction = filename.split()
         ground_seg, depth, _, K = self.loader.load_frame_data(scan, pos, height, direction)
-        return {"depth": np.asarray(depth, np.float32)[None], "ground_seg": ground_seg, "intrinsics": np.asarray(K, np.float32)[None],
+        depth = depth.unsqueeze(0) if torch.is_tensor(depth) else np.asarray(depth, np.float32)[None]
+        return {"depth": depth, "ground_seg": ground_seg, "intrinsics": np.asarray(K, np.float32)[None],
                 "inv_intrinsics": np.linalg.pinv(K).astype(np.float32)[None]}
 
     def process_data(self, data, robust_aggregation=None):
@@ -281,3 +320,27 @@ def get_options(argv=None):
     parser.add_argument("--idx_end", type=int, default=-1, help="index after the last one to process, -1 for all")
     parser.add_argument("--footprint_threshold", type=float, default=0.75, help="threshold for ground segmentation")
     return parser.parse_args(argv)
+
+
+GENERATORS = {("kitti", "hidden_depths"): KITTIGroundTruthGenerator, ("kitti", "moving_objects"): KITTIMovingObjectDetector,
+              ("kitti", "depth_masks"): KITTIDepthMaskingGenerator, ("matterport", "hidden_depths"): MatterportGroundTruthGenerator,
+              ("matterport", "depth_masks"): MatterportDepthMaskingGenerator}
+
+
+def generator_class(data_type, type):
+    """the reference's dispatch; anything it does not name (Matterport has no optical flow: no moving objects) is NotImplementedError"""
+    cls = GENERATORS.get((data_type, type))
+    if cls is None:
+        raise NotImplementedError("no generator for --data_type %s --type %s" % (data_type, type))
+    return cls
+
+
+def main(argv=None):
+    opts = get_options(argv)
+    generator = generator_class(opts.data_type, opts.type).from_options(opts)
+    generator.run()
+    return generator
+
+
+if __name__ == "__main__":
+    main()

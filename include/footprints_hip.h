@@ -622,6 +622,69 @@ int fp_label_resize(const void* src, int64_t src_bytes, const void* samples, int
                     const void* entries, int64_t entries_len, int32_t max_entries, double* out, int32_t H, int32_t W, int32_t* status,
                     fp_stream_t stream);
 
+/* ---- device-side loader work of the training-label generators (preprocessing/ground_truth_generation/data_loader.py;
+ * csrc/gt_frames.hip) ---- */
+#define FP_GT_F16 0 /* stored dtype of a source map */
+#define FP_GT_F32 1
+#define FP_GT_F64 2
+#define FP_GT_U16 3    /* Matterport's 16-bit depth; takes no pre-scale */
+#define FP_GT_LINEAR 0  /* cv2.resize's default INTER_LINEAR on float64, enlarging as well as shrinking, through two axis tables */
+#define FP_GT_NEAREST 1 /* cv2.INTER_NEAREST; equal sizes are a copy */
+#define FP_GT_AREA2 2   /* what cv::resize makes of INTER_LINEAR when both scales are exactly 2: the fast INTER_AREA path, h == 2 H and w == 2 W */
+/* one map of a launch; fp_gt_frame_bytes() == sizeof(fp_gt_frame).  Per output element, in this order: the stored element times `pre` in the
+ * stored dtype (pre arrives rounded to that dtype; 1 = none), widened to double, resized by `method`, v = (v * post_num) / post_den in double
+ * (two rounded operations), v = v > thr ? 1 : 0 when `threshold`, rounded to float32 (nearest even). */
+typedef struct fp_gt_frame {
+  int64_t offset; /* of the map's first byte in the packed source buffer, a multiple of 8; dense [h][w] of `dtype` */
+  int64_t dst;    /* of its [H][W] float32 slot in the cache, in elements */
+  int32_t h, w;
+  int32_t dtype;  /* FP_GT_F16 .. FP_GT_U16 */
+  int32_t method; /* FP_GT_LINEAR / NEAREST / AREA2 */
+  int32_t table_x; /* index of the clamped (w -> W) table; read by FP_GT_LINEAR only */
+  int32_t table_y; /* index of the unclamped (h -> H) table */
+  int32_t threshold;
+  int32_t pad;
+  double pre, post_num, post_den, thr;
+} fp_gt_frame;
+/* one axis table of INTER_LINEAR inside the word buffer (int32 words): [out_size] first source indices, then [out_size][2] float
+ * coefficient bits; fp_gt_table_bytes() == sizeof(fp_gt_table) */
+typedef struct fp_gt_table {
+  int32_t in_size, out_size;
+  int32_t clamp;  /* 1: the horizontal form, 0: the vertical form (fp_linear_table) */
+  int32_t offset; /* of the table in the word buffer, in words */
+} fp_gt_table;
+int32_t fp_gt_frame_bytes(void);
+int32_t fp_gt_table_bytes(void);
+/* HOST function (no GPU needed): cv2's INTER_LINEAR offsets and coefficients of one axis, a reading of OpenCV's portable C++ path
+ * (imgproc/src/resize.cpp).  With scale = 1 / ((double)out / in), for every output index d: f = (float)((d + 0.5) * scale - 0.5),
+ * s = floor(f), f -= s; with `clamp` (the horizontal pass) s < 0 gives f = 0, s = 0 and s >= in - 1 gives f = 0, s = in - 1; without (the
+ * vertical pass) s and f stay, and the reader clips the row indices s and s + 1 into [0, in - 1].  offsets int32 [out] = s, coeffs float
+ * [out][2] = (1.f - f, f). */
+int fp_linear_table(int32_t in_size, int32_t out_size, int32_t clamp, int32_t* offsets, float* coeffs);
+/* HOST function (no GPU needed): what fp_gt_frame_resize checks before it launches -- every record's source extent inside the src_bytes
+ * packed bytes at a multiple of 8, its destination slot inside the cache_elems elements of the cache, dtype and method known, an integer map
+ * without pre-scale, area2 at exactly twice the target, and for linear records two tables (host records; words_len = length of the word
+ * buffer) that fit the record's sizes and lie inside the word buffer.  0, or FP_EINVAL with the first bad record in the error string. */
+int fp_gt_frame_check(const fp_gt_frame* records, int32_t n_records, int64_t src_bytes, const fp_gt_table* tables, int32_t n_tables,
+                      int64_t words_len, int64_t cache_elems, int32_t H, int32_t W);
+/* n_records maps of mixed native sizes and stored dtypes, packed in `src` (device, src_bytes long), each resized into its float32 [H][W]
+ * slot of `cache` (device, cache_elems elements) as fp_gt_frame states, bit for bit what the reference's loader computes on float64 before
+ * its .float(): linear = HResizeLinear (out = S[s] * c0 + S[s + 1] * c1, S[in - 1] * 1.0 at the right clamp) of the two rows, then
+ * VResizeLinear (h0 * b0 + h1 * b1), float coefficients widened to double, every product and sum rounded; nearest reads
+ * min(floor(d * scale), in - 1) per axis; area2 sums the 2 x 2 block in row-major order and multiplies by (double)(1.f / 4.f).
+ * `records` / `tables` are HOST arrays and are validated (fp_gt_frame_check) before anything is launched; d_records / d_tables are the same
+ * bytes on the device, d_words the tables' word buffer; the kernel applies the same rule of what a record may address to its device copies
+ * and leaves the slot of a record it turns down unwritten.  One kernel, one thread per output element, no workspace, no atomics. */
+int fp_gt_frame_resize(const void* src, int64_t src_bytes, const fp_gt_frame* records, const void* d_records, int32_t n_records,
+                       const fp_gt_table* tables, const void* d_tables, int32_t n_tables, const int32_t* d_words, int64_t words_len, float* cache,
+                       int64_t cache_elems, int32_t H, int32_t W, fp_stream_t stream);
+/* The batch of one target frame out of the cache (n_slots slots of [H][W] float32): slots (HOST, validated) / d_slots (the same on the
+ * device) = int32 [2][B], the slot behind depths[b] and the slot behind ground_segs[b]; repeats and any order are fine.
+ * depths[b] = fb / slot (IEEE float32 division) when `divide` (KITTI caches disparity), the slot itself otherwise (Matterport caches
+ * depth); ground_segs[b] = its slot. */
+int fp_gt_gather_frames(const float* cache, int64_t n_slots, const int32_t* slots, const int32_t* d_slots, int32_t B, int32_t H, int32_t W,
+                        int32_t divide, float fb, float* depths, float* ground_segs, fp_stream_t stream);
+
 /* ---- device-side reader work of the segmentation trainer (footprints/preprocessing/segmentation/datasets;
  * csrc/resample_u8.hip, csrc/seg_reader.hip) ---- */
 /* HOST function (no GPU needed): rows first .. first + count - 1 of fp_resize_coeffs' tables (bounds int32 [count][2], kk int32
