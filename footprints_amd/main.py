@@ -3,7 +3,8 @@
 `--mode train` trains from the folders the config file names, like the reference: `--config_path`'s [training_dataset]['dataset' |
 'training_data'] and splits/<dataset>/{train,val}.txt relative to the working directory (datasets/training.py: the file readers on a pool
 of threads; the frame's resize, the label maps' cv2 resizes, the depth-mask filter, flip, jitter and label algebra on the device).  With
-`--synthetic_steps N` it runs over the synthetic loader the benchmark uses instead, and no file is read.  `--mode inference` is the
+`--synthetic_steps N` it runs over the synthetic loader the benchmark uses instead, and no file is read.  Training writes TensorBoard
+files under <log_path>/<model_name>/{train,val} every `--log_freq` steps (training/logger.py) unless `--no_summaries` is given.  `--mode inference` is the
 reference's test-set program (footprints/evaluation/inference.py:31-96): the test split of `--inference_data_type` through the network, one
 .npy (and with --save_test_visualisations one .jpg) per frame -- the input of `evaluation/evaluate_model.py --predictions`."""
 from .options import Options
@@ -45,11 +46,12 @@ def main(argv=None, model_manager=None):
         ctx = DistContext.from_env()
         if ctx.is_main:
             print("In training mode!")
+        summaries = not getattr(opt, "no_summaries", False)      # train.py:47-50: the reference always writes them
         if opt.synthetic_steps <= 0:
             # the reference's create_dataloaders over the device path; under a data-parallel launch TrainManager shards the train source
             from .datasets.training import create_dataloaders
             train, val = create_dataloaders(opt)
-            return TrainManager(opt, train_loader=train, val_loader=val, dist_context=ctx).train()
+            return TrainManager(opt, train_loader=train, val_loader=val, dist_context=ctx, summaries=summaries).train()
         if opt.device_augment and opt.training_dataset == "kitti":
             # row N3: host samples as the file readers deliver them -> pinned double-buffered H2D -> flip / jitter / label kernels
             from .datasets import DeviceBatchAssembler, DeviceLoader, SyntheticSampleSource
@@ -61,7 +63,7 @@ def main(argv=None, model_manager=None):
         val = SyntheticLoader(opt.batch_size, opt.height, opt.width, max(1, opt.val_batches), seed=11)
         # under torch.distributed.run (WORLD_SIZE > 1) TrainManager turns into one replica of a data-parallel run: --batch_size is the
         # per-GPU batch, --synthetic_steps the number of GLOBAL batches per epoch (each rank trains on every world-th one)
-        TrainManager(opt, train_loader=train, val_loader=val, dist_context=ctx).train()
+        TrainManager(opt, train_loader=train, val_loader=val, dist_context=ctx, summaries=summaries).train()
     elif opt.mode == "inference":
         return run_inference(opt, model_manager)[1]
     else:

@@ -2006,6 +2006,57 @@ def vis_side_by_side(image, pred, out=None):
     return out
 
 
+# ---- the trainer's TensorBoard pictures (csrc/log_panels.hip) ---------------------------------------------------------------------------------
+LOG_PANEL_TAGS = ("image", "target_disp", "target_visible_ground", "target_all_ground", "target_ground_depth", "depth_mask", "moving_pixels",
+                  "pred_disp_1", "pred_ground_visible_1", "pred_ground_all_1", "pred_ground_disp_1", "pred_ground_disp_masked_1")
+_log_workspaces = {}
+_LOG_LABELS = ("visible_ground", "depth", "ground_depth", "moving_object_mask", "depth_mask", "all_ground")      # fp_log_panels' argument order
+
+
+def log_panel_tags(n, moving=True):
+    """the tags of the reference's log (training/logger.py:19-67) in the order it writes them: sample by sample, panel by panel"""
+    return ["%s/%d" % (t, i) for i in range(n) for t in LOG_PANEL_TAGS if moving or t != "moving_pixels"]
+
+
+def log_panels(inputs, pred, depth_range, n=4, out=None):
+    """the pictures of one log event for the first min(n, B) samples, in two launches on the current stream: inputs = the batch (image
+    float32 [B, 3, H, W] and the label maps [B, H, W] or [B, 1, H, W]; 'moving_object_mask' may be missing or None, as in the reference),
+    pred = the raw scale-1/1 output [B, 4, H, W] -> (uint8 device tensor [n, P, H, W, 3], the n * P tags in the tensor's order)"""
+    lib = _lib.load()
+    image = inputs["image"]
+    if image.dim() != 4 or image.shape[1] != 3 or pred.dim() != 4 or pred.shape[1] != 4 or pred.shape[0] != image.shape[0] or \
+            pred.shape[2:] != image.shape[2:]:
+        raise RuntimeError("footprints_amd.ops.log_panels: image must be [B, 3, H, W] and pred [B, 4, H, W]")
+    B, _, H, W = image.shape
+    n = min(int(n), B)
+    labels = []
+    for key in _LOG_LABELS:
+        t = inputs.get(key)
+        if t is None and key != "moving_object_mask":
+            raise RuntimeError("footprints_amd.ops.log_panels: the batch has no %r" % key)
+        if t is not None and t.numel() != B * H * W:
+            raise RuntimeError("footprints_amd.ops.log_panels: %s must be [B, H, W] or [B, 1, H, W]" % key)
+        labels.append(t)
+    P = 12 if labels[3] is not None else 11
+    if out is None:
+        out = torch.empty((n, P, H, W, 3), dtype=torch.uint8, device=pred.device)
+    if out.dtype != torch.uint8 or out.numel() != n * P * H * W * 3:
+        raise RuntimeError("footprints_amd.ops.log_panels: out must be uint8 [%d, %d, %d, %d, 3]" % (n, P, H, W))
+    need = lib.fp_log_panels_workspace(n, H, W)
+    if need < 0:
+        raise RuntimeError("footprints_amd.ops.log_panels: bad sizes, or too large")
+    # a buffer of its own, not ops.workspace: no recorded launch plan holds its address, so its allocation must not make TrainStep drop them
+    key = (pred.device.index, stream())
+    ws = _log_workspaces.get(key)
+    if ws is None or ws.numel() < need:
+        release(ws, "workspace:log_panels")
+        ws = _log_workspaces[key] = torch.empty(int(need), dtype=torch.uint8, device=pred.device)
+    _lib.check(lib.fp_log_panels(_f32(image, "image"), *[_f32(t, k) if t is not None else None for t, k in zip(labels, _LOG_LABELS)],
+                                 _f32(pred, "pred"), _chk(_vis_lut(pred.device)), _chk(out, "out"), B, n, H, W, float(depth_range[0]),
+                                 float(depth_range[1]), ws.data_ptr(), ws.numel(), stream()), "fp_log_panels")
+    return out.view(n, P, H, W, 3), log_panel_tags(n, moving=P == 12)
+
+
 # ---- output stage of the ground-segmentation network's inference mode (csrc/seg_infer.hip) ---------------------------------------------------
 def seg_pack(logits, image=None, want_f32=False, want_picture=False, out=None):
     """sigmoid + float16 rounding (+ the reference's test picture) of full-resolution logits in one launch: logits float32 [B, 1, H, W],

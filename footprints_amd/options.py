@@ -38,6 +38,9 @@ class Options:
         # this build
         p.add_argument("--synthetic_steps", type=int, default=0, help="batches per epoch of synthetic data (no dataset mounted)")
         p.add_argument("--device_augment", action="store_true", help="flip / colour jitter / label assembly on the GPU (row N3)")
+        # absent from the namespace unless given, like the inference flags below
+        p.add_argument("--no_summaries", action="store_true", default=argparse.SUPPRESS,
+                       help="train without writing TensorBoard files under <log_path>/<model_name>/{train,val}")
         # inference mode of this build (row N12).  Off unless given -- and absent from the namespace then (read them with getattr(opt,
         # name, False)), so that a plain parse still yields the reference's flags and the two additions above, nothing else
         p.add_argument("--device_decode", action="store_true", default=argparse.SUPPRESS,

@@ -1,6 +1,6 @@
 """The training hot loop -- drop-in counterpart of footprints/training/train.py:145-227 (`run_epoch` /
-`process_batch`), without the tensorboard plumbing that is out of scope; the loaders over the KITTI / Matterport
-folders are datasets/training.py::create_dataloaders, which main.py hands in.
+`process_batch`); the loaders over the KITTI / Matterport folders are datasets/training.py::create_dataloaders, which main.py hands in, and
+the TensorBoard writing of train.py:47-50, 170-185 is training/logger.py + training/summary.py, switched on with `summaries=True`.
 
 `TrainStep` is the MI355X fast path of `process_batch` + `zero_grad` + `backward` + `optimiser.step`
 (train.py:150-156): it drives the HIP engine's explicit forward / loss / backward / Adam schedule on static
@@ -323,16 +323,20 @@ class TrainManager:
     one device vector (no synchronisation); every 100 steps the averaged-loss console line (train.py:161-166); every
     `log_freq` steps a validation pass over `val_batches` batches in eval mode (train.py:174-185, 193-215: forward + loss
     through the drop-in `model(x)` / `Evaluator.compute_losses` surface under no_grad); per epoch the checkpoint and
-    `scheduler.step()` (train.py:189-191).  Tensorboard writing is out of scope: `self.history` keeps
-    what `log(...)` would have received.
+    `scheduler.step()` (train.py:189-191).  `self.history` keeps the averaged losses of every log event.  With `summaries=True` and a
+    `log_path` the events are also written as TensorBoard files under <log_path>/<model_name>/{train,val} (train.py:47-50), at the
+    reference's two places (train.py:170-172, 181-183): the train batch with TrainStep's outputs and the last validation batch with its
+    outputs, each with `lr` and the averaged loss -- rendered on the device and written by a thread of their own (training/logger.py), so
+    the loop waits for neither; `panels` replaces the renderer (ops.log_panels).  Off by default.
 
     Data-parallel training (north_star config #4; the reference is single-process): started through `python -m torch.distributed.run
     --nproc-per-node N -m footprints_amd.main ...`, every rank builds the same manager on its own GPU; `DistContext` (parallel.py)
     shards the loader, `broadcast_state` makes the replicas identical, `TrainStep(distributed=True)` all-reduces the gradient buckets
-    over RCCL under the backward pass, rank 0 alone prints and saves, logged losses are averaged over the ranks."""
+    over RCCL under the backward pass, rank 0 alone prints, saves and writes summaries (of its own batch, with the rank-averaged loss;
+    no collective is added), logged losses are averaged over the ranks."""
 
     def __init__(self, options=None, train_loader=None, val_loader=None, log=print, dist_context=None, model_manager=None,
-                 train_step=None, **kw):
+                 train_step=None, summaries=False, panels=None, **kw):
         if options is not None and not hasattr(options, "epochs"):       # keyword style: first positional is the loader
             train_loader, options = options, None
         self.opt = options if options is not None else _Opts(**kw)
@@ -370,13 +374,43 @@ class TrainManager:
         self.step = 0
         self.lr = self.opt.lr
         self.num_total_steps = (len(train_loader) if hasattr(train_loader, "__len__") else 0) * self.epochs
-        self.train_network_time = self.val_time = 0.0
+        self.train_network_time = self.val_time = self.log_time = 0.0
         self.history = {"train": [], "val": []}                          # (step, averaged losses) per log event
+        # TensorBoard files (train.py:47-50): rank 0 only, and only when asked for
+        self.writers, self.logger = {}, None
+        if summaries and getattr(self.opt, "log_path", None) and self.dist.is_main:
+            from .logger import PanelLogger
+            from .summary import SummaryWriter
+            for mode in ("train", "val"):
+                self.writers[mode] = SummaryWriter(os.path.join(self.opt.log_path, self.opt.model_name, mode))
+            self.logger = PanelLogger(depth_range, panels=panels)
 
     def train(self):
         self.start_time = time.time()
-        for self.epoch in range(self.epochs):
-            self.run_epoch()
+        try:
+            for self.epoch in range(self.epochs):
+                self.run_epoch()
+        finally:
+            self.close_summaries()
+
+    def close_summaries(self):
+        """write what is queued, end the writer thread and close the files; raises what the writer thread raised"""
+        logger, writers = self.logger, self.writers
+        self.logger, self.writers = None, {}
+        try:
+            if logger is not None:
+                logger.close()
+        finally:
+            for w in writers.values():
+                w.close()
+
+    def log_summaries(self, mode, inputs, outputs, losses):
+        """train.py:170-172 / 181-183: queue one log event (training/logger.py); the time spent here is `log_time`"""
+        if self.logger is None or outputs is None:
+            return
+        t0 = time.time()
+        self.logger.log(self.writers[mode], inputs, outputs, losses, self.lr, self.step)
+        self.log_time += time.time() - t0
 
     def run_epoch(self):
         for batch_idx, inputs in enumerate(self.train_loader):
@@ -395,6 +429,7 @@ class TrainManager:
                 if self.step % self.opt.log_freq == 0:
                     avg = self.dist.mean_losses(self.evaluator.get_averaged_losses(mode="train", reset=True))
                     self.history["train"].append((self.step, avg))
+                    self.log_summaries("train", inputs, getattr(self.train_step, "outputs", None), avg)
                     if self.val_loader is not None:
                         self.model.eval()
                         self.val()
@@ -417,9 +452,13 @@ class TrainManager:
                 except StopIteration:
                     self.val_iter = iter(self.val_loader)
                     inputs = next(self.val_iter)
-                self.process_batch(inputs, mode="val", return_batch_loss=False)
+                if self.logger is not None and torch.cuda.is_available():          # the logged batch is the one on the device
+                    inputs = {k: v.cuda(non_blocking=True) for k, v in inputs.items()}
+                outputs, _ = self.process_batch(inputs, mode="val", return_batch_loss=False)
         avg = self.dist.mean_losses(self.evaluator.get_averaged_losses(mode="val", reset=True))
         self.history["val"].append((self.step, avg))
+        if self.opt.val_batches > 0:
+            self.log_summaries("val", inputs, outputs, avg)
         self.val_time += time.time() - t0
         return avg
 

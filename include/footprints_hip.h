@@ -781,6 +781,25 @@ int fp_vis_overlay(const float* pred, const uint8_t* src, int64_t bytes, const v
 int fp_vis_side_by_side(const float* image, const float* pred, uint8_t* out, int32_t B, int32_t H, int32_t W, uint32_t colour0,
                         uint32_t colour1, fp_stream_t stream);
 
+/* ---- the trainer's TensorBoard pictures (footprints/training/logger.py:19-67, training/losses.py:54-78; csrc/log_panels.hip) ---- */
+/* The twelve pictures the reference logs for each of the first n samples of a batch, as bytes: out uint8 [n][P][H][W][3] with P = 12, or 11
+ * when moving_object_mask is NULL.  Panel order: the image; then target_disp, target_visible_ground, target_all_ground, target_ground_depth,
+ * depth_mask, moving_pixels (when present); then from pred, the raw float [B][4][H][W] output of scale 1/1: pred_disp through lut (uint8
+ * [256][3], the plasma table; index min(int(x * 256), 255)), pred_ground_visible, pred_ground_all, pred_ground_disp and
+ * pred_ground_disp_masked.  image float [B][3][H][W] is written as uint8(x * 255.0f) (clamped to 0..255); every other panel is
+ * (v - min) / float(double(max) - double(min)) over its own H * W values (1e5 when they are equal), then uint8(x * 255.0f), replicated to
+ * three channels; disparities are (1 / (d + 1e-7f)) * (d > 0), predicted depths 1 / (1 / max_depth + (1 / min_depth - 1 / max_depth) * p),
+ * all in float32 without fused multiply-adds.  Labels are float [B][H][W].  Two launches (block partials of the minima and maxima, then
+ * combine and map): deterministic.  The workspace query returns the bytes needed, -1 on bad sizes (n >= 1, H * W <= 2^28). */
+int64_t fp_log_panels_workspace(int32_t n, int32_t H, int32_t W);
+int fp_log_panels(const float* image, const float* visible_ground, const float* depth, const float* ground_depth,
+                  const float* moving_object_mask, const float* depth_mask, const float* all_ground, const float* pred, const uint8_t* lut,
+                  uint8_t* out, int32_t B, int32_t n, int32_t H, int32_t W, double min_depth, double max_depth, void* workspace,
+                  int64_t workspace_bytes, fp_stream_t stream);
+/* Host only: CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) of `bytes` bytes at data, continuing from crc (0 at the start) -- the
+ * checksum of the event files' record framing (training/summary.py). */
+uint32_t fp_crc32c(uint32_t crc, const void* data, int64_t bytes);
+
 /* ---- output stage of the ground-segmentation network's inference mode (footprints/preprocessing/segmentation/inference.py:80-90,
  * datasets/inference_dataset.py:39-50; csrc/seg_infer.hip) ---- */
 /* One launch over the full-resolution logit planes: sample b's plane is the H * W floats at logits + b * logit_batch_stride (any stride >=
