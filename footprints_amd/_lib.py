@@ -187,6 +187,10 @@ SIGNATURES = {
     "fp_vis_side_by_side": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.c_uint32, C.c_uint32, _P]),
     "fp_log_panels_workspace": (_I64, [_I32, _I32, _I32]),
     "fp_log_panels": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _D, _D, _P, _I64, _P]),
+    "fp_seg_log_panels_workspace": (_I64, [_I32, _I32, _I32]),
+    "fp_seg_log_panels": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_stretch_colour_workspace": (_I64, [_I32, _I32, _I32]),
+    "fp_stretch_colour": (C.c_int, [_P, _I32, _P, _P, _I32, _I32, _I32, _P, _I64, _P]),
     "fp_crc32c": (C.c_uint32, [C.c_uint32, _P, _I64]),
     "fp_seg_pack": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
     "fp_infer_pack": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _I32, _I32, _I32, _P]),

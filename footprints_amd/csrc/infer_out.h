@@ -1,11 +1,18 @@
 // Device functions of the inference output stages, shared so that every kernel that writes a test-set file rounds the same way:
-//   pack_pred_fp16_kernel (loss_adam_misc.hip), vis_side_by_side_kernel (visualise.hip), seg_pack_kernel (seg_infer.hip) and
-//   infer_pack_kernel (infer_pack.hip).
+//   pack_pred_fp16_kernel (loss_adam_misc.hip), vis_side_by_side_kernel (visualise.hip), seg_pack_kernel (seg_infer.hip),
+//   infer_pack_kernel (infer_pack.hip), and the picture kernels of stretch_map.hip, which share the sigmoid and the 12-byte stores.
 // Nothing here holds a multiply next to an add, so the functions give the same bits with and without -ffp-contract=off; the division
 // is the correctly rounded one (no fast-math anywhere in this library).
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
+
+// the segmentation network's probability: the accurate exponential and a correctly rounded division (seg_pack_kernel, the log's prediction panel)
+__device__ __forceinline__ float sigmoid_exact(float x) {
+  const float e = expf(-x);
+  const float den = 1.0f + e;
+  return 1.0f / den;
+}
 
 // one element of the test-set .npy file: sigmoid on the two mask channels (0, 1), depth channels (2, 3) unchanged, rounded to float16
 // to nearest even (numpy's astype), subnormals kept

@@ -19,7 +19,7 @@
 #include <hip/hip_fp16.h>
 
 #include "fp_common.h"
-#include "infer_out.h"      // fp_pack12 / fp_store12: 4 pixels -> the 12 bytes of an [..][3] row
+#include "infer_out.h"      // sigmoid_exact; fp_pack12 / fp_store12: 4 pixels -> the 12 bytes of an [..][3] row
 
 namespace {
 
@@ -36,12 +36,6 @@ struct SegPackArgs {
   int32_t H, W, quads;      // quads = ceil(W / 4)
   unsigned vec;             // SP_VEC_*
 };
-
-__device__ __forceinline__ float sigmoid_exact(float x) {
-  const float e = expf(-x);
-  const float den = 1.0f + e;
-  return 1.0f / den;
-}
 
 __device__ __forceinline__ unsigned int image_byte(float v) {
   const float c = fminf(fmaxf(v, 0.0f), 1.0f);      // a NaN gives 0

@@ -2057,6 +2057,122 @@ def log_panels(inputs, pred, depth_range, n=4, out=None):
     return out.view(n, P, H, W, 3), log_panel_tags(n, moving=P == 12)
 
 
+# ---- stretched maps as pictures (csrc/stretch_map.hip) ----------------------------------------------------------------------------------------
+_colour_tables = {}
+_stretch_workspaces = {}
+
+
+def colour_table(name, rule):
+    """uint8 [256, 3] numpy, read-only: the 256 colours of matplotlib's map `name` as bytes, read from matplotlib at first use.
+    rule "bytes": `(cmap(arange(256))[:, :3] * 255).astype(uint8)` in float64, matplotlib's own table for `bytes=True` (imsave);
+    rule "float32": `(float32(colour) * 255).astype(uint8)`, what tensorboardX makes of the float colours a log hands it"""
+    import numpy as np
+    key = (str(name), str(rule))
+    lut = _colour_tables.get(key)
+    if lut is None:
+        if rule not in ("bytes", "float32"):
+            raise ValueError("footprints_amd.ops.colour_table: rule must be 'bytes' or 'float32'")
+        import matplotlib
+        rgb = matplotlib.colormaps[name].resampled(256)(np.arange(256))[:, :3]
+        if rule == "float32":
+            rgb = rgb.astype(np.float32) * np.float32(255)
+        else:
+            rgb = rgb * 255
+        lut = _colour_tables[key] = np.ascontiguousarray(rgb.astype(np.uint8))
+        lut.setflags(write=False)
+    return lut
+
+
+def _colour_lut(name, rule, device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (str(name), str(rule), device)
+    t = _colour_tables.get(key)
+    if t is None:
+        t = _colour_tables[key] = torch.from_numpy(colour_table(name, rule).copy()).to(device)
+    return t
+
+
+def _own_workspace(cache, tag, need, device):
+    """a buffer of its own, not ops.workspace: no recorded launch plan holds its address, so its allocation must not make TrainStep drop them"""
+    key = (device.index, stream())
+    ws = cache.get(key)
+    if ws is None or ws.numel() < need:
+        release(ws, "workspace:" + tag)
+        ws = cache[key] = torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def seg_log_panel_tags(n):
+    return ["Image/%d" % i for i in range(n)]
+
+
+def seg_log_panels(inputs, logits, n=10, out=None):
+    """the pictures of the segmentation trainer's log event (reference preprocessing/segmentation/logger.py:28-42) for the first
+    min(n, B) samples, in two launches on the current stream: inputs = the batch ('image' float32 [B, 3, H, W], 'ground_mask' float32
+    [B, H, W]); logits = the full-resolution logit map float32 [B, 1, H, W] or [B, H, W], dense or a `[:, 0:1]` view of the engine's
+    [B, 2, H, W] head buffer (its batch stride is passed through, nothing is copied; any other non-contiguity raises)
+    -> (uint8 device tensor [n, H, 3 W, 3]: image | ground truth | prediction, the tags "Image/0", ...)"""
+    lib = _lib.load()
+    image, mask = inputs["image"], inputs["ground_mask"]
+    if image.dim() != 4 or image.shape[1] != 3 or not image.is_cuda:
+        raise RuntimeError("footprints_amd.ops.seg_log_panels: image must be a float32 CUDA tensor [B, 3, H, W]")
+    B, _, H, W = image.shape
+    if logits.dim() == 3:
+        logits = logits.unsqueeze(1)
+    if tuple(logits.shape) != (B, 1, H, W) or logits.dtype != torch.float32 or logits.device != image.device:
+        raise RuntimeError("footprints_amd.ops.seg_log_panels: logits must be float32 [B, 1, H, W] beside the image")
+    if mask.numel() != B * H * W:
+        raise RuntimeError("footprints_amd.ops.seg_log_panels: ground_mask must be [B, H, W]")
+    sb, _, sh, sw = logits.stride()
+    if B == 1:
+        sb = H * W
+    if (W > 1 and sw != 1) or (H > 1 and sh != W) or sb < H * W:
+        raise RuntimeError("footprints_amd.ops.seg_log_panels: logits must be dense planes at a batch stride >= H * W "
+                           "(a [:, 0:1] view of a contiguous [B, C, H, W] buffer), got strides %r" % (tuple(logits.stride()),))
+    n = min(int(n), B)
+    if out is None:
+        out = torch.empty((n, H, 3 * W, 3), dtype=torch.uint8, device=image.device)
+    if out.dtype != torch.uint8 or out.numel() != n * H * W * 9:
+        raise RuntimeError("footprints_amd.ops.seg_log_panels: out must be uint8 [%d, %d, %d, 3]" % (n, H, 3 * W))
+    need = lib.fp_seg_log_panels_workspace(n, H, W)
+    if need < 0:
+        raise RuntimeError("footprints_amd.ops.seg_log_panels: bad sizes, or too large")
+    ws = _own_workspace(_stretch_workspaces, "seg_log_panels", need, image.device)
+    _lib.check(lib.fp_seg_log_panels(_f32(image, "image"), _f32(mask, "ground_mask"), logits.data_ptr(), int(sb),
+                                     _chk(_colour_lut("plasma", "float32", image.device)), _chk(out, "out"), B, n, H, W, ws.data_ptr(), ws.numel(),
+                                     stream()), "fp_seg_log_panels")
+    return out.view(n, H, 3 * W, 3), seg_log_panel_tags(n)
+
+
+def stretch_colour(maps, cmap="viridis", out=None):
+    """matplotlib's `plt.imsave` of 2-D arrays (Normalize by the map's own minimum and maximum, the colour map with bytes=True), in two
+    launches on the current stream: maps = a CUDA tensor [B, H, W] or [H, W] of float32, uint8 or bool, finite
+    -> uint8 device tensor [B, H, W, 3] (or [H, W, 3])"""
+    lib = _lib.load()
+    if not maps.is_cuda or maps.dim() not in (2, 3) or maps.dtype not in (torch.float32, torch.uint8, torch.bool):
+        raise RuntimeError("footprints_amd.ops.stretch_colour: maps must be a CUDA tensor [B, H, W] or [H, W] of float32, uint8 or bool")
+    single = maps.dim() == 2
+    m = maps.unsqueeze(0) if single else maps
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8)
+    if not m.is_contiguous():
+        m = m.contiguous()
+    B, H, W = m.shape
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=m.device)
+    if out.dtype != torch.uint8 or out.numel() != B * H * W * 3:
+        raise RuntimeError("footprints_amd.ops.stretch_colour: out must be uint8 [%d, %d, %d, 3]" % (B, H, W))
+    need = lib.fp_stretch_colour_workspace(B, H, W)
+    if need < 0:
+        raise RuntimeError("footprints_amd.ops.stretch_colour: bad sizes, or too large")
+    ws = workspace(need, m.device, "stretch")
+    _lib.check(lib.fp_stretch_colour(_chk(m, "maps"), 1 if m.dtype == torch.uint8 else 0, _chk(_colour_lut(cmap, "bytes", m.device)),
+                                     _chk(out, "out"), B, H, W, ws.data_ptr(), ws.numel(), stream()), "fp_stretch_colour")
+    return out.view(H, W, 3) if single else out.view(B, H, W, 3)
+
+
 # ---- output stage of the ground-segmentation network's inference mode (csrc/seg_infer.hip) ---------------------------------------------------
 def seg_pack(logits, image=None, want_f32=False, want_picture=False, out=None):
     """sigmoid + float16 rounding (+ the reference's test picture) of full-resolution logits in one launch: logits float32 [B, 1, H, W],
@@ -2205,17 +2321,20 @@ class JpegTables:
 _jpeg_tables = {}
 
 
-def jpeg_tables(quality=95):
-    """JpegTables of the installed Pillow at `quality`: a small RGB dummy is encoded once per quality and its header parsed; nothing of a
-    JPEG header is compiled into this package"""
-    t = _jpeg_tables.get(int(quality))
+def jpeg_tables(quality=95, dpi=None):
+    """JpegTables of the installed Pillow at `quality`: a small RGB dummy is encoded once per (quality, dpi) and its header parsed; nothing
+    of a JPEG header is compiled into this package.  dpi = None, or the (x, y) pair handed to Pillow's save: it changes the JFIF unit and
+    density bytes of the header and nothing else (matplotlib's imsave writes dpi=(100, 100))"""
+    key = (int(quality), None if dpi is None else (dpi[0], dpi[1]))
+    t = _jpeg_tables.get(key)
     if t is None:
         import io
         import numpy as np
         from PIL import Image
         buf = io.BytesIO()
-        Image.fromarray(np.zeros((16, 16, 3), dtype=np.uint8)).save(buf, format="JPEG", quality=int(quality))
-        t = _jpeg_tables[int(quality)] = JpegTables(buf.getvalue())
+        extra = {} if dpi is None else {"dpi": key[1]}
+        Image.fromarray(np.zeros((16, 16, 3), dtype=np.uint8)).save(buf, format="JPEG", quality=int(quality), **extra)
+        t = _jpeg_tables[key] = JpegTables(buf.getvalue())
     return t
 
 
@@ -2268,19 +2387,19 @@ def jpeg_encode_packed(src, src_bytes, samples, B, quality=95, out=None, max_h=N
     return out, table
 
 
-def jpeg_files(scans, table, shapes, quality=95):
+def jpeg_files(scans, table, shapes, quality=95, dpi=None):
     """complete files from the encoder's output on the HOST: scans (bytes-like, at least the bytes the table's last row counts), table
     (int64 [B + 1, 2] numpy), shapes [(h, w), ...] -> list of bytes: header + scan + EOI"""
     if int(table[len(shapes)][1]) != 0:
         raise ValueError("footprints_amd.ops.jpeg_encode: a sample record was turned down on the device, or the output buffer was too small")
-    t = jpeg_tables(quality)
+    t = jpeg_tables(quality, dpi)
     view = memoryview(scans)
     return [t.file_header(h, w) + bytes(view[int(table[b][0]):int(table[b][0]) + int(table[b][1])]) + b"\xff\xd9" for b, (h, w) in enumerate(shapes)]
 
 
-def jpeg_encode(pictures, quality=95):
-    """Pillow's `Image.fromarray(p).save(f, format="JPEG", quality=quality)` for a batch, byte for byte (Pillow on libjpeg-turbo), encoded
-    on the device: pictures = a uint8 device tensor [B, H, W, 3], or a list of numpy uint8 [h, w, 3] of any sizes (uploaded here)
+def jpeg_encode(pictures, quality=95, dpi=None):
+    """Pillow's `Image.fromarray(p).save(f, format="JPEG", quality=quality)` (with `dpi=dpi` when one is given: only the files' headers
+    differ) for a batch, byte for byte (Pillow on libjpeg-turbo), encoded on the device: pictures = a uint8 device tensor [B, H, W, 3], or a list of numpy uint8 [h, w, 3] of any sizes (uploaded here)
     -> list of B bytes objects, each a complete file.  Copies the length table, waits, copies exactly the bytes used."""
     import numpy as np
     if torch.is_tensor(pictures):
@@ -2299,7 +2418,7 @@ def jpeg_encode(pictures, quality=95):
     out, table = jpeg_encode_packed(packed, total, torch.from_numpy(records).to(packed.device), len(shapes), quality, max_h=max_h, max_w=max_w)
     table = table.cpu().numpy()                  # waits
     used = int(table[len(shapes)][0])
-    return jpeg_files(out[:used].cpu().numpy().tobytes() if used else b"", table, shapes, quality)
+    return jpeg_files(out[:used].cpu().numpy().tobytes() if used else b"", table, shapes, quality, dpi)
 
 
 # ---- baseline JPEG decoder (csrc/jpeg_decode.hip) ------------------------------------------------------------------------------------------

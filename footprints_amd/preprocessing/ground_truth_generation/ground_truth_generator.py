@@ -88,11 +88,41 @@ class GroundTruthGenerator:
     def load_data(self, idx, filename):
         raise NotImplementedError
 
+    def _to_host(self, result):
+        """the device tensor a generator's result is -> the array that is saved; the tensor is kept for the picture of save_result"""
+        self._device_result = result
+        return result.cpu().numpy()
+
     def save_result(self, result, savepath, filename, save_viz=False):
-        """<savepath>/data/<filename, zero-filled to 10>.npy, the layout the datasets read.  Visualisation images are not written."""
+        """<savepath>/data/<filename, zero-filled to 10>.npy, the layout the datasets read.  With save_viz also
+        <savepath>/visualisations/<the same name>.jpg, the file the reference's `plt.imsave` writes: the result stretched by its own
+        minimum and maximum through viridis (ops.stretch_colour, from the device tensor the result came from: nothing is uploaded
+        again), as a JPEG of quality 75 with dpi (100, 100).  Pillow encodes the RGB bytes on the host; with --device_jpeg
+        ops.jpeg_encode does on the device and only the file's bytes come back."""
         _savepath = os.path.join(savepath, "data")
         os.makedirs(_savepath, exist_ok=True)
         np.save(os.path.join(_savepath, "{}.npy".format(str(filename).zfill(10))), result)
+        if save_viz:
+            _savepath = os.path.join(savepath, "visualisations")
+            os.makedirs(_savepath, exist_ok=True)
+            with open(os.path.join(_savepath, "{}.jpg".format(str(filename).zfill(10))), "wb") as fh:
+                fh.write(self.visualisation(result))
+
+    def visualisation(self, result):
+        """-> the bytes of the .jpg of `result`, the array process_data has just returned"""
+        device = getattr(self, "_device_result", None)
+        self._device_result = None
+        if device is None or tuple(device.shape) != tuple(result.shape):      # a result made on the host (too few ground pixels: zeros)
+            host = np.ascontiguousarray(result, dtype=np.uint8 if result.dtype == np.bool_ else np.float32)
+            device = torch.from_numpy(host).to(_device())
+        picture = ops.stretch_colour(device)
+        if getattr(self.opts, "device_jpeg", False):
+            return ops.jpeg_encode(picture.unsqueeze(0), quality=75, dpi=(100, 100))[0]
+        import io
+        from PIL import Image
+        buf = io.BytesIO()
+        Image.fromarray(picture.cpu().numpy()).save(buf, format="JPEG", dpi=(100, 100))
+        return buf.getvalue()
 
     def compute_depth_mask(self, depth, ground_seg, K, invK, samples=None):
         """The depth mask of *untraversable* pixels: depth [1,H,W], ground_seg [H,W], K / invK [1,4,4] -> bool array [H,W].
@@ -110,14 +140,14 @@ class GroundTruthGenerator:
             samples = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int32)).to(world.device)
         fit = ops.gt_plane_score(world, ground_seg, self.footprint_threshold, samples)
         keys = ops.gt_flatten_splat(world, ground_seg, self.footprint_threshold, K, fit["best_plane"])
-        return ops.gt_depth_mask(keys, depth, ground_seg).cpu().numpy()
+        return self._to_host(ops.gt_depth_mask(keys, depth, ground_seg))
 
     def process_data(self, data, robust_aggregation=True):
         """data: `depths` [B,H,W], `poses`, `intrinsics`, `inv_intrinsics` [B,4,4] on the device -> the [H,W] float32 array that is
         saved: per pixel the median of the depths the source frames project there (0 unless more than 2 frames agree on the pixel
         when `robust_aggregation`, more than 0 otherwise)"""
         keys = self.projector.warp_splat(data["depths"], data["inv_intrinsics"], data["poses"], data["intrinsics"])
-        return ops.gt_aggregate(keys, self.height, self.width, robust_aggregation).cpu().numpy()
+        return self._to_host(ops.gt_aggregate(keys, self.height, self.width, robust_aggregation))
 
     def run(self):
         time_before_batch = time.time()
@@ -212,7 +242,7 @@ class KITTIMovingObjectDetector(KITTIGroundTruthGenerator):
         disparity, flow = _upload(base_data["disparity"], "disparity"), _upload(base_data["flow"], "flow")
         fx_baseline = float(self.K[0, 0, 0]) * self.loader.stereo_baseline
         mask = ops.gt_moving_mask(disparity, flow, _upload(self.invK, "invK"), _upload(T, "T"), _upload(self.K, "K"), fx_baseline)
-        return mask.cpu().numpy()
+        return self._to_host(mask)
 
 
 class _DepthMasking:
@@ -221,6 +251,7 @@ class _DepthMasking:
     def _mask_or_zeros(self, depth, ground_seg, K, invK):
         ground_seg = _upload(ground_seg, "ground_seg")
         if int(ops.gt_ground_count(ground_seg, self.footprint_threshold).item()) < 100:
+            self._device_result = None
             return np.zeros([self.height, self.width])
         return self.compute_depth_mask(depth, ground_seg, K, invK)
 
@@ -314,7 +345,12 @@ def get_options(argv=None):
     parser.add_argument("--data_type", type=str, choices=["kitti", "matterport"])
     parser.add_argument("--save_folder_name", type=str,
                         help="folder name to save to; defaults to 'hidden_depths', 'moving_object_masks' or 'depth_masks' by type")
-    parser.add_argument("--save_visualisations", action="store_true", help="accepted for compatibility: images are not written")
+    parser.add_argument("--save_visualisations", action="store_true",
+                        help="also write <savepath>/visualisations/<name>.jpg beside every data/<name>.npy: the result through viridis, "
+                             "the file matplotlib's imsave writes")
+    # absent from the namespace unless given: the namespace without it is the reference's
+    parser.add_argument("--device_jpeg", action="store_true", default=argparse.SUPPRESS,
+                        help="with --save_visualisations: encode the pictures on the GPU (same files as Pillow writes)")
     parser.add_argument("--textfile", type=str, help="textfile containing frames to be computed")
     parser.add_argument("--idx_start", type=int, default=0, help="first index of the textfile to process (splitting work across GPUs)")
     parser.add_argument("--idx_end", type=int, default=-1, help="index after the last one to process, -1 for all")

@@ -1,4 +1,5 @@
-"""python -m footprints_amd.preprocessing.segmentation.main: train the ground-segmentation network on device-assembled batches, or
+"""python -m footprints_amd.preprocessing.segmentation.main: train the ground-segmentation network on device-assembled batches (TensorBoard
+files under <log_path>/<model_name>/{train,val} every `--log_freq` steps unless `--no_summaries` is given), or
 (`--mode inference`) run the trained network over a dataset's train and val frames and write the ground-probability maps that
 ground_truth_generation reads (reference: footprints/preprocessing/segmentation/main.py)."""
 from .options import SegmentationOptions
@@ -9,7 +10,7 @@ def main(args=None):
     if options.mode == "train":
         print("In training mode!")
         from .train import Trainer
-        Trainer(options).train()
+        Trainer(options, summaries=not options.no_summaries).train()      # train.py:58-62: the reference always writes them
     elif options.mode == "inference":
         print("In inference mode!")
         from .inference import Tester

@@ -25,6 +25,8 @@ class SegmentationOptions:
         p.add_argument("--num_workers", help="the number of workers for dataloading", type=int, default=4)
         p.add_argument("--model_name", help="the name of the model for saving", type=str, default="model")
         p.add_argument("--log_path", help="the path to save logs and trained models to", type=str, default="./logs")
+        p.add_argument("--no_summaries", action="store_true",
+                       help="train without writing TensorBoard files under <log_path>/<model_name>/{train,val}")
         # testing
         p.add_argument("--load_path", help="the model path to load from", type=str)
         p.add_argument("--test_save_folder", help="folder to save results to - added to training_data path from config", type=str,

@@ -1,8 +1,10 @@
 """Trainer of the ground-segmentation network on device-assembled batches (reference: footprints/preprocessing/segmentation/train.py).
 
 Per step: forward, the four bilinear up-sizes + per-sample masked BCE / 4 (one kernel, losses.py), backward, Adam at `lr`.  StepLR(10) is
-stepped at the START of every epoch, as the reference does.  Every `log_freq` steps the tracked losses are printed (there is no
-tensorboardX here) after `val_batches` validation batches from a cycling iterator.  `epoch_{n}.pth` holds the model's state_dict alone.
+stepped at the START of every epoch, as the reference does.  Every `log_freq` steps the tracked losses are printed after `val_batches`
+validation batches from a cycling iterator; with `summaries=True` the train batch and the last validation batch are also logged to
+`<log_path>/<model_name>/{train,val}` event files at the reference's points (train.py:132, 167), rendered on the device and written by a
+thread of their own (logger.py).  `epoch_{n}.pth` holds the model's state_dict alone.
 Single process: data parallelism is not part of this trainer."""
 import os
 import random
@@ -15,9 +17,10 @@ from .network import Segmentor
 
 
 class Trainer:
-    def __init__(self, options, model=None, train_loader=None, val_loader=None):
+    def __init__(self, options, model=None, train_loader=None, val_loader=None, summaries=False, panels=None):
         """model / train_loader / val_loader: injected objects (tests, benchmarks); by default the Segmentor of the options and
-        DeviceLoaders over the file readers named in the config file"""
+        DeviceLoaders over the file readers named in the config file.  summaries: write the TensorBoard files (train.py:58-62);
+        panels: the renderer handed to logger.SegPanelLogger (ops.seg_log_panels by default)"""
         print("setting up...")
         self.opt = options
         if not torch.cuda.is_available():
@@ -43,6 +46,13 @@ class Trainer:
         print("validation images: {}".format(len(self.val_loader.dataset)))
         self.step, self.epoch, self.lr = 0, 0, self.opt.lr
         self.history = []                    # one entry per logged step: dict(epoch, step, lr, batch_loss, train, val)
+        self.writers, self.logger = {}, None
+        if summaries:
+            from ...training.summary import SummaryWriter
+            from .logger import SegPanelLogger
+            for mode in ("train", "val"):
+                self.writers[mode] = SummaryWriter(os.path.join(self.opt.log_path, self.opt.model_name, mode))
+            self.logger = SegPanelLogger(panels=panels)
 
     def create_dataloaders(self):
         """train.py:64-101 with the file readers of datasets/ and the device path: ConcatDataset of the chosen datasets, shuffled, so
@@ -71,20 +81,40 @@ class Trainer:
     def train(self):
         print("training")
         self.step = 0
-        for self.epoch in range(self.opt.epochs):
-            self.run_epoch()
+        try:
+            for self.epoch in range(self.opt.epochs):
+                self.run_epoch()
+        finally:
+            self.close_summaries()
+
+    def close_summaries(self):
+        """write what is queued, end the writer thread and close the files; raises what the writer thread raised"""
+        logger, writers = self.logger, self.writers
+        self.logger, self.writers = None, {}
+        try:
+            if logger is not None:
+                logger.close()
+        finally:
+            for w in writers.values():
+                w.close()
+
+    def log_summaries(self, mode, inputs, outputs, losses):
+        """train.py:132 / 167: queue one log event on the stream that trains (logger.py)"""
+        if self.logger is not None:
+            self.logger.log(self.writers[mode], inputs, outputs, losses, self.lr, self.step, num_outputs=10)
 
     def run_epoch(self):
         self.scheduler.step()                # at the start of the epoch (train.py:111)
         for inputs in self.train_loader:
             self.model.train()
-            _, batch_loss = self.forward(inputs)
+            outputs, batch_loss = self.forward(inputs)
             self.model.zero_grad()
             batch_loss.backward()
             self.optimiser.step()
             self.lr = self.scheduler.get_last_lr()[0]
             if (self.step % self.opt.log_freq) == 0:
                 tracked = self.evaluator.get_tracked_losses()
+                self.log_summaries("train", inputs, outputs, tracked)
                 val = self.run_validation(self.opt.val_batches)
                 self.history.append(dict(epoch=self.epoch, step=self.step, lr=self.lr, batch_loss=float(batch_loss.detach()),
                                          train={k: float(v) for k, v in tracked.items()}, val={k: float(v) for k, v in val.items()}))
@@ -104,8 +134,11 @@ class Trainer:
                 except StopIteration:
                     self.val_iter = iter(self.val_loader)
                     inputs = next(self.val_iter)
-                self.forward(inputs)
-            return self.evaluator.get_tracked_losses()
+                outputs, _ = self.forward(inputs)
+            tracked = self.evaluator.get_tracked_losses()
+            if batches > 0:
+                self.log_summaries("val", inputs, outputs, tracked)
+            return tracked
 
     def forward(self, inputs):
         outputs = self.model(inputs["image"])

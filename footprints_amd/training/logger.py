@@ -35,7 +35,8 @@ def scale_one_prediction(outputs):
 
 
 class PanelLogger:
-    """`log(writer, inputs, outputs, losses, lr, step)` with the reference's arguments, returning as soon as the work is queued.
+    """`log(writer, inputs, outputs, losses, lr, step)` with the reference's arguments, returning as soon as the work is queued.  `queue`
+    is the same machinery with the renderer and the scalar list from the caller (preprocessing/segmentation/logger.py uses it).
 
     panels: the renderer, `panels(inputs, pred, depth_range, n=..., out=...) -> (uint8 tensor [n, P, H, W, 3], tags)`; ops.log_panels by
     default.  A renderer that returns a host tensor (the tests' stand-in) needs no copy and no event."""
@@ -55,6 +56,23 @@ class PanelLogger:
 
     # ---- training thread ----------------------------------------------------------------------------------------------------------------
     def log(self, writer, inputs, outputs, losses, lr, step):
+        """the footprint trainer's event: `lr`, `loss`, and the twelve pictures of each logged sample"""
+        def render(device_out):
+            pred = scale_one_prediction(outputs)
+            if not pred.is_contiguous():
+                pred = pred.contiguous()
+            batch = {k: (v if v is None or v.is_contiguous() else v.contiguous()) for k, v in inputs.items()}
+            B, _, H, W = pred.shape
+            P = 12 if batch.get("moving_object_mask") is not None else 11
+            out = device_out(pred.device, (min(self.n, B), P, H, W, 3))
+            return self.panels(batch, pred, self.depth_range, n=self.n, out=out)
+        self.queue(writer, render, lambda: [("lr", float(lr)), ("loss", float(losses["loss"]))], step)
+
+    def queue(self, writer, render, scalars, step):
+        """one log event of any trainer.  render(device_out) -> (uint8 tensor whose last three dimensions are one picture [h, w, 3], one
+        tag per picture), where device_out(device, shape) is the slot's device buffer if it has that device and shape, else None (the
+        renderer then allocates, and its result becomes the slot's buffer); scalars() -> [(tag, value), ...], written before the
+        pictures.  Both run here, on the training thread; whatever they raise is raised by the next call or by close()."""
         self._raise_pending()
         if self._thread is None:
             self._thread = threading.Thread(target=self._run, name="footprints-summary-writer", daemon=True)
@@ -62,16 +80,11 @@ class PanelLogger:
         slot = self._take_slot()
         try:
             wall = time.time()
-            pred = scale_one_prediction(outputs)
-            if not pred.is_contiguous():
-                pred = pred.contiguous()
-            inputs = {k: (v if v is None or v.is_contiguous() else v.contiguous()) for k, v in inputs.items()}
-            out = slot["device"]
-            B, _, H, W = pred.shape
-            P = 12 if inputs.get("moving_object_mask") is not None else 11
-            if out is not None and (out.device != pred.device or tuple(out.shape) != (min(self.n, B), P, H, W, 3)):
-                out = None
-            panels, tags = self.panels(inputs, pred, self.depth_range, n=self.n, out=out)
+
+            def device_out(device, shape):
+                out = slot["device"]
+                return out if out is not None and out.device == device and tuple(out.shape) == tuple(shape) else None
+            panels, tags = render(device_out)
             if panels.is_cuda:
                 slot["device"] = panels
                 nbytes = panels.numel()
@@ -84,7 +97,7 @@ class PanelLogger:
                 pixels, event = slot["host"][:nbytes].numpy().reshape(tuple(panels.shape)), slot["event"]
             else:
                 pixels, event = panels.numpy(), None
-            scalars = [("lr", float(lr)), ("loss", float(losses["loss"]))]
+            scalars = list(scalars())
         except Exception as exc:                 # like a failure of the writer thread: raised by the next log or by close
             self._free.put(slot)
             if self._error is None:
@@ -136,7 +149,7 @@ class PanelLogger:
                     t0 = time.time()
                     for tag, value in scalars:
                         writer.add_scalar(tag, value, step, walltime=wall)
-                    flat = pixels.reshape((-1,) + pixels.shape[2:])
+                    flat = pixels.reshape((-1,) + pixels.shape[-3:])
                     if len(tags) != flat.shape[0]:
                         raise RuntimeError("log: %d tags for %d pictures" % (len(tags), flat.shape[0]))
                     for tag, picture in zip(tags, flat):

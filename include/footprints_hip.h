@@ -796,6 +796,24 @@ int fp_log_panels(const float* image, const float* visible_ground, const float* 
                   const float* moving_object_mask, const float* depth_mask, const float* all_ground, const float* pred, const uint8_t* lut,
                   uint8_t* out, int32_t B, int32_t n, int32_t H, int32_t W, double min_depth, double max_depth, void* workspace,
                   int64_t workspace_bytes, fp_stream_t stream);
+/* ---- stretched maps as pictures (csrc/stretch_map.hip) ---- */
+/* The segmentation trainer's TensorBoard picture (footprints/preprocessing/segmentation/logger.py:28-42, then tensorboardX's
+ * (x.astype(float32) * 255).astype(uint8)) for the first n samples of a batch: out uint8 [n][H][3 W][3] = image | ground truth | prediction.
+ * image float [B][3][H][W]: (x - min) / float(double(max) - double(min)) over the sample's three channels together (1e5 when they are
+ * equal), then (int)(v * 255.0f).  ground_mask float [B][H][W]: red 255 where it is 1, else 0; green and blue 0.  logits: the
+ * full-resolution logit plane of sample s at logits + s * logit_batch_stride (channel 0 of the [B][2][H][W] head buffer, as fp_seg_pack takes
+ * it); p = the sigmoid of fp_seg_pack, colour lut[min((int)(p * 256.0f), 255)] with lut uint8 [256][3] from the caller.  Two launches
+ * (block partials of the minimum and maximum, then combine and map): deterministic.  The workspace query returns the bytes needed, -1 on
+ * bad sizes (1 <= n <= 65535, H * W <= 2^27). */
+int64_t fp_seg_log_panels_workspace(int32_t n, int32_t H, int32_t W);
+int fp_seg_log_panels(const float* image, const float* ground_mask, const float* logits, int64_t logit_batch_stride, const uint8_t* lut,
+                      uint8_t* out, int32_t B, int32_t n, int32_t H, int32_t W, void* workspace, int64_t workspace_bytes, fp_stream_t stream);
+/* matplotlib's imsave of 2-D arrays: maps [B][H][W], float (is_u8 = 0) or uint8 (is_u8 = 1; booleans as bytes), finite -> out uint8
+ * [B][H][W][3].  Per map: n = float(double(float(x - min)) / (double(max) - double(min))), 0 everywhere when max == min; colour
+ * lut[min((int)(n * 256.0f), 255)] with lut uint8 [256][3] from the caller.  Two launches, as above; same workspace rule. */
+int64_t fp_stretch_colour_workspace(int32_t B, int32_t H, int32_t W);
+int fp_stretch_colour(const void* maps, int32_t is_u8, const uint8_t* lut, uint8_t* out, int32_t B, int32_t H, int32_t W, void* workspace,
+                      int64_t workspace_bytes, fp_stream_t stream);
 /* Host only: CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) of `bytes` bytes at data, continuing from crc (0 at the start) -- the
  * checksum of the event files' record framing (training/summary.py). */
 uint32_t fp_crc32c(uint32_t crc, const void* data, int64_t bytes);
