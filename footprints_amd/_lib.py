@@ -64,8 +64,8 @@ class ResizeSample(C.Structure):
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("table_h", C.c_int32), ("table_v", C.c_int32)]
 
 
-LABEL_U8, LABEL_F16, LABEL_F32, LABEL_F64 = range(4)        # FP_LABEL_*: stored dtype of a label map
-LABEL_ZERO, LABEL_NEAREST, LABEL_AREA = range(3)            # FP_LABEL_*: resize method
+LABEL_U8, LABEL_F16, LABEL_F32, LABEL_F64, LABEL_U16 = range(5)      # FP_LABEL_*: stored dtype of a label map
+LABEL_ZERO, LABEL_NEAREST, LABEL_AREA, LABEL_PIL_NEAREST = range(4)  # FP_LABEL_*: resize method
 LABEL_MAX_ENTRIES = 12                                      # FP_LABEL_MAX_ENTRIES
 
 

@@ -1,11 +1,19 @@
 // Device-side reader work of the Footprints trainer: the cv2 resizes of the label maps.
 //   reference: footprints/datasets/footprint_dataset.py:82-94 (load_and_resize_npy: .astype(float), np.fliplr, cv2.resize with INTER_AREA or
-//              INTER_NEAREST on float64, times the disparity multiplier), kitti_dataset.py:65-105, matterport_dataset.py:55-89.
+//              INTER_NEAREST on float64, times the disparity multiplier), kitti_dataset.py:65-105, matterport_dataset.py:55-89;
+//              footprint_dataset.py:73-80 (load_and_resize_image: Pillow's resize(NEAREST) of Matterport's 16-bit depth PNG, then the transpose).
 // fp_label_resize: one launch resizes every map of a batch -- mixed native sizes, mixed stored dtypes -- into the float64 [K][B][H][W] buffer
 // that fp_filter_depth_mask and fp_assemble_labels read.  OpenCV's arithmetic is restated operation by operation (imgproc/src/resize.cpp:
 // resizeNN, resizeAreaFast_, computeResizeAreaTab + resizeArea_ for double data): float weights widened to double, products and sums in
 // double in OpenCV's order.  This file is compiled with -ffp-contract=off and spells every product and sum as __dmul_rn / __dadd_rn: a fused
 // multiply-add anywhere would change bits.  No atomics, no reductions: every output element is written once, by one thread.
+// FP_LABEL_PIL_NEAREST is Pillow's NEAREST instead of cv2's: a plain gather of src = min(floor((dst + 0.5) * in / out), in - 1) per axis, in
+// integers ((2 * dst + 1) * in / (2 * out)); it enlarges as well as shrinks.  Its flip differs from the cv2 methods': the reference flips
+// the .npy maps FIRST and resizes them then (source column w - 1 - index[x] lands at final column x), but resizes the depth PNG first and
+// transposes it THEN (final column x holds source column index[W - 1 - x]).  The two orders differ wherever (x + 0.5) * w / W is a whole
+// number -- floor(w - t) is w - 1 - floor(t) for every other t -- which is every column at an even ratio such as Matterport's 1280 -> 640,
+// and no column at 53 -> 32.  So a flipped PIL_NEAREST record reads the source unmirrored: stored column c -- which fp_assemble_labels
+// moves to W - 1 - c -- holds source column index[c].
 #include <float.h>
 #include <math.h>
 
@@ -18,8 +26,8 @@ constexpr int kMaxEntries = FP_LABEL_MAX_ENTRIES;      // most table entries per
 struct LabelSample {        // fp_label_sample
   int64_t offset;           // of the map's first byte in the packed source buffer, a multiple of 8; dense [h][w] of `dtype`
   int32_t h, w;
-  int32_t dtype;            // FP_LABEL_U8 / F16 / F32 / F64
-  int32_t method;           // FP_LABEL_ZERO / NEAREST / AREA
+  int32_t dtype;            // FP_LABEL_U8 / F16 / F32 / F64 / U16
+  int32_t method;           // FP_LABEL_ZERO / NEAREST / AREA / PIL_NEAREST
   int32_t flip;             // read the source mirrored and store mirrored: cv2.resize(np.fliplr(m)) once fp_assemble_labels has flipped
   int32_t table_x, table_y; // (w -> W) and (h -> H) area tables; read only on INTER_AREA's general path
   int32_t pad;
@@ -63,11 +71,20 @@ __device__ __forceinline__ double load_elem(const unsigned char* base, int dtype
     case FP_LABEL_U8: return load_as_double<unsigned char>(base, i);
     case FP_LABEL_F16: return load_as_double<_Float16>(base, i);
     case FP_LABEL_F32: return load_as_double<float>(base, i);
+    case FP_LABEL_U16: return load_as_double<unsigned short>(base, i);
     default: return load_as_double<double>(base, i);
   }
 }
 
-__device__ __forceinline__ int elem_bytes(int dtype) { return dtype == FP_LABEL_U8 ? 1 : dtype == FP_LABEL_F16 ? 2 : dtype == FP_LABEL_F32 ? 4 : 8; }
+__device__ __forceinline__ int elem_bytes(int dtype) {
+  return dtype == FP_LABEL_U8 ? 1 : dtype == FP_LABEL_F16 || dtype == FP_LABEL_U16 ? 2 : dtype == FP_LABEL_F32 ? 4 : 8;
+}
+
+// Pillow's NEAREST source index of output index d: floor((d + 0.5) * in / out), clamped
+__device__ __forceinline__ int pil_nearest(int d, int in_size, int out_size) {
+  const int64_t s = ((int64_t)(2 * d + 1) * in_size) / ((int64_t)2 * out_size);
+  return (int)(s < in_size - 1 ? s : in_size - 1);
+}
 
 __device__ __forceinline__ bool table_ok(const Args& a, int t, int in_size, int out_size) {
   if (t < 0 || t >= a.n_tables) return false;
@@ -99,9 +116,10 @@ __global__ void __launch_bounds__(256) label_resize_kernel(const Args a) {
   const LabelSample r = a.samples[blockIdx.y];             // uniform address: scalar loads, the record lives in SGPRs
   const int H = a.H, W = a.W;
   const bool zero = r.method == FP_LABEL_ZERO;
-  bool ok = r.method == FP_LABEL_ZERO || r.method == FP_LABEL_NEAREST || r.method == FP_LABEL_AREA;
+  const bool pil = r.method == FP_LABEL_PIL_NEAREST;
+  bool ok = r.method == FP_LABEL_ZERO || r.method == FP_LABEL_NEAREST || r.method == FP_LABEL_AREA || pil;
   if (ok && !zero) {
-    ok = r.h > 0 && r.w > 0 && r.dtype >= FP_LABEL_U8 && r.dtype <= FP_LABEL_F64 && r.offset >= 0 && (r.offset & 7) == 0 &&
+    ok = r.h > 0 && r.w > 0 && r.dtype >= FP_LABEL_U8 && r.dtype <= FP_LABEL_U16 && r.offset >= 0 && (r.offset & 7) == 0 &&
          r.offset + (int64_t)r.h * r.w * elem_bytes(r.dtype) <= a.src_bytes;
   }
   // cv2::resize: inv_scale = dsize / ssize in double, scale = 1 / inv_scale
@@ -109,7 +127,7 @@ __global__ void __launch_bounds__(256) label_resize_kernel(const Args a) {
   double scale_x = 1.0, scale_y = 1.0;
   int ix = 1, iy = 1;
   bool fast = false;
-  if (ok && !zero && !same) {
+  if (ok && !zero && !same && !pil) {
     scale_x = __ddiv_rn(1.0, __ddiv_rn((double)W, (double)r.w));
     scale_y = __ddiv_rn(1.0, __ddiv_rn((double)H, (double)r.h));
     if (r.method == FP_LABEL_AREA) {
@@ -141,7 +159,10 @@ __global__ void __launch_bounds__(256) label_resize_kernel(const Args a) {
   const int w = r.w, dt = r.dtype;
   const int mirror = r.flip ? w - 1 : 0, step = r.flip ? -1 : 1;       // source column of the flipped map: mirror + step * sx
   double v;
-  if (same) {                                                             // cv2's early copyTo
+  if (pil) {                                                              // Image.resize(NEAREST); flipped AFTER the resize (see the top)
+    const int c = r.flip ? W - 1 - dx : dx;                               // the column this thread stores
+    v = load_elem(src, dt, (size_t)pil_nearest(dy, r.h, H) * w + pil_nearest(c, w, W));
+  } else if (same) {                                                             // cv2's early copyTo
     v = load_elem(src, dt, (size_t)dy * w + mirror + step * dx);
   } else if (r.method == FP_LABEL_NEAREST) {                              // resizeNN
     const int sx = min((int)floor(__dmul_rn((double)dx, scale_x)), w - 1);

@@ -18,7 +18,12 @@ Every user goes through the stage, with or without device decoding: the two pipe
 predict_simple, which calls queue and finish back to back.  A pipeline that decodes on the device calls queue(k + 1) before finish(k) and
 queues the rest of batch k after it, so the only device wait of the calling thread is for decode work queued a whole network pass
 earlier; with every status 0 the host decodes nothing.  Counters: `device` (decoded by the
-device), `host_parser` (refused by the parser), `host_status` (decoded again after a non-zero status)."""
+device), `host_parser` (refused by the parser), `host_status` (decoded again after a non-zero status).
+
+The trainer's loaders (datasets/device_path.py, --device_decode) run the same protocol with the halves of `queue` apart, because their
+host half and their device half live on two threads: fill + pack_into on the staging thread -- pack_into writes the scans, records and
+table blocks into pinned buffers of the SLOT, which grow when a batch needs more, so that a warmed-up ring allocates no pinned memory per
+training step -- queue_packed on the thread that launches, finish when the batch is collected."""
 import ctypes as C
 import io
 import time
@@ -74,10 +79,11 @@ def _decode_named(decode, data, path):
 
 class DecodeStage:
 
-    def __init__(self, batch_size, H, W, tables, device, decode=host_decode, stop=None):
+    def __init__(self, batch_size, H, W, tables, device, decode=host_decode, stop=None, max_hw=None):
         """tables: the device's ops.resize_table_set; decode: bytes -> uint8 [h, w, 3] (Pillow; tests inject a recording one); stop: a
-        threading.Event the wait in `finish` looks at"""
+        threading.Event the wait in `finish` looks at; max_hw: the largest frame (h, w) the layout accepts (None: any that fits a row)"""
         self.batch_size, self.H, self.W = int(batch_size), int(H), int(W)
+        self.max_hw = None if max_hw is None else (int(max_hw[0]), int(max_hw[1]))
         self.tables, self.device, self.decode, self.stop = tables, device, decode, stop
         self.counters = dict(device=0, host_parser=0, host_status=0)
 
@@ -124,6 +130,8 @@ class DecodeStage:
             if shapes[-1][1] * 3 > MAX_ROW_BYTES:
                 raise ValueError("%s: a frame of %d columns is wider than the resize's row buffer (%d bytes)"
                                  % (smp.get("path", "a sample"), shapes[-1][1], MAX_ROW_BYTES))
+            if self.max_hw is not None and (shapes[-1][0] > self.max_hw[0] or shapes[-1][1] > self.max_hw[1]):
+                raise ValueError("%s: a frame of %d x %d is larger than max_src_hw = %r" % (smp.get("path", "a sample"), *shapes[-1], self.max_hw))
         offsets, at = [], 0
         for h, w in shapes:
             offsets.append(at)
@@ -152,25 +160,50 @@ class DecodeStage:
                           on_host=on_host, on_device=on_device)
         return s["batch"]
 
-    def pack(self, batch):
-        """ops.jpeg_decode_pack of the batch's device samples, every array in pinned memory, or None"""
+    PACK_ARRAYS = (("scans", np.uint8, torch.uint8), ("records", np.uint8, torch.uint8), ("tables", np.int32, torch.int32))
+
+    def _pack_arrays(self, batch):
+        """ops.jpeg_decode_pack of the batch's device samples, or None"""
         idx = batch["on_device"]
         if not idx:
             return None
         smp = batch["samples"]
-        pack = ops.jpeg_decode_pack([smp[b]["bytes"] for b in idx], [smp[b]["info"] for b in idx],
-                                    out_offsets=[batch["offsets"][b] for b in idx])
-        for key, np_type, dtype in (("scans", np.uint8, torch.uint8), ("records", np.uint8, torch.uint8), ("tables", np.int32, torch.int32)):
+        return ops.jpeg_decode_pack([smp[b]["bytes"] for b in idx], [smp[b]["info"] for b in idx], out_offsets=[batch["offsets"][b] for b in idx])
+
+    def pack(self, batch):
+        """ops.jpeg_decode_pack of the batch's device samples, every array in pinned memory, or None"""
+        pack = self._pack_arrays(batch)
+        if pack is None:
+            return None
+        for key, np_type, dtype in self.PACK_ARRAYS:
             host = self._pinned(pack[key].size, dtype)
             host.numpy()[:] = pack[key].view(np_type)
             pack[key] = host
+        return pack
+
+    def pack_into(self, s, batch):
+        """`pack` into pinned buffers that belong to the slot (h_scans, h_records, h_tables; made on first use, replaced by larger ones when
+        a batch needs more: the slot's previous uploads have landed when it is filled again) -> the pack (kept in s['pack']), or None"""
+        pack = self._pack_arrays(batch)
+        if pack is not None:
+            for key, np_type, dtype in self.PACK_ARRAYS:
+                n = pack[key].size
+                host = s.get("h_" + key)
+                if host is None or host.numel() < n:
+                    host = s["h_" + key] = self._pinned(n + n // 4, dtype)
+                host.numpy()[:n] = pack[key].view(np_type)
+                pack[key] = host[:n]
+        s["pack"] = pack
         return pack
 
     # ---- device half --------------------------------------------------------------------------------------------------------------------
     def queue(self, s, samples):
         """queue a batch's uploads and its decode on the current stream; waits for nothing"""
         batch = self.fill(s, samples)
-        pack = self.pack(batch)
+        self.queue_packed(s, batch, self.pack(batch))
+
+    def queue_packed(self, s, batch, pack):
+        """the device half of `queue`, for a batch that `fill` laid out and `pack` / `pack_into` packed"""
         self._upload_records(s)
         if pack is None:                                    # the host decoded every frame: they lie dense from 0, one copy
             self._upload(s, 0, batch["total"])
@@ -180,6 +213,24 @@ class DecodeStage:
             self._upload(s, batch["offsets"][b], h * w * 3)
         self._decode(s, pack, batch)
         s["decoded"].record()
+
+    # ---- the same, in the three pieces a training loader calls (host half on its staging thread, device half on the launching one) ---------
+    def prepare(self, s, samples):
+        """fill + pack_into -> the batch's description"""
+        batch = self.fill(s, samples)
+        self.pack_into(s, batch)
+        return batch
+
+    def launch(self, s):
+        """queue_packed of what `prepare` left in the slot"""
+        self.queue_packed(s, s["batch"], s["pack"])
+
+    def collect(self, s, again):
+        """finish; when a frame had to be decoded by the host, `again()` queues the work that read the packed buffer once more -> finish's dict"""
+        done = self.finish(s)
+        if any(st > 0 for st in done["status"]):
+            again()
+        return done
 
     def _upload_records(self, s):
         s["d_rec"].copy_(s["h_rec"], non_blocking=True)

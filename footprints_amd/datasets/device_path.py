@@ -16,6 +16,18 @@ run in one launch in front of the filter (csrc/label_resize.hip).  No cv2 was at
 restatement of OpenCV's algorithm (tests/label_resize_restatement.py), which is anchored on the exact area average; INTER_AREA is built
 for shrinking or equal sizes only -- where it would enlarge an axis cv2 switches to a linear kernel, and the pack refuses the map.
 
+With `device_decode=True` (needs raw_images; --device_decode) a sample's image may also be the FILE: what decode_stage.read_sample returns,
+{'path', 'bytes', 'info'}.  Such frames are decoded by ops.jpeg_decode_packed straight into the slot's packed source buffer, at the
+offsets and with the records ops.resize_pack would have written (the sizes come from the headers); frames that arrive decoded are copied
+into the pinned buffer at their offsets and uploaded alone.  Layout, pack, status copy and fallback are decode_stage.DecodeStage's, the
+one owner of that protocol.  Everything is launched optimistically on the assembler's own stream, and the decoder's status is looked at
+only when the batch is collected -- DeviceLoader queues the NEXT batch's decode first, so a whole training step has been queued behind
+the decode whose status the host then reads, and the host does not wait for it in practice.  A frame whose status is not 0 (guarded, not
+settled, corrupt) is decoded by Pillow then and uploaded to its offset, and the slot's resize and image assembly are queued once more
+before the batch is handed over; both may run twice on a slot (they write every byte of their outputs from their inputs, and
+fp_assemble_images clears `sums` itself).  Matterport's depth_raw may then be the uint16 PNG array at its native size, resized on the
+device with Pillow's NEAREST rule.
+
 Random decisions stay on the host and consume Python's `random` exactly like the reference does (flip draw, colour-aug draw, then
 torchvision 0.4.2's ColorJitter.get_params: four uniforms in the order brightness, contrast, saturation, hue and one shuffle), so a
 seeded run makes the same decisions as the reference pipeline.  Byte arithmetic is bit-exact with Pillow 12 (tests).
@@ -33,7 +45,8 @@ JITTER_RANGES = ((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.1, 0.1))          # foo
 MAP_KEYS = {"kitti": ("visible_ground", "ground_depth", "depth_mask", "disparity", "moving_objects"),
             "matterport": ("visible_ground", "ground_depth", "depth_mask", "depth_raw")}
 # cv2.resize's interpolation per map in the reference (kitti_dataset.py:67-105, matterport_dataset.py:57-82); Matterport's raw depth arrives
-# at the target size (Pillow's NEAREST on the reader thread) and is copied
+# at the target size (Pillow's NEAREST on the reader thread) and is copied -- or, under device_decode, as the PNG's uint16 array at its native
+# size, which goes through 'pil_nearest' instead
 MAP_METHODS = {"visible_ground": "area", "ground_depth": "area", "depth_mask": "nearest", "disparity": "area", "moving_objects": "nearest",
                "depth_raw": "nearest"}
 OUT_KEYS = ("visible_ground", "depth", "ground_depth", "moving_object_mask", "depth_mask", "all_ground")
@@ -90,6 +103,13 @@ class SlotAssembler:
         self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
         self.slots = []
         self._next = 0
+
+    def use_stream(self, stream):
+        """move the copies and kernels to `stream` -- an engine stream that did not exist yet when the assembler was built (main.py builds
+        the loaders before the model) -- before the first launch only"""
+        if any(s["launched"] for s in self.slots):
+            raise RuntimeError("SlotAssembler.use_stream: a slot has been launched on the old stream already")
+        self.stream = stream
 
     def _add_slot(self, **buffers):
         self.slots.append(dict(buffers, ready=torch.cuda.Event(), consumed=None, launched=False))
@@ -153,14 +173,22 @@ class DeviceBatchAssembler(SlotAssembler):
     the arrays as loaded -- any h <= max_map_hw[0] and w <= max_map_hw[1], uint8 / bool / float16 / float32 / float64 (anything else is
     converted to float64 first), None for a missing depth mask -- and are resized on the device with cv2's INTER_AREA / INTER_NEAREST per
     MAP_METHODS; every other map must be present (a KeyError names a missing one).  max_map_itemsize (8 = float64 maps) is the stored
-    element the staging buffers are sized for at the start; a batch that needs more makes its slot's buffers grow."""
+    element the staging buffers are sized for at the start; a batch that needs more makes its slot's buffers grow.
+
+    device_decode=True (needs raw_images): the image of a sample may be a file as decode_stage.read_sample(path, True) returns it (or a
+    decoded frame, as before); see the top of this file.  This is shape 2 of the two ways to keep the training thread from waiting for a
+    decode: everything is launched optimistically and `collect` looks at the status, one DeviceLoader iteration after the decode was
+    queued, so no slot is added.  decode: bytes -> uint8 [h, w, 3] for frames the device turns down (Pillow by default).  `counters`
+    has the decode stage's three."""
 
     def __init__(self, batch_size, height, width, dataset="kitti", map_dtype=np.float64, slots=3, no_depth_mask=False,
                  project_down_baseline=False, moving_objects_method="ours", footprint_threshold=0.75, baseline=0.54,
                  depth_scaling=0.25e-3, device="cuda", stream=None, raw_images=False, max_src_hw=None, filter_depth_mask=False,
-                 raw_maps=False, max_map_hw=None, max_map_itemsize=8, check=False):
+                 raw_maps=False, max_map_hw=None, max_map_itemsize=8, check=False, device_decode=False, decode=None):
         if dataset not in MAP_KEYS:
             raise ValueError("dataset must be 'kitti' or 'matterport'")
+        if device_decode and not raw_images:
+            raise ValueError("device_decode=True needs raw_images=True: the decoder writes frames at their native sizes")
         if raw_images and (max_src_hw is None or min(max_src_hw) <= 0):
             raise ValueError("raw_images=True needs max_src_hw=(largest source height, largest source width)")
         if raw_maps and (max_map_hw is None or min(max_map_hw) <= 0):
@@ -171,6 +199,7 @@ class DeviceBatchAssembler(SlotAssembler):
         self.max_map_hw = tuple(int(v) for v in max_map_hw) if raw_maps else None
         self.check = bool(check)          # read fp_label_resize's status word after every launch (this WAITS for the stream): tests, debugging
         self.max_src_hw = tuple(int(v) for v in max_src_hw) if raw_images else None
+        self.device_decode = bool(device_decode)
         _lib.load()
         assert _lib.load().fp_aug_params_bytes() == C.sizeof(AugParams)
         self.B, self.H, self.W, self.dataset = batch_size, height, width, dataset
@@ -190,6 +219,10 @@ class DeviceBatchAssembler(SlotAssembler):
         tdt = torch.float64 if self.map_dtype == np.float64 else torch.float32
         self.tables = ops.resize_table_set(self.device) if self.raw_images else None
         self.map_tables = ops.label_table_set(self.device) if self.raw_maps else None
+        self.stage = None
+        if self.device_decode:              # decode: bytes -> uint8 [h, w, 3] for the frames the device turns down (Pillow; tests inject one)
+            from .decode_stage import DecodeStage, host_decode
+            self.stage = DecodeStage(batch_size, height, width, self.tables, self.device, decode=decode or host_decode, max_hw=self.max_src_hw)
         if self.raw_maps:
             lib = _lib.load()
             assert lib.fp_label_sample_bytes() == C.sizeof(_lib.LabelSample) and lib.fp_label_table_bytes() == C.sizeof(_lib.LabelTable)
@@ -209,6 +242,10 @@ class DeviceBatchAssembler(SlotAssembler):
                 h_rec = torch.empty(batch_size * C.sizeof(_lib.ResizeSample), dtype=torch.uint8).pin_memory()
                 self.slots[-1].update(h_src=h_src, h_rec=h_rec, d_src=torch.empty_like(h_src, device=self.device),
                                       d_rec=torch.empty_like(h_rec, device=self.device), src_bytes=0)
+                if self.device_decode:      # the decode stage's part of the slot; its pinned scan / record / table buffers come with the first batch
+                    self.slots[-1].update(src_cap=h_src.numel(), h_status=torch.empty(batch_size + 1, dtype=torch.int32).pin_memory(),
+                                          d_status=torch.empty(batch_size + 1, dtype=torch.int32, device=self.device),
+                                          decoded=torch.cuda.Event(), batch=None, pack=None)
             if self.raw_maps:               # the packed native-size maps and their fp_label_sample records
                 n = len(self.keys) * batch_size
                 per_map = (self.max_map_hw[0] * self.max_map_hw[1] * int(max_map_itemsize) + 7) // 8 * 8
@@ -219,6 +256,11 @@ class DeviceBatchAssembler(SlotAssembler):
                                       status=torch.zeros(1, dtype=torch.int32, device=self.device))
         assert npx > 0
 
+    @property
+    def counters(self):
+        """DecodeStage.counters: frames decoded by the device, refused by the parser, decoded again after a non-zero status"""
+        return dict(self.stage.counters) if self.stage is not None else dict(device=0, host_parser=0, host_status=0)
+
     def fill(self, samples, params):
         """host half of staging one batch: copy the samples and augmentation draws into the next slot's pinned buffers (60 MB of numpy
         copies for a KITTI batch with float64 maps at the target size; with raw_maps the maps as stored at their native size, 78 MB for
@@ -228,7 +270,9 @@ class DeviceBatchAssembler(SlotAssembler):
             raise ValueError("expected %d samples" % self.B)
         i, s = self._take_slot()
         img_np, maps_np = s["h_img"].numpy(), s["h_maps"].numpy()
-        if self.raw_images:
+        if self.device_decode:              # files and decoded frames: the stage lays them out, refuses what is too large, packs the scans
+            s["src_bytes"] = self.stage.prepare(s, [img if isinstance(img, dict) else {"image": img} for img, _ in samples])["total"]
+        elif self.raw_images:
             images = [img for img, _ in samples]
             if any(im.ndim != 3 or im.shape[2] != 3 or im.shape[0] > self.max_src_hw[0] or im.shape[1] > self.max_src_hw[1] for im in images):
                 raise ValueError("raw images must be uint8 [h, w, 3] within max_src_hw = %r" % (self.max_src_hw,))
@@ -249,7 +293,8 @@ class DeviceBatchAssembler(SlotAssembler):
                     if m is None and key not in ("depth_mask", "moving_objects"):
                         raise ValueError("the map %r of a sample is None: only depth_mask (and moving_objects) may be missing" % key)
                     raw.append(m)
-                    methods.append("zero" if m is None else MAP_METHODS[key])
+                    pil = key == "depth_raw" and self.device_decode and getattr(m, "dtype", None) == np.uint16     # the PNG as stored
+                    methods.append("zero" if m is None else "pil_nearest" if pil else MAP_METHODS[key])
                     flips.append(bool(p.flip))
                     mults.append(self.W / m.shape[1] if key == "disparity" and m is not None else 1.0)     # footprint_dataset.py:92
             need = ops.label_pack_bytes(raw)
@@ -263,13 +308,36 @@ class DeviceBatchAssembler(SlotAssembler):
         s["h_par"].numpy()[:] = np.frombuffer(bytes(arr), dtype=np.uint8)
         return i
 
+    def _resize_frames(self, s):
+        ops.resize_u8_packed(s["d_src"], s["src_bytes"], s["d_rec"], self.B, self.H, self.W, 3, self.max_src_hw[0], self.max_src_hw[1], self.tables,
+                             out=s["d_img"])
+
+    def _assemble_images(self, s):
+        _lib.check(_lib.load().fp_assemble_images(s["d_img"].data_ptr(), s["d_par"].data_ptr(), s["sums"].data_ptr(), s["image"].data_ptr(),
+                                                  self.B, self.H, self.W, ops.stream()), "fp_assemble_images")
+
+    def collect(self, slot):
+        s = self.slots[slot]
+        if self.device_decode and s["batch"] is not None:
+            # the decode was queued a whole step ago (DeviceLoader): its status is there.  What the device turned down goes through Pillow
+            # now, and the image half of the slot's chain runs again on the repaired source buffer; the label half never read it
+            def again():
+                self._resize_frames(s)
+                self._assemble_images(s)
+                s["ready"].record(self.stream)
+            with ops.on_stream(self.stream):
+                self.stage.collect(s, again)
+        return super().collect(slot)
+
     def _launch(self, s):
-        if self.raw_images:                 # Image.resize first, like the reference (footprint_dataset.py:77), straight into d_img
+        if self.device_decode:              # uploads of the records, the host frames and the scans, the decode into d_src, the status copy
+            self.stage.launch(s)
+            self._resize_frames(s)
+        elif self.raw_images:               # Image.resize first, like the reference (footprint_dataset.py:77), straight into d_img
             n = s["src_bytes"]
             s["d_src"][:n].copy_(s["h_src"][:n], non_blocking=True)
             s["d_rec"].copy_(s["h_rec"], non_blocking=True)
-            ops.resize_u8_packed(s["d_src"], n, s["d_rec"], self.B, self.H, self.W, 3, self.max_src_hw[0], self.max_src_hw[1], self.tables,
-                                 out=s["d_img"])
+            self._resize_frames(s)
         else:
             s["d_img"].copy_(s["h_img"], non_blocking=True)
         if self.raw_maps:                   # cv2.resize of every map, straight into d_maps
@@ -285,8 +353,7 @@ class DeviceBatchAssembler(SlotAssembler):
             ops.filter_depth_mask(s["d_maps"][2], out=s["d_maps"][2])
         lib = _lib.load()
         st = ops.stream()
-        _lib.check(lib.fp_assemble_images(s["d_img"].data_ptr(), s["d_par"].data_ptr(), s["sums"].data_ptr(), s["image"].data_ptr(),
-                                          self.B, self.H, self.W, st), "fp_assemble_images")
+        self._assemble_images(s)
         m, o = s["d_maps"], s["out"]
         kitti = self.dataset == "kitti"
         _lib.check(lib.fp_assemble_labels(m[0].data_ptr(), m[1].data_ptr(), m[2].data_ptr(), m[3].data_ptr(),
@@ -313,6 +380,11 @@ class DeviceLoader:
     def __init__(self, source, assembler, is_train=True, rng=random, draw=None):
         self.source, self.asm, self.is_train, self.rng = source, assembler, is_train, rng
         self.draw = draw if draw is not None else (lambda samples, is_train, rng: [draw_augmentation(is_train, rng) for _ in samples])
+
+    @property
+    def counters(self):
+        """the assembler's decode counters (device, host_parser, host_status); zeros without device_decode"""
+        return getattr(self.asm, "counters", None) or dict(device=0, host_parser=0, host_status=0)
 
     def __len__(self):
         return len(self.source)
@@ -343,11 +415,18 @@ class DeviceLoader:
                 return
             self.asm.launch(pending)
             fut = ex.submit(fill_next)
+            # an assembler that decodes on the device reads the decoder's status in collect: the next batch's decode is queued in front of
+            # that, so that batch `pending`'s decode has a whole step of queued work behind it when the host looks at its status
+            launch_first = bool(getattr(self.asm, "device_decode", False))
             while True:
-                batch = self.asm.collect(pending)
+                if not launch_first:
+                    batch = self.asm.collect(pending)
                 nxt = fut.result()
                 if nxt is not None:
                     self.asm.launch(nxt)                  # the OTHER slot: copied and assembled while the consumer works on `pending`
+                if launch_first:
+                    batch = self.asm.collect(pending)
+                if nxt is not None:
                     fut = ex.submit(fill_next)
                 yield batch
                 self.asm.release(pending)                 # the step that used it has been queued: its completion frees the slot

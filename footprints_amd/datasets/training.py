@@ -11,7 +11,14 @@ INTER_NEAREST resizes of the maps, filter_depth_mask, flip, colour jitter and th
 `.convert("RGB")`; every reader of this package converts, and so does this one.
 
 One exception: Matterport's 16-bit depth PNG keeps Pillow's `resize(NEAREST)` on the reader thread and is handed over at the target size
-as float32 (exact for 16 bits) -- no device entry point takes 16-bit sources.
+as float32 (exact for 16 bits).
+
+device_decode=True (--device_decode) takes the remaining pixel work off the reader threads.  The image of a sample is then what
+decode_stage.read_sample(path, True) returns: {'path', 'bytes', 'info'} -- the file's bytes and its parsed header -- for a baseline JPEG,
+which the assembler decodes on the device (csrc/jpeg_decode.hip, byte-equal to Pillow), or {'path', 'image', 'refused'} for a file the
+parser refuses (progressive, restart markers, CMYK, PNG, ...), which Pillow decodes at once on that thread.  Matterport's depth PNG is
+handed over as the uint16 array at its native size and resized on the device (fp_label_resize: FP_LABEL_U16, FP_LABEL_PIL_NEAREST).  A
+reader thread then reads files, parses headers and decodes PNG, and does no other pixel work.
 
 ThreadedBatchSource is BatchSource (the segmentation trainer's shuffled sample lists, with its `shard(rank, world)`) reading the samples of
 upcoming batches on a pool of threads: one thread cannot decode 12 JPEGs and load 60 .npy files inside one training step."""
@@ -46,11 +53,19 @@ class TrainingReader:
     dataset = None
 
     def __init__(self, raw_data_path, training_data_path, filenames, height, width, no_depth_mask=False, moving_objects_method="ours",
-                 project_down_baseline=False, is_train=False, **kwargs):
+                 project_down_baseline=False, is_train=False, device_decode=False, **kwargs):
         self.raw_data_path, self.training_data_path = raw_data_path, training_data_path
         self.filenames = list(filenames)
         self.height, self.width, self.is_train = height, width, is_train
         self.no_depth_mask, self.moving_objects_method, self.project_down_baseline = no_depth_mask, moving_objects_method, project_down_baseline
+        self.device_decode = bool(device_decode)
+
+    def image(self, path):
+        """the decoded frame, or under device_decode what decode_stage.read_sample returns"""
+        if self.device_decode:
+            from .decode_stage import read_sample
+            return read_sample(path, True)
+        return pil_loader(path)
 
     def __len__(self):
         return len(self.filenames)
@@ -89,7 +104,7 @@ class KITTIReader(TrainingReader):
         maps = {"visible_ground": load_npy(p["visible_ground"]), "ground_depth": load_npy(p["ground_depth"]),
                 "depth_mask": load_optional_npy(p["depth_mask"]), "disparity": load_npy(p["disparity"]),
                 "moving_objects": load_npy(p["moving_objects"]) if self.moving_objects_method == "ours" else None}
-        return pil_loader(p["image"]), maps
+        return self.image(p["image"]), maps
 
 
 class MatterportReader(TrainingReader):
@@ -109,11 +124,14 @@ class MatterportReader(TrainingReader):
     def __getitem__(self, index):
         from PIL import Image
         p = self.paths(index)
-        with Image.open(p["depth_raw"]) as im:                         # the 16-bit PNG: Pillow's NEAREST, on this thread
-            depth = np.array(im.resize((self.width, self.height), Image.NEAREST))
+        with Image.open(p["depth_raw"]) as im:
+            if self.device_decode:                                     # the 16-bit PNG as stored: the device resizes it
+                depth = np.asarray(im)
+            else:                                                      # Pillow's NEAREST, on this thread
+                depth = np.array(im.resize((self.width, self.height), Image.NEAREST)).astype(np.float32)
         maps = {"visible_ground": load_npy(p["visible_ground"]), "ground_depth": load_npy(p["ground_depth"]),
-                "depth_mask": load_optional_npy(p["depth_mask"]), "depth_raw": depth.astype(np.float32)}
-        return pil_loader(p["image"]), maps
+                "depth_mask": load_optional_npy(p["depth_mask"]), "depth_raw": depth}
+        return self.image(p["image"]), maps
 
 
 def get_dataset_class(name):
@@ -164,14 +182,14 @@ class ThreadedBatchSource(BatchSource):
                         f.cancel()
 
 
-def create_dataloaders(opt, stream=None, max_src_hw=None, max_map_hw=None, max_map_itemsize=4):
+def create_dataloaders(opt, stream=None, max_src_hw=None, max_map_hw=None, max_map_itemsize=4, device_decode=False):
     """TrainManager.create_dataloaders of the reference (training/train.py:99-134) over the device path: the config file's
     [training_dataset]['dataset' | 'training_data'], splits/<dataset>/{train,val}.txt relative to the working directory, the options
     no_depth_mask, moving_objects_method and project_down_baseline handed on, val with is_train=False; both shuffled, as the reference's
     DataLoaders are -> (train DeviceLoader, val DeviceLoader).  Under a data-parallel launch TrainManager shards the train loader's source.
     No file is read here.  max_src_hw / max_map_hw: the largest frame / label map (a larger one is refused by name when its batch is
     filled); max_map_itemsize: the stored element the map staging buffers start with (4: float32 maps) -- a batch of wider maps makes them
-    grow once."""
+    grow once.  device_decode: both readers hand over file bytes and both assemblers decode them on the device (see the top)."""
     import random
     import yaml
     from .device_path import DeviceBatchAssembler, DeviceLoader
@@ -187,12 +205,13 @@ def create_dataloaders(opt, stream=None, max_src_hw=None, max_map_hw=None, max_m
         with open(os.path.join("splits", dataset, split + ".txt")) as fh:
             files = fh.read().splitlines()
         reader = dataset_class(raw_data_path, training_data_path, files, opt.height, opt.width, no_depth_mask=opt.no_depth_mask,
-                               moving_objects_method=opt.moving_objects_method, project_down_baseline=opt.project_down_baseline, is_train=is_train)
+                               moving_objects_method=opt.moving_objects_method, project_down_baseline=opt.project_down_baseline, is_train=is_train,
+                               device_decode=device_decode)
         source = ThreadedBatchSource([reader], opt.batch_size, shuffle=True, rng=random, num_workers=workers)
         asm = DeviceBatchAssembler(opt.batch_size, opt.height, opt.width, dataset=dataset, slots=slots, no_depth_mask=opt.no_depth_mask,
                                    project_down_baseline=opt.project_down_baseline, moving_objects_method=opt.moving_objects_method,
                                    stream=stream, raw_images=True, max_src_hw=max_src_hw, filter_depth_mask=True, raw_maps=True,
-                                   max_map_hw=max_map_hw, max_map_itemsize=max_map_itemsize)
+                                   max_map_hw=max_map_hw, max_map_itemsize=max_map_itemsize, device_decode=device_decode)
         loader = DeviceLoader(source, asm, is_train=is_train, rng=random)
         loader.dataset = source.dataset
         loaders.append(loader)

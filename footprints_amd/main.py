@@ -50,7 +50,7 @@ def main(argv=None, model_manager=None):
         if opt.synthetic_steps <= 0:
             # the reference's create_dataloaders over the device path; under a data-parallel launch TrainManager shards the train source
             from .datasets.training import create_dataloaders
-            train, val = create_dataloaders(opt)
+            train, val = create_dataloaders(opt, device_decode=getattr(opt, "device_decode", False))
             return TrainManager(opt, train_loader=train, val_loader=val, dist_context=ctx, summaries=summaries).train()
         if opt.device_augment and opt.training_dataset == "kitti":
             # row N3: host samples as the file readers deliver them -> pinned double-buffered H2D -> flip / jitter / label kernels

@@ -1286,8 +1286,26 @@ def filter_depth_mask(mask, out=None):
 
 
 # ---- reader work on the device: the cv2 resizes of the label maps (csrc/label_resize.hip) ------------------------------------------------
-LABEL_METHODS = {"zero": _lib.LABEL_ZERO, "nearest": _lib.LABEL_NEAREST, "area": _lib.LABEL_AREA}
+LABEL_METHODS = {"zero": _lib.LABEL_ZERO, "nearest": _lib.LABEL_NEAREST, "area": _lib.LABEL_AREA, "pil_nearest": _lib.LABEL_PIL_NEAREST}
 _area_host_tables = {}
+_pil_nearest_axes = {}
+
+
+def pil_nearest_axis(in_size, out_size):
+    """the kernel's closed form of Pillow's NEAREST for one axis, min(floor((d + 0.5) * in / out), in - 1) -> int32 [out_size].  Pillow adds
+    the step up in double (nearest_index restates that); where the two disagree -- a sum that lands a rounding error beside an integer --
+    the axis is refused rather than resized almost like Pillow."""
+    import numpy as np
+    key = (int(in_size), int(out_size))
+    idx = _pil_nearest_axes.get(key)
+    if idx is None:
+        d = np.arange(key[1], dtype=np.int64)
+        idx = np.minimum((2 * d + 1) * key[0] // (2 * key[1]), key[0] - 1).astype(np.int32)
+        if not np.array_equal(idx, nearest_index(*key)):
+            raise ValueError("footprints_amd.ops.pil_nearest_axis: %d -> %d: Pillow's accumulated coordinate leaves the closed form" % key)
+        idx.setflags(write=False)
+        _pil_nearest_axes[key] = idx
+    return idx
 
 
 def area_table(in_size, out_size):
@@ -1358,7 +1376,7 @@ def _label_source(m):
     if m.dtype == np.bool_:
         m = m.view(np.uint8)
     code = {np.dtype(np.uint8): _lib.LABEL_U8, np.dtype(np.float16): _lib.LABEL_F16, np.dtype(np.float32): _lib.LABEL_F32,
-            np.dtype(np.float64): _lib.LABEL_F64}.get(m.dtype)
+            np.dtype(np.float64): _lib.LABEL_F64, np.dtype(np.uint16): _lib.LABEL_U16}.get(m.dtype)
     if code is None:
         m, code = m.astype(np.float64), _lib.LABEL_F64
     return m, code
@@ -1368,7 +1386,7 @@ def label_source_itemsize(m):
     """bytes per element a map takes in the packed source buffer"""
     import numpy as np
     dt = np.asarray(m).dtype
-    return dt.itemsize if dt in (np.dtype(np.bool_), np.dtype(np.uint8), np.dtype(np.float16), np.dtype(np.float32)) else 8
+    return dt.itemsize if dt in (np.dtype(np.bool_), np.dtype(np.uint8), np.dtype(np.float16), np.dtype(np.float32), np.dtype(np.uint16)) else 8
 
 
 def label_pack_bytes(maps):
@@ -1396,8 +1414,8 @@ def label_area_fast(h, w, H, W):
 def label_resize_pack(maps, H, W, method, flip=False, multiplier=1.0, tables=None, packed=None, records=None, max_map_hw=None):
     """host half of fp_label_resize: the maps ([h, w] arrays in the dtype the .npy holds; None = a map of zeros) one after the other at
     8-byte-aligned offsets of `packed` (a uint8 numpy buffer, e.g. pinned; allocated when None) and their fp_label_sample records in
-    `records` (uint8 numpy view, allocated when None).  method ('zero' / 'nearest' / 'area'), flip and multiplier: one value, or one per
-    map.  tables: the LabelTableSet of the device (label_table_set).  INTER_AREA that would enlarge an axis is refused (cv2 switches to a
+    `records` (uint8 numpy view, allocated when None).  method ('zero' / 'nearest' / 'area', or 'pil_nearest': Pillow's resize(NEAREST),
+    which is flipped after the resize, not before it), flip and multiplier: one value, or one per map.  uint16 maps are stored as they are.  tables: the LabelTableSet of the device (label_table_set).  INTER_AREA that would enlarge an axis is refused (cv2 switches to a
     linear kernel there, which is not provided), and so is a map larger than max_map_hw when that is given.
     -> (packed, records, bytes used, tables)"""
     import numpy as np
@@ -1426,6 +1444,8 @@ def label_resize_pack(maps, H, W, method, flip=False, multiplier=1.0, tables=Non
                                  "(cv2 uses a linear kernel when it enlarges)" % (j, h, w, H, W))
             if not label_area_fast(h, w, H, W):
                 tx, ty = tables.index(w, W), tables.index(h, H)
+        if meth == _lib.LABEL_PIL_NEAREST:
+            pil_nearest_axis(h, H), pil_nearest_axis(w, W)
         rec[j] = _lib.LabelSample(total, h, w, code, meth, int(bool(flips[j])), tx, ty, 0, float(mults[j]))
         srcs.append(m)
         total += (m.nbytes + 7) // 8 * 8
@@ -1471,7 +1491,9 @@ def label_resize_packed(src, src_bytes, samples, n, H, W, tables, out=None, stat
 def label_resize(maps, H, W, method, flip=False, multiplier=1.0, device="cuda"):
     """cv2.resize(m.astype(float), (W, H), interpolation=INTER_AREA | INTER_NEAREST) * multiplier of a list of maps of any (mixed) sizes
     and stored dtypes, bit for bit on float64, in one library call -> float64 device tensor [n, H, W].  With flip the result is
-    cv2.resize(np.fliplr(m)) mirrored back -- what the assembler's own flip expects."""
+    cv2.resize(np.fliplr(m)) mirrored back -- what the assembler's own flip expects.  method 'pil_nearest' is
+    Image.fromarray(m).resize((W, H), Image.NEAREST) instead (uint16 maps: mode I;16), flipped after the resize: mirrored back it is the
+    unflipped resize."""
     tables = label_table_set(device)
     assert _lib.load().fp_label_sample_bytes() == C.sizeof(_lib.LabelSample) and _lib.load().fp_label_table_bytes() == C.sizeof(_lib.LabelTable)
     packed, records, total, _ = label_resize_pack(maps, H, W, method, flip, multiplier, tables)

@@ -41,11 +41,13 @@ class Options:
         # absent from the namespace unless given, like the inference flags below
         p.add_argument("--no_summaries", action="store_true", default=argparse.SUPPRESS,
                        help="train without writing TensorBoard files under <log_path>/<model_name>/{train,val}")
-        # inference mode of this build (row N12).  Off unless given -- and absent from the namespace then (read them with getattr(opt,
-        # name, False)), so that a plain parse still yields the reference's flags and the two additions above, nothing else
+        # inference mode of this build (row N12), and with --device_decode the training readers (row N18).  Off unless given -- and absent
+        # from the namespace then (read them with getattr(opt, name, False)), so that a plain parse still yields the reference's flags and
+        # the two additions above, nothing else
         p.add_argument("--device_decode", action="store_true", default=argparse.SUPPRESS,
-                       help="inference mode: decode baseline JPEG frames on the GPU, one batch ahead of the network (same files; "
-                            "what the decoder does not take goes to Pillow)")
+                       help="decode baseline JPEG frames on the GPU (same pixels; what the decoder does not take goes to Pillow): in inference "
+                            "mode one batch ahead of the network, in train mode from a dataset folder inside the batch assembly, with "
+                            "Matterport's depth PNG resized there too (ignored with --synthetic_steps)")
         p.add_argument("--device_jpeg", action="store_true", default=argparse.SUPPRESS,
                        help="with --save_test_visualisations: encode the pictures on the GPU (same files as Pillow writes)")
 

@@ -370,6 +370,15 @@ class TrainManager:
             broadcast_state(self.model, src=0, group=self.dist.group)     # every replica starts from rank 0's weights, buffers and Adam-free state
         self.train_step = train_step if train_step is not None else TrainStep(
             self.model, self.optimiser, depth_range, self.opt.footprint_prior, distributed=self.dist.active)
+        eng = getattr(self.train_step, "eng", None)
+        if getattr(self.opt, "device_decode", False) and eng is not None:
+            # loaders that decode on the device were built before the engine and own a fifth stream, which shares a hardware queue with one
+            # of the engine's: the decoder's chain of small dependent kernels then sits in front of that stream's kernels (18.4 against
+            # 15.3 ms per step, profiles/train_reader_notes.md).  On the mask decoder's weight-gradient stream it costs the step nothing
+            for loader in (train_loader, val_loader):
+                asm = getattr(loader, "asm", None)
+                if getattr(asm, "device_decode", False):
+                    asm.use_stream(eng.dwg[0])
         self.epochs = self.opt.epochs
         self.step = 0
         self.lr = self.opt.lr
@@ -435,6 +444,13 @@ class TrainManager:
                         self.val()
                         self.model.train()
             self.step += 1
+        if getattr(self.opt, "device_decode", False):                              # where this epoch's frames were decoded, once
+            for name, loader in (("train", self.train_loader), ("val", self.val_loader)):
+                loader = getattr(loader, "loader", loader)                         # a ShardedLoader's own
+                if getattr(getattr(loader, "asm", None), "device_decode", False):    # not the synthetic loaders: they ignore the flag
+                    c = loader.counters
+                    self.log("Epoch {} -- {} frames decoded so far: device {}, host (parser) {}, host (status) {}".format(
+                        self.epoch, name, c["device"], c["host_parser"], c["host_status"]))
         # checkpoint: rank 0 only (weights are bit-identical on every rank after each step; BatchNorm running statistics are per
         # replica and rank 0's are the ones kept -- SURVEY.md section 8e); the others wait so that nobody races ahead into a load
         if self.model_manager.save_folder is not None and self.dist.is_main:

@@ -569,17 +569,20 @@ int fp_filter_depth_mask(const void* mask, int32_t is_double, void* out, int32_t
 #define FP_LABEL_F16 1
 #define FP_LABEL_F32 2
 #define FP_LABEL_F64 3
+#define FP_LABEL_U16 4 /* uint16: Matterport's depth PNG (mode I;16) */
 #define FP_LABEL_ZERO 0    /* the map is 0.0 everywhere (a missing depth mask); nothing is read */
 #define FP_LABEL_NEAREST 1 /* cv2.INTER_NEAREST */
 #define FP_LABEL_AREA 2    /* cv2.INTER_AREA, shrinking or equal on both axes; its upscaling branch (a linear kernel) is not provided */
+#define FP_LABEL_PIL_NEAREST 3 /* Pillow's Image.resize(NEAREST): src = min(floor((dst + 0.5) * in / out), in - 1) per axis, any ratio;
+                                * a flipped record is resized first and flipped then, so it reads the source unmirrored */
 #define FP_LABEL_MAX_ENTRIES 12 /* most entries of one output index in an area table that a launch stages: non-integer shrink factors up to 10 */
 /* one map of the batch; fp_label_sample_bytes() == sizeof(fp_label_sample) */
 typedef struct fp_label_sample {
   int64_t offset;  /* of its first byte in the packed source buffer, a multiple of 8; the map is dense [h][w] of `dtype` */
   int32_t h, w;
-  int32_t dtype;   /* FP_LABEL_U8 .. FP_LABEL_F64 */
-  int32_t method;  /* FP_LABEL_ZERO / NEAREST / AREA */
-  int32_t flip;    /* read the source mirrored and store mirrored */
+  int32_t dtype;   /* FP_LABEL_U8 .. FP_LABEL_U16 */
+  int32_t method;  /* FP_LABEL_ZERO / NEAREST / AREA / PIL_NEAREST */
+  int32_t flip;    /* read the source mirrored and store mirrored (PIL_NEAREST: read unmirrored, store mirrored) */
   int32_t table_x; /* index of its (w -> W) area table; read only on INTER_AREA's general path */
   int32_t table_y; /* index of its (h -> H) area table */
   int32_t pad;
@@ -612,7 +615,8 @@ int32_t fp_area_table(int32_t in_size, int32_t out_size, int32_t* bounds, int32_
  * DBL_EPSILON) sums the block in row-major order in double and multiplies by (double)(1.f / (float)area); AREA otherwise walks the two
  * axis tables: per y entry buf = 0.0, buf = buf + S[sy][sx] * alpha over the x entries, sum = beta * buf for the first y entry and
  * sum = sum + beta * buf after it, the float weights widened to double, no fused multiply-add.  A flipped record gives
- * cv2.resize(np.fliplr(m)) mirrored, so that the flip of fp_assemble_labels undoes the mirroring.  tables: n_tables fp_label_table records
+ * cv2.resize(np.fliplr(m)) mirrored, so that the flip of fp_assemble_labels undoes the mirroring.  PIL_NEAREST gathers
+ * S[min(((2 * y + 1) * h) / (2 * H), h - 1)][min(((2 * x + 1) * w) / (2 * W), w - 1)] in integers, flipped or not.  tables: n_tables fp_label_table records
  * over `entries` (device, entries_len 8-byte elements).  A record that points outside the packed buffer, asks AREA to enlarge, or whose
  * table does not fit its sizes leaves that map unwritten and sets *status (one int32 on the device) to 1; every call clears it first; read
  * it after the stream has finished.  max_entries: the largest max_count of the tables (0 without tables, at most FP_LABEL_MAX_ENTRIES); it

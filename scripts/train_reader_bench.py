@@ -3,6 +3,7 @@ next to the host chain it replaces, and what the file loader costs the training 
 375 x 1242.
 
     python scripts/train_reader_bench.py [--seconds 2.0] [--rounds 5] [--steps 40] [--frames 48] [--workers 8] [--map_dtype float32]
+                                         [--loader_stream own|dwg0]
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/train_reader_bench.py --only_resize      # the kernel's own time, in a run of its own
 
 Legs: the fp_label_resize CALL alone on an uploaded batch (HIP events around a loop of calls: the status word's 4-byte memset, the launch
@@ -12,7 +13,9 @@ the packed maps and records; the host pack
 which is not installed: the same arithmetic, vectorised by numpy instead of OpenCV's loops); per-stage host times of the file path (JPEG
 decode, np.load, fill) on one thread; the training step alone on a resident batch; the loader alone; and the training step with the file
 loader in the loop, on a synthetic on-disk tree this script writes (random frames and maps: JPEG entropy and .npy sizes are not KITTI's).
-Prints one JSON line."""
+The last two legs run a second time with --device_decode (the readers hand over file bytes, the assembler decodes them on the device),
+alternating with the Pillow legs inside each round, with the reader's, fill's and the decode stage's host times per batch and the
+decode counters next to them.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -98,6 +101,9 @@ def main():
     ap.add_argument("--workers", type=int, default=8, help="--num_workers of the file loader")
     ap.add_argument("--map_dtype", default="float32", choices=["float16", "float32", "float64"], help="stored dtype of the real-valued maps")
     ap.add_argument("--only_resize", action="store_true", help="the label-resize legs alone (for a kernel-trace run)")
+    ap.add_argument("--loader_stream", default="own", choices=["own", "dwg0"],
+                    help="the loaders' copy / assembly stream: one of their own (what main.py gives them) or the engine's decoder "
+                         "weight-gradient stream (what bench.py gives its assembler)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("train_reader_bench.py needs a GPU: a time measured anywhere else says nothing about it")
@@ -174,28 +180,50 @@ def main():
         files = {"jpeg_decode_per_frame": lambda: pil_loader(p["image"]),
                  "np_load_5_maps_per_frame": lambda: [load_npy(p[k]) for k in keys]}
         stage = {k: host_ms(fn, a.seconds / 4) for k, fn in files.items()}
-        train, _ = create_dataloaders(opt)
-        train.source.index = (train.source.index * -(-(a.steps + 5) * B // a.frames))[:(a.steps + 5) * B]      # cycle the tree: steps + 5 batches per pass
+        mm = ModelManager(use_cuda=True)
+        ts = TrainStep(mm.model, mm.optimiser)
+        loader_stream = ts.eng.dwg[0] if a.loader_stream == "dwg0" else None
+        train, _ = create_dataloaders(opt, stream=loader_stream)
+        train_dd, _ = create_dataloaders(opt, stream=loader_stream, device_decode=True)
+        for ld in (train, train_dd):
+            ld.source.index = (ld.source.index * -(-(a.steps + 5) * B // a.frames))[:(a.steps + 5) * B]        # cycle the tree: steps + 5 batches per pass
         batch_samples = [reader[i] for i in range(B)]
         from footprints_amd.datasets import draw_augmentation
         prm = [draw_augmentation(True, random.Random(3)) for _ in range(B)]
         stage["fill_per_batch_one_thread"] = host_ms(lambda: train.asm.fill(batch_samples, prm), a.seconds / 4)
-        mm = ModelManager(use_cuda=True)
-        ts = TrainStep(mm.model, mm.optimiser)
+        # the same three under --device_decode: a reader thread's work per frame (file bytes + header), fill, and inside fill the decode
+        # stage's host half (layout, records, scans and table blocks into the slot's pinned buffers)
+        reader_dd = KITTIReader(os.path.join(root, "raw"), os.path.join(root, "training_data"), lines, H, W, device_decode=True)
+        samples_dd = [reader_dd[i] for i in range(B)]
+        stage["device_decode_read_and_parse_per_frame"] = host_ms(lambda: reader_dd.image(p["image"]), a.seconds / 4)
+        stage["device_decode_fill_per_batch_one_thread"] = host_ms(lambda: train_dd.asm.fill(samples_dd, prm), a.seconds / 4)
+        frames_dd = [smp for smp, _ in samples_dd]
+        stage["device_decode_host_half_per_batch"] = host_ms(lambda: train_dd.asm.stage.prepare(train_dd.asm.slots[0], frames_dd), a.seconds / 4)
+        train_dd.asm.slots[0]["batch"] = None
+        finish, waited = train_dd.asm.stage.finish, []
+
+        def timed_finish(s):                                            # the launching thread's time inside the status check of a batch
+            t0 = time.perf_counter()
+            try:
+                return finish(s)
+            finally:
+                waited.append((time.perf_counter() - t0) * 1e3)
+        train_dd.asm.stage.finish = timed_finish
         resident = {k: v.clone() for k, v in train.asm.collect(train.asm.submit(batch_samples, prm)).items()}
         for _ in range(5):
             ts(resident)
         torch.cuda.synchronize()
-        alone, looped, loader_only = [], [], []
-        for _ in range(max(a.rounds // 2, 2)):                         # the three loops alternate
+        alone, looped, loader_only, looped_dd, loader_only_dd = [], [], [], [], []
+        for _ in range(max(a.rounds // 2, 2)):                         # the five loops alternate
             t0 = time.perf_counter()
             for _ in range(a.steps):
                 ts(resident)
             torch.cuda.synchronize()
             alone.append((time.perf_counter() - t0) * 1e3 / a.steps)
-            for sink, use in ((looped, ts), (loader_only, lambda bt: None)):
+            for sink, use, loader in ((looped, ts, train), (looped_dd, ts, train_dd), (loader_only, lambda bt: None, train),
+                                      (loader_only_dd, lambda bt: None, train_dd)):
                 k, t0 = 0, None
-                for bt in train:
+                for bt in loader:
                     if k == 5:                                          # the loader's first batches fill the pipeline
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
@@ -203,11 +231,19 @@ def main():
                     k += 1
                 torch.cuda.synchronize()
                 sink.append((time.perf_counter() - t0) * 1e3 / (k - 5))
-        stage.update(train_step_alone=float(np.median(alone)), train_step_with_file_loader=float(np.median(looped)),
-                     file_loader_alone=float(np.median(loader_only)))
-        out["file_loader"] = {"frames_on_disk": a.frames, "workers": train.source.num_workers, "ms": stage,
-                              "img_per_s": {k: B / stage[k] * 1e3 for k in ("train_step_alone", "train_step_with_file_loader", "file_loader_alone")},
-                              "loader_cost_fraction": stage["train_step_with_file_loader"] / stage["train_step_alone"] - 1.0}
+        loops = dict(train_step_alone=alone, train_step_with_file_loader=looped, file_loader_alone=loader_only,
+                     train_step_with_file_loader_device_decode=looped_dd, file_loader_alone_device_decode=loader_only_dd)
+        stage.update({k: float(np.median(v)) for k, v in loops.items()})
+        stage["device_decode_status_check_per_batch_mean"] = float(np.mean(waited))
+        stage["device_decode_status_check_per_batch_max"] = float(np.max(waited))
+        out["file_loader"] = {"frames_on_disk": a.frames, "loader_stream": a.loader_stream, "workers": train.source.num_workers, "ms": stage,
+                              "img_per_s": {k: B / stage[k] * 1e3 for k in loops},
+                              "spread": {k: float((max(v) - min(v)) / np.median(v)) for k, v in loops.items()},
+                              "loader_cost_fraction": stage["train_step_with_file_loader"] / stage["train_step_alone"] - 1.0,
+                              # the condition of profiles/jpeg_decode_notes.md: with the flag not slower than without it by more than the run's spread
+                              "device_decode_over_pillow": stage["train_step_with_file_loader_device_decode"] / stage["train_step_with_file_loader"],
+                              "device_decode_gap_to_step_alone": stage["train_step_with_file_loader_device_decode"] / stage["train_step_alone"] - 1.0,
+                              "device_decode_counters": train_dd.counters}
     finally:
         os.chdir(cwd)
         shutil.rmtree(root, ignore_errors=True)
