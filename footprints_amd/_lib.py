@@ -284,6 +284,7 @@ SIGNATURES = {
     "fp_conv_stem_hp_supported": (C.c_int, [_P]),
     "fp_conv_stem_hp": (C.c_int, [_P, _P, _P, _P, _P, _P, _AUX, _P]),
     "fp_conv_stem_wgrad_hp": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _I64, _P, _P]),
+    "fp_head_grid": (C.c_int, [_I32, _I32, _I32, _I32, _P]),
     "fp_head_wgrad_workspace": (_I64, [_I32, _I32, _I32, _I32]),
     "fp_head_wgrad": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, C.c_int, _P, _I64, _P]),
     "fp_bn_workspace": (_I64, [_I64, _I32]),

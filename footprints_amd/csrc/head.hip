@@ -615,11 +615,23 @@ bool head_cin_ok(int Cin) { return Cin >= 4 && Cin <= MAXC && (Cin & (Cin - 1)) 
 
 }  // namespace
 
+// host-only: the workgroup mapping fp_head_fwd and fp_head_dgrad launch with -- out = (column blocks, rows walked per workgroup, row groups
+// per image).  The launches below take it from here, so the answer cannot drift from what runs.
+extern "C" int fp_head_grid(int32_t N, int32_t h, int32_t w, int32_t Cin, int32_t out[3]) {
+  FP_REQUIRE(out, "fp_head_grid: null pointer");
+  FP_REQUIRE(head_cin_ok(Cin) && N >= 1 && h >= 2 && w >= 2, "fp_head_grid: Cin=%d must be a power of two in [4,128], dims >= 2", Cin);
+  const HeadGrid g = head_grid(N, h, w, Cin, 16);
+  out[0] = g.colblocks; out[1] = g.rows; out[2] = g.gpi;
+  return FP_OK;
+}
+
 extern "C" int fp_head_fwd(const float* x, const float* w_oihw, const float* bias, float* low, int32_t N, int32_t h, int32_t w,
                            int32_t Cin, int32_t apply_sigmoid, fp_stream_t stream) {
   FP_REQUIRE(x && w_oihw && bias && low, "fp_head_fwd: null pointer");
   FP_REQUIRE(head_cin_ok(Cin) && h >= 2 && w >= 2, "fp_head_fwd: Cin=%d must be a power of two in [4,128], dims >= 2", Cin);
-  const HeadGrid g = head_grid(N, h, w, Cin, 16);
+  int32_t gq[3];
+  if (int rc = fp_head_grid(N, h, w, Cin, gq)) return rc;
+  const HeadGrid g{gq[0], gq[1], gq[2]};
   fp_launch(head_fwd_kernel, dim3(g.colblocks, N * g.gpi), dim3(256), 0, (hipStream_t)stream, x, w_oihw, bias, low, h, w, Cin,
                      g.rows, g.gpi, apply_sigmoid);
   return fp_check_launch("fp_head_fwd");
@@ -665,7 +677,9 @@ extern "C" int fp_head_dgrad(const float* dzlow, const float* w_oihw, const floa
   unsigned* amax_out = fp_amax_out_of(aux);
   FP_REQUIRE(dzlow && w_oihw && dx, "fp_head_dgrad: null pointer");
   FP_REQUIRE(head_cin_ok(Cin) && h >= 2 && w >= 2, "fp_head_dgrad: unsupported Cin=%d", Cin);
-  const HeadGrid g = head_grid(N, h, w, Cin, 16);
+  int32_t gq[3];
+  if (int rc = fp_head_grid(N, h, w, Cin, gq)) return rc;
+  const HeadGrid g{gq[0], gq[1], gq[2]};
   fp_launch(head_dgrad_kernel, dim3(g.colblocks, N * g.gpi), dim3(256), 0, (hipStream_t)stream, dzlow, w_oihw, elu_src, dx, h, w,
                      Cin, g.rows, g.gpi, amax_out);
   return fp_check_launch("fp_head_dgrad");

@@ -293,6 +293,8 @@ int fp_head_upsample_bwd(const float* dout_nchw, const float* low, float* dzlow,
  * elu_src != NULL: dx *= elu'(elu_src) (the head is the only consumer of an ELU output: outconv4, network.py:78-80) */
 int fp_head_dgrad(const float* dzlow, const float* w_oihw, const float* elu_src, float* dx, int32_t N, int32_t h, int32_t w,
                   int32_t Cin, const fp_aux* aux, fp_stream_t stream);
+/* host-only query: the workgroup mapping of fp_head_fwd / fp_head_dgrad, out = (column blocks, rows per workgroup, row groups per image) */
+int fp_head_grid(int32_t N, int32_t h, int32_t w, int32_t Cin, int32_t out[3]);
 /* dw_oihw[2][Cin][3][3], db[2] (+)= ... ; deterministic two-stage */
 int64_t fp_head_wgrad_workspace(int32_t N, int32_t h, int32_t w, int32_t Cin);
 int fp_head_wgrad(const float* x, const float* dzlow, float* dw_oihw, float* db, int32_t N, int32_t h, int32_t w,

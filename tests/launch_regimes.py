@@ -1,0 +1,190 @@
+"""The host launch arithmetic of the step's non-convolution kernels, restated in plain Python, and what follows from it for a
+test: which launch REGIME a shape runs in, and how long the longest chain of dependent float32 additions behind one reduced output is.
+
+Every function names the file:line it restates.  tests/test_launch_regimes_cpu.py sweeps these against the library's own answers
+(the workspace queries and fp_head_grid), so a changed launch rule fails there before the small GPU shapes silently stop reaching
+what the product runs.
+
+A regime is a small tuple; a launch maps to a frozenset of them (a head launch holds workgroups of several kinds: full row groups, the
+tail group, the part-dead last column block).  "covered" means: every tuple the workload produces is produced by some GPU case.
+"""
+import math
+
+U = 2.0 ** -24            # unit roundoff of float32 (round to nearest)
+
+
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+# ---- grids -------------------------------------------------------------------------------------------------------------------------
+def head_grid(N, H, W, Cin, max_rows=16):
+    """csrc/head.hip:597 head_grid -> (colblocks, rows, groups per image); fp_head_grid answers the same"""
+    colblocks = ceil_div(W * (Cin // 4), 256)
+    rows = max_rows
+    while rows > 4 and colblocks * N * ceil_div(H, rows) < 2048:
+        rows >>= 1
+    return colblocks, rows, ceil_div(H, rows)
+
+
+def head_wgrad_blocks(M, Cin):
+    """csrc/head.hip:606 head_wgrad_blocks"""
+    ppb = 256 // (Cin // 4)
+    return max(1, min(1024, ceil_div(M, ppb * 8)))
+
+
+def bn_blocks(M, C, iters=4):
+    """csrc/bn_pool.hip:20 bn_blocks (FP_BN_ROWS_PER_THREAD unset: 4 rows per thread)"""
+    rows = 256 // (C // 4)
+    return max(1, min(512, ceil_div(M, rows * iters)))
+
+
+def colsum_blocks(M, C):
+    """csrc/loss_adam_misc.hip:153 colsum_blocks"""
+    rows = 256 // (C // 4)
+    return max(1, min(512, ceil_div(M, rows * 16)))
+
+
+def loss_blocks(npix):
+    """csrc/loss_adam_misc.hip:109 loss_blocks"""
+    return max(1, min(2048, ceil_div(npix, 256 * 4)))
+
+
+def ew_grid(total, cap=8192):
+    """csrc/bn_pool.hip:339 and csrc/loss_adam_misc.hip:11 ew_grid (same rule, default cap 8192); csrc/psp.hip:150 grid_for is the
+    same rule with cap 4096"""
+    return max(1, min(cap, ceil_div(total, 256)))
+
+
+def adam_grid(n):
+    """csrc/loss_adam_misc.hip:301,346: ew_grid(n / 4 + 1, 4096) over float4 items; the n % 4 tail is workgroup 0's"""
+    return ew_grid(n // 4 + 1, 4096)
+
+
+def _prod(shape):
+    p = 1
+    for s in shape:
+        p *= s
+    return p
+
+
+# kernel -> (work items of one launch, grid cap): the element-wise kernels, items as the kernel counts them (float4 where it loads float4)
+EW = {
+    "bn_apply": (lambda M, C: M * (C // 4), 8192),                                     # bn_pool.hip:394-395
+    "bn_bwd_apply": (lambda M, C: M * (C // 4), 8192),                                 # bn_pool.hip:414-415
+    "maxpool_fwd": (lambda N, H, W, C: N * ((H + 1) // 2) * ((W + 1) // 2) * (C // 4), 8192),   # bn_pool.hip:440-441
+    "maxpool_bwd": (lambda N, H, W, C: N * H * W * (C // 4), 8192),                    # bn_pool.hip:449-450
+    "up2cat_bwd": (lambda N, h, w, C0, C1: max(N * h * w * (C0 // 4), N * 4 * h * w * (C1 // 4)), 8192),   # loss_adam_misc.hip:401-403
+    "nchw_to_nhwc": (lambda N, C, H, W: N * C * H * W, 8192),                          # loss_adam_misc.hip:410
+    "nhwc_to_nchw": (lambda N, C, H, W: N * C * H * W, 8192),                          # loss_adam_misc.hip:415
+    "fill": (lambda n: n, 8192),                                                       # loss_adam_misc.hip:421
+    "scale_rows": (lambda *shape: _prod(shape), 8192),                                 # loss_adam_misc.hip:359
+    "adam": (lambda n: n // 4, 4096),                                                  # loss_adam_misc.hip:123-124 (grid: adam_grid)
+    "psp": (lambda total: total, 4096),                                                # psp.hip:150 (any of its five kernels)
+}
+
+
+def ew_launch(kernel, *shape):
+    items, cap = EW[kernel]
+    n = items(*shape)
+    grid = adam_grid(shape[0]) if kernel == "adam" else ew_grid(n, cap)
+    return n, grid
+
+
+# ---- regimes -----------------------------------------------------------------------------------------------------------------------
+def ew_regime(kernel, *shape):
+    """("ew", kernel, passes, ragged_last_pass): passes = grid-stride iterations of the busiest thread, reported as 1 or 2 (2 = "more than once":
+    the loop has no third path); ragged = the last pass does not fill the grid (for one pass: the last workgroup is not full)"""
+    n, grid = ew_launch(kernel, *shape)
+    passes = ceil_div(n, grid * 256) if n else 0
+    ragged = (n % (grid * 256) != 0) if passes > 1 else (n % 256 != 0)
+    return frozenset([("ew", kernel, min(passes, 2), ragged)])
+
+
+def adam_regime(n):
+    """the float4 body as an "ew" regime plus ("adam_tail", n % 4): the scalar tail (loss_adam_misc.hip:140)"""
+    return ew_regime("adam", n) | frozenset([("adam_tail", n % 4)])
+
+
+def head_regime(N, H, W, Cin):
+    """("head", rows, ring_wraps, tail_rows, dead_lanes) per KIND of workgroup in the launch.  rows = row-group height; ring_wraps = how
+    many times the four-buffer row ring goes round for that workgroup (head.hip:99-107: four rows per turn); tail_rows = rows the last
+    group of an image walks when that is fewer than `rows` (0 for a full group); dead_lanes = the last column block holds lanes past W"""
+    colblocks, rows, gpi = head_grid(N, H, W, Cin)
+    tail = H - (gpi - 1) * rows
+    heights = {rows} if gpi > 1 or tail == rows else set()
+    if tail != rows:
+        heights.add(tail)
+    deads = {False} if (colblocks > 1 or W * (Cin // 4) == 256 * colblocks) else set()
+    if W * (Cin // 4) != 256 * colblocks:
+        deads.add(True)
+    return frozenset(("head", rows, ceil_div(hh, 4), 0 if hh == rows else hh, d) for hh in heights for d in deads)
+
+
+def _final_lanes(nblk):
+    """the one-wave-per-output final kernels: lane l takes partials l, l + 64, ...: 0 = some lanes get none, 1 = one pass, 2 = a loop"""
+    return 0 if nblk < 64 else min(ceil_div(nblk, 64), 2)
+
+
+def head_wgrad_regime(N, H, W, Cin):
+    """("head_wgrad", capped, grid_stride_loop, final_lanes_loop)"""
+    M = N * H * W
+    ppb = 256 // (Cin // 4)
+    nblk = head_wgrad_blocks(M, Cin)
+    return frozenset([("head_wgrad", ceil_div(M, ppb * 8) > 1024, ceil_div(M, nblk * ppb) > 1, _final_lanes(nblk))])
+
+
+def bn_reduce_regime(M, C):
+    """("bn_reduce", capped, zero_row_threads, final_lanes_loop) for bn_stats_kernel and bn_bwd_reduce_kernel (same mapping)"""
+    R = 256 // (C // 4)
+    nblk = bn_blocks(M, C)
+    return frozenset([("bn_reduce", ceil_div(M, R * 4) > 512, nblk * R > M, _final_lanes(nblk))])
+
+
+def colsum_regime(M, C):
+    """("colsum", capped, zero_row_threads, idle_threads, final_lanes_loop); idle_threads: C / 4 does not divide 256
+    (loss_adam_misc.hip:162)"""
+    C4 = C // 4
+    R = 256 // C4
+    nblk = colsum_blocks(M, C)
+    return frozenset([("colsum", ceil_div(M, R * 16) > 512, nblk * R > M, 256 % C4 != 0, _final_lanes(nblk))])
+
+
+# ---- chain lengths -----------------------------------------------------------------------------------------------------------------
+# L = the longest chain of dependent float32 additions behind one reduced output: iterations of one thread, then the in-LDS merges, then
+# the shuffle tree, then the final kernel's per-lane loop (and its tree).  Stages a kernel runs in double are counted all the same: the
+# bound stays an upper bound.
+def bn_chain(M, C):
+    """bn_stats_kernel / bn_bwd_reduce_kernel (bn_pool.hip:31,156) + their final kernels (:71,:203)"""
+    R = 256 // (C // 4)
+    nblk = bn_blocks(M, C)
+    return ceil_div(M, nblk * R) + (R - 1) + ceil_div(nblk, 64) + 6
+
+
+def colsum_chain(M, C):
+    """colsum_kernel + colsum_final_kernel (loss_adam_misc.hip:160,179)"""
+    R = 256 // (C // 4)
+    nblk = colsum_blocks(M, C)
+    return ceil_div(M, nblk * R) + (R - 1) + ceil_div(nblk, 64) + 6
+
+
+def head_wgrad_chain(N, H, W, Cin):
+    """head_wgrad_kernel + head_wgrad_reduce_kernel (head.hip:433,576).  A pixel on row/column 1 or n-2 is also a mirror source: up to
+    four multiply-adds into one accumulator per iteration (head.hip:508-518); then the slot tree (log2(64 / Q) steps), the four waves
+    in LDS (3), the reduce kernel's lane loop and its tree (6)"""
+    M = N * H * W
+    Q = Cin // 4
+    ppb = 256 // Q
+    nblk = head_wgrad_blocks(M, Cin)
+    return 4 * ceil_div(M, nblk * ppb) + int(math.log2(64 // Q) if Q < 64 else 0) + 3 + ceil_div(nblk, 64) + 6
+
+
+def head_chain(Cin):
+    """head_fwd_kernel (head.hip:79-88): 9 taps x 4 channels in one lane, then log2(Q) shuffle steps, then the bias"""
+    Q = Cin // 4
+    return 36 + int(math.log2(Q)) + 1
+
+
+def sum_bound(L, k, abs_terms, result):
+    """first-order summation bound: (L + k) u sum|terms| + u |result|; k = roundings inside one term"""
+    return (L + k) * U * abs_terms + U * abs(result)

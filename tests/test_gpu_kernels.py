@@ -745,18 +745,20 @@ def test_bn_train_fwd_bwd(N, H, W, Cn):
 @pytest.mark.parametrize("N,H,W,Cn", [(2, 8, 12, 16), (2, 96, 320, 64), (1, 7, 9, 8)])
 def test_maxpool(N, H, W, Cn):
     ops, L = _ops()
-    x = F.relu(rnd((N, Cn, H, W), 48)).requires_grad_(True)       # many exact ties at 0, like the real input
-    y = F.max_pool2d(x, 3, 2, 1)
-    g = rnd(tuple(y.shape), 49)
-    y.backward(g)
-    OH, OW = y.shape[2:]
-    ys = torch.empty((N, OH, OW, Cn), device="cuda")
-    am = torch.empty((N, OH, OW, Cn), dtype=torch.uint8, device="cuda")
-    ops.maxpool_fwd(nhwc(x.detach()), ys, am)
-    assert torch.equal(nchw(ys), y.detach())
-    dx = torch.empty((N, H, W, Cn), device="cuda")
-    ops.maxpool_bwd(nhwc(g), am, dx)
-    check(nchw(dx), x.grad, "maxpool_bwd", 1e-6)
+    x0 = rnd((N, Cn, H, W), 48)
+    # many exact ties at 0, like the real input; then signed with whole windows below zero: a pad value of 0 instead of -inf would win those
+    for x in (F.relu(x0).requires_grad_(True), (x0 - 0.7).requires_grad_(True)):
+        y = F.max_pool2d(x, 3, 2, 1)
+        g = rnd(tuple(y.shape), 49)
+        y.backward(g)
+        OH, OW = y.shape[2:]
+        ys = torch.empty((N, OH, OW, Cn), device="cuda")
+        am = torch.empty((N, OH, OW, Cn), dtype=torch.uint8, device="cuda")
+        ops.maxpool_fwd(nhwc(x.detach()), ys, am)
+        assert torch.equal(nchw(ys), y.detach())
+        dx = torch.empty((N, H, W, Cn), device="cuda")
+        ops.maxpool_bwd(nhwc(g), am, dx)
+        check(nchw(dx), x.grad, "maxpool_bwd", 1e-6)
 
 
 # ----------------------------------------------------------------------------------------------------------

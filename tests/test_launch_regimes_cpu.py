@@ -1,0 +1,257 @@
+"""CPU: do the small shapes of tests/test_gpu_step_kernels.py still reach the launch regimes the product runs, and are the error
+bounds those tests use tight enough to see one dropped row?
+
+1. tests/launch_regimes.py restates the host launch arithmetic; here it is swept against the library's own answers.
+2. WORKLOAD lists, per kernel, the shapes the engine launches (footprints network at 12x192x640 and 4x512x640, the PSP segmentor at
+   12x192x640), read off footprints_amd/engine.py; CASES lists the GPU test shapes.  Every regime tuple of WORKLOAD must occur in CASES:
+   when a launch rule changes, this is the test that says which small shape stopped standing in for the product's.
+3. For every reduction case the float64 reference is recomputed without the last row and without the last workgroup's rows; one
+   reduced output at least must move by more than ten times its bound (tests/step_kernel_refs.py), else the bound could not see it.
+"""
+import ctypes
+
+import pytest
+import torch
+
+from tests import launch_regimes as LR
+from tests import step_kernel_refs as SR
+
+ADAM_N = 31021392          # parameters of the footprints network = length of the flat buffers optim.py:44,54,83 hand to Adam
+
+
+def network_shapes(N, H, W, psp=False):
+    """kernel -> shapes of one train step, by engine.py line.  Encoder levels: stem H/2 (64), layer1 H/4 (64), layer2 H/8 (128), layer3
+    H/16 (256), layer4 H/32 (512) (engine.py:670-698, 876-880); decoder block bi: pre convs at level 4-bi, post convs at level 3-bi with
+    chans[bi][1] channels (engine.py:152, 987-1000), outconv4 at full resolution with 32 (engine.py:1005-1007).  Where a switch decides
+    between one of these kernels and a fused path, the shape is listed: the table is a superset."""
+    lv = [(H >> s, W >> s, c) for s, c in ((1, 64), (2, 64), (3, 128), (4, 256), (5, 512))]
+    bn = [(N * h * w, c) for h, w, c in lv]
+    (h0, w0, _), (h1, w1, _), (h2, w2, _), (h3, w3, _), (h4, w4, _) = lv
+    out = {
+        "bn_reduce": bn,                       # engine.py:522 (statistics), :1163 :1177 :1208 :1212 :1261 (backward sums)
+        "bn_apply": bn,                        # engine.py:530
+        "bn_bwd_apply": bn,                    # engine.py:1163 ... :1261
+        "maxpool_fwd": [(N, h0, w0, 64)],      # engine.py:705
+        "maxpool_bwd": [(N, h0, w0, 64)],      # engine.py:1232 (dx = the stem feature gradient, accumulate=True)
+        # bias gradients of the decoder convolutions, engine.py:1032 :1075: pre1/pre2 and post1/post2 of the four blocks, o41/o42
+        "colsum": [(N * h4 * w4, 256), (N * h3 * w3, 256), (N * h3 * w3, 128), (N * h2 * w2, 128), (N * h2 * w2, 64), (N * h1 * w1, 64),
+                   (N * h1 * w1, 64), (N * h0 * w0, 64), (N * H * W, 32)],
+        # engine.py:1391 (outconv4's input), :1427 (blocks 4..1: hl, wl = the pre-concat resolution, C0 = C1 = cout)
+        "up2cat_bwd": [(N, h0, w0, 64, 0), (N, h1, w1, 64, 64), (N, h2, w2, 64, 64), (N, h3, w3, 128, 128), (N, h4, w4, 256, 256)],
+        # engine.py:979 (forward), :1359 :1370 (data gradient), :552 (weight gradient): heads on blocks 2, 3, 4 and outconv4
+        "head": [(N, h2, w2, 128), (N, h1, w1, 64), (N, h0, w0, 64), (N, H, W, 32)],
+        "head_wgrad": [(N, h2, w2, 128), (N, h1, w1, 64), (N, h0, w0, 64), (N, H, W, 32)],
+        "adam": [(ADAM_N,)],                   # optim.py:44 :54 :83
+        # engine.py:655: every encoder convolution's OIHW weights (ResNet-34: stem, 3x3 pairs, 1x1 shortcuts)
+        "scale_rows": [(64, 3, 7, 7), (64, 64, 3, 3), (128, 64, 3, 3), (128, 128, 3, 3), (128, 64, 1, 1), (256, 128, 3, 3), (256, 256, 3, 3),
+                       (256, 128, 1, 1), (512, 256, 3, 3), (512, 512, 3, 3), (512, 256, 1, 1)],
+    }
+    if psp:                                    # the segmentor's decoder starts from the 1024-channel pyramid concatenation (engine.py:152):
+        out = dict(out)                        # the shapes of THESE kernels do not change (its heads: engine.py:148-150, no sigmoid, scale 1)
+        del out["adam"]
+    return out
+
+
+WORKLOAD = {"footprints 12x192x640": network_shapes(12, 192, 640), "footprints 4x512x640": network_shapes(4, 512, 640),
+            "psp segmentor 12x192x640": network_shapes(12, 192, 640, psp=True)}
+
+BN_BIG = (3, 82, 100, 512)
+BN_SMALL = (2, 6, 6, 128)
+HEAD_BIG = (2, 1027, 500, 16)
+HEAD_R16 = (2, 2050, 500, 16)
+HEAD_SMALL = [(2, 6, 10, 16), (2, 40, 56, 128)]
+
+# the GPU test shapes (tests/test_gpu_step_kernels.py takes them from here)
+CASES = {
+    "bn": [BN_BIG, (2, 1, 1, 512), (2, 2, 2, 128), BN_SMALL, (1, 3, 1, 16), (3, 10, 10, 4), (3, 10, 10, 1024)],        # (N, H, W, C)
+    "maxpool_fwd": [(1, 1, 5, 4), (2, 2, 2, 8), (1, 7, 9, 8), (2, 8, 12, 16), (2, 8, 16, 32), (3, 211, 209, 64)],
+    "maxpool_bwd": [(1, 1, 5, 4), (2, 2, 2, 8), (1, 7, 9, 8), (2, 8, 12, 16), (2, 8, 16, 32), (3, 211, 209, 64)],
+    "colsum": [(M, C) for C in (4, 20, 36, 72, 1024) for M in (1, 3, 1000)] + [(1100, 1024), (24600, 512)],
+    "up2cat_bwd": [(1, 1, 1, 4, 4), (1, 3, 5, 8, 4), (2, 4, 6, 8, 0), (2, 4, 8, 16, 16), (2, 129, 128, 64, 64)],
+    "head": HEAD_SMALL + [HEAD_BIG, HEAD_R16],
+    "head_wgrad": HEAD_SMALL + [HEAD_BIG],
+    "adam": [(n,) for n in (1, 2, 3, 4, 5, 1023, 4300003, 4300004)],
+    "scale_rows": [(512, 512, 3, 3), (64, 3, 7, 7), (64, 64, 3, 3)],
+    "layout": [(2, 5, 7, 9), (3, 5, 373, 401)],                                                                  # (N, C, H, W)
+    "fill": [(1,), (2097153,)],
+}
+
+
+def regimes(kernel, shape):
+    if kernel == "bn_reduce":
+        return LR.bn_reduce_regime(*shape)
+    if kernel == "colsum":
+        return LR.colsum_regime(*shape)
+    if kernel == "head":
+        return LR.head_regime(*shape)
+    if kernel == "head_wgrad":
+        return LR.head_wgrad_regime(*shape)
+    if kernel == "adam":
+        return LR.adam_regime(*shape)
+    return LR.ew_regime(kernel, *shape)
+
+
+def case_shapes(kernel):
+    """the CASES rows that exercise `kernel`, in the kernel's own argument order"""
+    if kernel in ("bn_reduce", "bn_apply", "bn_bwd_apply"):
+        return [(N * H * W, C) for N, H, W, C in CASES["bn"]]
+    if kernel in ("nchw_to_nhwc", "nhwc_to_nchw"):
+        return CASES["layout"]
+    return CASES[kernel]
+
+
+KERNELS = sorted({k for w in WORKLOAD.values() for k in w})
+
+
+def _lib():
+    from footprints_amd import _lib as L
+    return L.load()
+
+
+# ---- 1. restatement against the library ----------------------------------------------------------------------------------------------
+def _sweep(seed, n, lo, hi):
+    g = torch.Generator().manual_seed(seed)
+    return [int(v) for v in torch.randint(lo, hi, (n,), generator=g)]
+
+
+def test_bn_blocks_match_library():
+    lib = _lib()
+    Ms = [1, 2, 3, 8, 72, 255, 256, 257, 2047, 2048, 2049, 24600, 368640, 1474560] + _sweep(1, 40, 1, 3000000)
+    for C in (4, 8, 16, 32, 64, 128, 256, 512, 1024):
+        for M in Ms:
+            nblk = (lib.fp_bn_workspace(M, C) - C * 2 * 4) // (C * 3 * 4)
+            assert nblk == LR.bn_blocks(M, C), (M, C)
+
+
+def test_colsum_blocks_match_library():
+    lib = _lib()
+    Ms = [1, 3, 1000, 1100, 8191, 8192, 8193, 24600, 1474560] + _sweep(2, 30, 1, 3000000)
+    for C in (4, 20, 32, 36, 64, 72, 128, 256, 512, 1024):
+        for M in Ms:
+            assert lib.fp_colsum_workspace(M, C) == LR.colsum_blocks(M, C) * C * 4, (M, C)
+
+
+def test_head_grids_match_library():
+    lib = _lib()
+    hs, ws = [2, 3, 6, 24, 37, 96, 192, 512, 1027, 2050] + _sweep(3, 6, 2, 2100), [2, 5, 8, 56, 80, 320, 500, 640] + _sweep(4, 4, 2, 700)
+    out = (ctypes.c_int32 * 3)()
+    for Cin in (4, 8, 16, 32, 64, 128):
+        for N in (1, 2, 12, 20):
+            for h in hs:
+                for w in ws:
+                    assert lib.fp_head_grid(N, h, w, Cin, out) == 0
+                    assert tuple(out) == LR.head_grid(N, h, w, Cin), (N, h, w, Cin)
+                    per = (9 * Cin * 2 + 2) * 4
+                    assert lib.fp_head_wgrad_workspace(N, h, w, Cin) == LR.head_wgrad_blocks(N * h * w, Cin) * per, (N, h, w, Cin)
+    assert lib.fp_head_grid(2, 6, 10, 12, out) != 0 and lib.fp_head_grid(2, 1, 10, 16, out) != 0        # what the launches refuse
+
+
+def test_loss_blocks_match_library():
+    lib = _lib()
+    for B, H, W in [(1, 1, 1), (1, 32, 32), (1, 32, 33), (12, 192, 640), (4, 512, 640), (3, 40, 72), (20, 192, 640), (2, 1024, 1024),
+                    (2, 1024, 1025)] + [(2, h, 37) for h in _sweep(5, 30, 1, 40000)]:
+        assert lib.fp_loss_workspace(B, H, W) == LR.loss_blocks(B * H * W) * 16 * 4, (B, H, W)
+
+
+def test_issue_table_rows():
+    """the launch regimes of the 12x192x640 step that the kernel tests did not reach before this file existed"""
+    assert LR.head_grid(12, 96, 320, 64)[1] == 8 and LR.head_grid(12, 192, 640, 32)[1] == 16          # the row ring wraps
+    assert [LR.ceil_div(12 * h * w, (256 // (c // 4)) * 8) for h, w, c in ((192, 640, 32), (96, 320, 64))] == [5760, 2880]   # capped at 1024
+    assert [LR.ceil_div(m, (256 // (c // 4)) * 4) for m, c in ((368640, 64), (92160, 64), (23040, 128))] == [5760, 1440, 720]    # capped at 512
+    assert LR.ew_launch("scale_rows", 512, 512, 3, 3) == (2359296, 8192) and 2359296 > 8192 * 256
+    assert LR.ew_launch("adam", ADAM_N)[1] == 4096 and ADAM_N // 4 > 4096 * 256
+    assert LR.colsum_blocks(12 * 192 * 640, 32) == 512 and LR.ceil_div(12 * 192 * 640, 32 * 16) > 512
+
+
+# ---- 2. the workload is covered by the cases ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_workload_regimes_occur_in_cases(kernel):
+    have = set()
+    for shape in case_shapes(kernel):
+        have |= regimes(kernel, shape)
+    for name, table in WORKLOAD.items():
+        for shape in table.get(kernel, ()):
+            missing = regimes(kernel, shape) - have
+            assert not missing, "%s, %s %s runs %s: no GPU case does (cases reach %s)" % (name, kernel, shape, sorted(missing), sorted(have))
+
+
+def test_cases_reach_the_structural_edges():
+    """regimes no workload runs today that the cases add on purpose"""
+    bn = set().union(*(LR.bn_reduce_regime(N * H * W, C) for N, H, W, C in CASES["bn"]))
+    assert any(r[2] for r in bn), "no BatchNorm case leaves threads without rows"
+    cs = set().union(*(LR.colsum_regime(*s) for s in CASES["colsum"]))
+    assert any(r[3] for r in cs) and any(r[2] for r in cs), "no column-sum case with idle threads / threads without rows"
+    hd = set().union(*(LR.head_regime(*s) for s in CASES["head"]))
+    assert ("head", 8, 1, 3, True) in hd and ("head", 16, 1, 2, True) in hd and ("head", 16, 4, 0, False) in hd
+    ad = set().union(*(LR.adam_regime(*s) for s in CASES["adam"]))
+    assert {("adam_tail", r) for r in range(4)} <= ad
+
+
+# ---- 3. the bounds can see a dropped row -------------------------------------------------------------------------------------------
+def _moves(full, dropped, bound):
+    """largest (shift of a reduced output) / (its bound) over all outputs of the case"""
+    worst = 0.0
+    for k in full:
+        b = bound[k].double()
+        shift = (full[k] - dropped[k]).abs()
+        ok = b > 0
+        if bool(ok.any()):
+            worst = max(worst, float((shift[ok] / b[ok]).max()))
+        if bool((shift[~ok] > 0).any()):
+            worst = float("inf")              # bound 0: the output must be exact, any shift shows
+    return worst
+
+
+def _drops(M, rows_per_block, nblk, empty_ok=False):
+    d = [("last row", SR.last_row_mask(M))] if (M > 1 or empty_ok) else []
+    if nblk > 1:
+        d.append(("last workgroup", SR.last_block_mask(M, rows_per_block, nblk)))
+    return d
+
+
+def _assert_sensitive(what, ref_fn, M, rows_per_block, nblk, conditioned=(), empty_ok=False):
+    full, bound = ref_fn(None)
+    for k in conditioned:
+        r = SR.rel_to_max(bound[k], full[k])
+        assert r < 1e-4, "%s: the bound on %s is %.2e of the tensor's max: badly conditioned inputs" % (what, k, r)
+    for name, keep in _drops(M, rows_per_block, nblk, empty_ok):
+        dropped, _ = ref_fn(keep)
+        mv = _moves(full, dropped, bound)
+        assert mv > 10.0, "%s: dropping the %s moves no output by more than %.2f bounds" % (what, name, mv)
+
+
+@pytest.mark.parametrize("shape", CASES["bn"])
+def test_bn_bounds_see_a_dropped_row(shape):
+    inp = SR.bn_inputs(shape)
+    M, C = inp["z"].shape
+    R, nblk = 256 // (C // 4), LR.bn_blocks(M, C)
+
+    def stats(keep):
+        ref, bound = SR.bn_stats_ref(inp, keep)
+        return {k: ref[k] for k in ("mean", "var")}, {k: bound[k] for k in ("mean", "var")}
+    _assert_sensitive("bn_train_stats %s" % (shape,), stats, M, R, nblk)
+    ref, bound = SR.bn_stats_ref(inp)
+    for k in ref:
+        r = SR.rel_to_max(bound[k], ref[k])
+        assert r < 1e-4, "bn_train_stats %s: the bound on %s is %.2e of the tensor's max" % (shape, k, r)
+    for relu_out in (True, False):
+        _assert_sensitive("bn_bwd %s" % (shape,), lambda keep: SR.bn_bwd_sums_ref(inp, relu_out, keep), M, R, nblk, ("dbeta", "dgamma"))
+    if shape in (BN_BIG, BN_SMALL):
+        dz, bdz, _ = SR.bn_bwd_dz_ref(inp, True)
+        assert SR.rel_to_max(bdz, dz) < 1e-4
+
+
+@pytest.mark.parametrize("shape", CASES["colsum"])
+def test_colsum_bounds_see_a_dropped_row(shape):
+    M, C = shape
+    inp = SR.colsum_inputs(M, C)
+    _assert_sensitive("colsum %s" % (shape,), lambda keep: SR.colsum_ref(inp, keep), M, 256 // (C // 4), LR.colsum_blocks(M, C),
+                      ("sum",), empty_ok=True)       # (a sum over no rows is 0: M = 1 can drop its only row)
+
+
+@pytest.mark.parametrize("shape", CASES["head_wgrad"])
+def test_head_wgrad_bounds_see_a_dropped_pixel(shape):
+    N, h, w, Cin = shape
+    inp = SR.head_inputs(shape)
+    _assert_sensitive("head_wgrad %s" % (shape,), lambda keep: SR.head_wgrad_ref(inp, keep), N * h * w, 256 // (Cin // 4),
+                      LR.head_wgrad_blocks(N * h * w, Cin), ("dw", "db"))
