@@ -112,6 +112,11 @@ class JpegDecodeSample(C.Structure):
         "scan_bytes", "h", "w", "ncomp", "hs", "vs", "table_set", "reserved")]
 
 
+class JpegDecodeWindowSample(C.Structure):
+    """fp_jpeg_decode_window_sample (include/footprints_hip.h)"""
+    _fields_ = JpegDecodeSample._fields_ + [(n, C.c_int32) for n in ("y0", "x0", "rh", "rw")]
+
+
 _P, _I32, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _DESC = C.POINTER(ConvDesc)
 
@@ -203,6 +208,8 @@ SIGNATURES = {
     "fp_jpeg_decode_table_words": (_I32, []),
     "fp_jpeg_decode_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32, _I32]),
     "fp_jpeg_decode": (C.c_int, [_P, _I64, _P, _P, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "fp_jpeg_decode_window_sample_bytes": (_I32, []),
+    "fp_jpeg_decode_window": (C.c_int, [_P, _I64, _P, _P, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "fp_adaptive_avgpool_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
     "fp_adaptive_avgpool_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, C.c_int, _P]),
     "fp_bilinear_ac_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),

@@ -19,6 +19,13 @@
 //   dc        one workgroup per sample: prefix sums of the DC differences per component in scan order
 //   idct      8 threads per block: dequantise, jidctint's column and row pass, +128, clamp, into component planes
 //   colour    one thread per pixel: fancy upsampling of the chroma planes, YCbCr -> RGB, into the packed output
+// fp_jpeg_decode_window decodes one rectangle (y0, x0, rh, rw) of every picture: the bytes of the whole picture's [y0:y0+rh, x0:x0+rw],
+// dense at the sample's out_offset.  The entropy half is the same launches (a scan has no random access: every coefficient is decoded);
+// the pixel half is proportional to the window.  The component planes stay frame-sized and keep the whole picture's addressing, so the
+// upsampler's neighbours and edge clamps are the picture's; only the blocks the window needs are filled:
+//   idct      the luma blocks that intersect the rectangle, and the chroma blocks that intersect its chroma footprint grown by one sample
+//             on every side (clamped to the component): the fancy upsampler's far neighbour may lie in an MCU the window does not touch
+//   colour    one thread per window pixel
 #include <algorithm>
 
 #include "fp_common.h"
@@ -34,6 +41,13 @@ struct DecSample {          // fp_jpeg_decode_sample
   int32_t hs, vs;           // luma sampling factors: 1x1, 2x1 or 2x2; the chroma components are 1x1
   int32_t table_set;        // index of the table block
   int32_t reserved;
+};
+struct DecWinSample {       // fp_jpeg_decode_window_sample: the same fields, then the rectangle; out_offset is the window's, dense uint8 [rh][rw][3]
+  DecSample s;
+  int32_t y0, x0, rh, rw;
+};
+struct Rect {
+  int y0, x0, rh, rw;
 };
 
 // one table block, in 32-bit words
@@ -64,7 +78,7 @@ __constant__ unsigned char NATURAL[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24
 struct DecArgs {
   const unsigned char* scans;
   int64_t scans_bytes;
-  const DecSample* samples;
+  const unsigned char* samples;     // [B] records of sample_stride bytes: DecSample, or DecWinSample when `windowed`
   const uint32_t* tables;   // [n_sets][TAB_WORDS]
   unsigned char* out;
   int64_t out_bytes;
@@ -80,11 +94,25 @@ struct DecArgs {
   int64_t stream_stride, plane_bytes;
   int32_t B, n_sets, max_h, max_w, max_scan, subseq_bits, max_sub, max_blocks, round;
   int32_t stage_words;      // of the dynamic LDS of the sync and write kernels; 0 = subsequences too long to stage
+  int32_t sample_stride, windowed, max_win_h, max_win_w;
 };
 
 constexpr unsigned long long NEVER = ~0ull;
 
-__device__ __forceinline__ bool record_ok(const DecArgs& a, const DecSample& s) {
+__device__ __forceinline__ DecSample sample_of(const DecArgs& a, int b) {
+  return *reinterpret_cast<const DecSample*>(a.samples + (size_t)b * a.sample_stride);
+}
+// the rectangle of the picture a sample writes: the whole picture unless the call is windowed
+__device__ __forceinline__ Rect rect_of(const DecArgs& a, int b, const DecSample& s) {
+  Rect r = {0, 0, s.h, s.w};
+  if (a.windowed) {
+    const DecWinSample* ws = reinterpret_cast<const DecWinSample*>(a.samples + (size_t)b * a.sample_stride);
+    r.y0 = ws->y0, r.x0 = ws->x0, r.rh = ws->rh, r.rw = ws->rw;
+  }
+  return r;
+}
+
+__device__ __forceinline__ bool record_ok(const DecArgs& a, int b, const DecSample& s) {
   if (s.h < 1 || s.w < 1 || s.h > 65535 || s.w > 65535 || s.h > a.max_h || s.w > a.max_w) return false;
   if (s.scan_bytes < 1 || s.scan_bytes > a.max_scan || s.scan_offset < 0 || s.scan_offset + s.scan_bytes > a.scans_bytes) return false;
   if (s.table_set < 0 || s.table_set >= a.n_sets) return false;
@@ -95,7 +123,12 @@ __device__ __forceinline__ bool record_ok(const DecArgs& a, const DecSample& s) 
   } else {
     return false;
   }
-  return s.out_offset >= 0 && s.out_offset + (int64_t)s.h * s.w * 3 <= a.out_bytes;
+  const Rect r = rect_of(a, b, s);
+  if (a.windowed) {                 // not empty and inside the picture (h, w >= 1 here; rh, rw <= 65535 before they are subtracted)
+    if (r.rh < 1 || r.rw < 1 || r.rh > a.max_win_h || r.rw > a.max_win_w || r.y0 < 0 || r.x0 < 0) return false;
+    if (r.y0 > s.h - r.rh || r.x0 > s.w - r.rw) return false;
+  }
+  return s.out_offset >= 0 && s.out_offset + (int64_t)r.rh * r.rw * 3 <= a.out_bytes;
 }
 
 struct Geom {
@@ -139,8 +172,8 @@ __device__ __forceinline__ uint32_t group_scan(uint32_t v, uint32_t* wave_sums, 
 __global__ void __launch_bounds__(1024) dec_destuff_kernel(const DecArgs a) {
   __shared__ uint32_t wave_sums[16];
   const int b = blockIdx.x;
-  const DecSample s = a.samples[b];
-  if (!record_ok(a, s)) return;                 // the init kernel reports it
+  const DecSample s = sample_of(a, b);
+  if (!record_ok(a, b, s)) return;                 // the init kernel reports it
   const unsigned char* src = a.scans + s.scan_offset;
   unsigned char* dst = a.stream + (size_t)b * a.stream_stride;
   const int n = s.scan_bytes;
@@ -175,9 +208,9 @@ __global__ void __launch_bounds__(1024) dec_destuff_kernel(const DecArgs a) {
 // init: grid = (x, B), 256 threads
 __global__ void __launch_bounds__(256) dec_init_kernel(const DecArgs a) {
   const int b = blockIdx.y;
-  const DecSample s = a.samples[b];
+  const DecSample s = sample_of(a, b);
   int32_t* info = a.info + (size_t)b * INFO;
-  const bool ok = record_ok(a, s);
+  const bool ok = record_ok(a, b, s);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     info[I_CHANGE] = 0;
     info[I_HOPS] = 0;
@@ -344,7 +377,7 @@ __global__ void __launch_bounds__(GROUP) dec_sync_kernel(const DecArgs a) {
   int32_t* info = a.info + (size_t)b * INFO;
   if (!info[I_OK]) return;
   if (a.round > 0 && info[I_CHANGE] < a.round) return;          // nothing moved in the launch before: settled
-  const DecSample s = a.samples[b];
+  const DecSample s = sample_of(a, b);
   const uint32_t nbytes = (uint32_t)info[I_BYTES];
   const uint32_t total_bits = nbytes * 8;
   const uint32_t S = (uint32_t)a.subseq_bits;
@@ -419,7 +452,7 @@ __global__ void __launch_bounds__(256) dec_place_kernel(const DecArgs a, int rou
   const int b = blockIdx.x;
   int32_t* info = a.info + (size_t)b * INFO;
   if (!info[I_OK]) return;
-  const DecSample s = a.samples[b];
+  const DecSample s = sample_of(a, b);
   const uint32_t total_bits = (uint32_t)info[I_BYTES] * 8, S = (uint32_t)a.subseq_bits;
   const uint32_t nsub = max((total_bits + S - 1) / S, 1u);
   const bool settled = info[I_CHANGE] < rounds;
@@ -454,7 +487,7 @@ __global__ void __launch_bounds__(GROUP) dec_write_kernel(const DecArgs a) {
   const int b = blockIdx.y;
   int32_t* info = a.info + (size_t)b * INFO;
   if (!info[I_OK] || a.status[b] != 0) return;
-  const DecSample s = a.samples[b];
+  const DecSample s = sample_of(a, b);
   const uint32_t nbytes = (uint32_t)info[I_BYTES];
   const uint32_t total_bits = nbytes * 8, S = (uint32_t)a.subseq_bits;
   const uint32_t nsub = max((total_bits + S - 1) / S, 1u);
@@ -498,7 +531,7 @@ __global__ void __launch_bounds__(256) dec_dc_kernel(const DecArgs a) {
     return;
   }
   if (a.status[b] != 0) return;
-  const DecSample s = a.samples[b];
+  const DecSample s = sample_of(a, b);
   const Geom gm = geom_of(s);
   const int nblocks = min(gm.nblocks, a.max_blocks);
   int16_t* coef = a.coef + (size_t)b * a.max_blocks * 64;
@@ -571,25 +604,23 @@ __device__ __forceinline__ void idct_pass(const int* d, int* o, int n) {
 // the plane of component c of a sample: rows of `stride` bytes, padded to whole blocks
 __device__ __forceinline__ int plane_stride(const Geom& g, const DecSample& s, int c) { return g.mx * 8 * (c == 0 ? s.hs : 1); }
 
-// idct: grid = (ceil(max_blocks / 32), B), 256 threads = 32 blocks x 8 columns, then x 8 rows
-__global__ void __launch_bounds__(256) dec_idct_kernel(const DecArgs a) {
-  __shared__ int ws[32][8][9];
-  __shared__ uint32_t quant[4 * 64];
-  __shared__ int sel[3];
-  const int b = blockIdx.y;
-  const int32_t* info = a.info + (size_t)b * INFO;
-  if (!info[I_OK] || a.status[b] != 0) return;
-  const DecSample s = a.samples[b];
-  const Geom gm = geom_of(s);
-  const int nblocks = min(gm.nblocks, a.max_blocks);
-  if ((int)blockIdx.x * 32 >= nblocks) return;
+struct IdctLds {
+  int ws[32][8][9];
+  uint32_t quant[4 * 64];
+  int sel[3];
+};
+
+// 256 threads = 32 blocks x 8 columns, then x 8 rows: thread group threadIdx.x >> 3 transforms block `i` of the scan (when `active`) into
+// its place in its component's plane.  Every thread of the workgroup must call it.
+__device__ __forceinline__ void idct_blocks(const DecArgs& a, int b, const DecSample& s, const Geom& gm, bool active, int i, IdctLds& l) {
+  int (*ws)[8][9] = l.ws;
+  uint32_t* quant = l.quant;
+  int* sel = l.sel;
   const uint32_t* tab = a.tables + (size_t)s.table_set * TAB_WORDS;
   quant[threadIdx.x] = tab[TAB_Q + threadIdx.x];
   if (threadIdx.x < 3) sel[threadIdx.x] = (int)tab[TAB_SEL + threadIdx.x * 4] & 3;
   __syncthreads();
   const int lb = threadIdx.x >> 3, c = threadIdx.x & 7;
-  const int i = blockIdx.x * 32 + lb;
-  const bool active = i < nblocks;
   const int m = i / gm.nb, k = i - m * gm.nb;
   const int comp = k < gm.nluma ? 0 : k - gm.nluma + 1;
   if (active) {
@@ -621,19 +652,74 @@ __global__ void __launch_bounds__(256) dec_idct_kernel(const DecArgs a) {
   *reinterpret_cast<uint2*>(plane + (size_t)(by * 8 + c) * plane_stride(gm, s, comp) + bx * 8) = make_uint2(lo, hi);
 }
 
-// colour: grid = (ceil(max_h * max_w / 256), B), one pixel per thread
-__global__ void __launch_bounds__(256) dec_colour_kernel(const DecArgs a) {
+// idct: grid = (ceil(max_blocks / 32), B), 256 threads
+__global__ void __launch_bounds__(256) dec_idct_kernel(const DecArgs a) {
+  __shared__ IdctLds lds;
   const int b = blockIdx.y;
   const int32_t* info = a.info + (size_t)b * INFO;
   if (!info[I_OK] || a.status[b] != 0) return;
-  const DecSample s = a.samples[b];
-  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (pix >= (int64_t)s.h * s.w) return;
-  const int y = (int)(pix / s.w), x = (int)(pix - (int64_t)y * s.w);
+  const DecSample s = sample_of(a, b);
+  const Geom gm = geom_of(s);
+  const int nblocks = min(gm.nblocks, a.max_blocks);
+  if ((int)blockIdx.x * 32 >= nblocks) return;
+  const int i = blockIdx.x * 32 + (threadIdx.x >> 3);
+  idct_blocks(a, b, s, gm, i < nblocks, i, lds);
+}
+
+// the blocks a window needs, per dimension a first block and a count: of the luma plane those that intersect the rectangle; of a chroma
+// plane those that intersect the rectangle's chroma footprint grown by one sample on every side and clamped to the component
+struct WinBlocks {
+  int lx0, ly0, lnx, lny, cx0, cy0, cnx, cny;
+};
+__device__ __forceinline__ WinBlocks win_blocks(const DecSample& s, const Rect& r) {
+  WinBlocks w;
+  w.lx0 = r.x0 >> 3, w.ly0 = r.y0 >> 3;
+  w.lnx = ((r.x0 + r.rw - 1) >> 3) - w.lx0 + 1, w.lny = ((r.y0 + r.rh - 1) >> 3) - w.ly0 + 1;
+  w.cx0 = w.cy0 = w.cnx = w.cny = 0;
+  if (s.ncomp == 3) {
+    const int cw = (s.w + s.hs - 1) / s.hs, ch = (s.h + s.vs - 1) / s.vs;
+    const int xa = max(r.x0 / s.hs - 1, 0), xb = min((r.x0 + r.rw - 1) / s.hs + 1, cw - 1);
+    const int ya = max(r.y0 / s.vs - 1, 0), yb = min((r.y0 + r.rh - 1) / s.vs + 1, ch - 1);
+    w.cx0 = xa >> 3, w.cy0 = ya >> 3;
+    w.cnx = (xb >> 3) - w.cx0 + 1, w.cny = (yb >> 3) - w.cy0 + 1;
+  }
+  return w;
+}
+// an upper bound of the blocks a span of n samples touches, whatever its origin
+inline int64_t span_blocks(int64_t n) { return (n + 6) / 8 + 1; }
+
+// window idct: grid = (ceil(items / 32), B) for items = the most blocks a window of max_win_h x max_win_w needs, 256 threads
+__global__ void __launch_bounds__(256) dec_idct_window_kernel(const DecArgs a) {
+  __shared__ IdctLds lds;
+  const int b = blockIdx.y;
+  const int32_t* info = a.info + (size_t)b * INFO;
+  if (!info[I_OK] || a.status[b] != 0) return;
+  const DecSample s = sample_of(a, b);
+  const Geom gm = geom_of(s);
+  const WinBlocks w = win_blocks(s, rect_of(a, b, s));
+  const int nl = w.lnx * w.lny, nc = w.cnx * w.cny;             // each at most (65535 / 8 + 2)^2
+  if ((int64_t)blockIdx.x * 32 >= (int64_t)nl + 2 * nc) return;
+  const int j = blockIdx.x * 32 + (threadIdx.x >> 3);
+  bool active = j < nl + 2 * nc;
+  int i = 0;
+  if (active) {
+    if (j < nl) {
+      const int by = w.ly0 + j / w.lnx, bx = w.lx0 + j % w.lnx;
+      i = ((by / s.vs) * gm.mx + bx / s.hs) * gm.nb + (by % s.vs) * s.hs + bx % s.hs;
+    } else {
+      const int comp = 1 + (j - nl) / nc, q = (j - nl) % nc;
+      i = ((w.cy0 + q / w.cnx) * gm.mx + w.cx0 + q % w.cnx) * gm.nb + gm.nluma + comp - 1;
+    }
+    active = i < min(gm.nblocks, a.max_blocks);                 // always, for a record record_ok accepted: the guard of the loads
+  }
+  idct_blocks(a, b, s, gm, active, i, lds);
+}
+
+// one pixel (y, x) of the picture into the three bytes at `o`
+__device__ __forceinline__ void colour_pixel(const DecArgs& a, int b, const DecSample& s, int y, int x, unsigned char* o) {
   const Geom gm = geom_of(s);
   const unsigned char* p0 = a.planes + (size_t)b * 3 * a.plane_bytes;
   const int Y = p0[(size_t)y * plane_stride(gm, s, 0) + x];
-  unsigned char* o = a.out + s.out_offset + pix * 3;           // inside out: record_ok
   if (s.ncomp == 1) {
     o[0] = o[1] = o[2] = (unsigned char)Y;
     return;
@@ -666,6 +752,31 @@ __global__ void __launch_bounds__(256) dec_colour_kernel(const DecArgs a) {
   o[0] = (unsigned char)min(max(R, 0), 255);
   o[1] = (unsigned char)min(max(G, 0), 255);
   o[2] = (unsigned char)min(max(B, 0), 255);
+}
+
+// colour: grid = (ceil(max_h * max_w / 256), B), one pixel per thread
+__global__ void __launch_bounds__(256) dec_colour_kernel(const DecArgs a) {
+  const int b = blockIdx.y;
+  const int32_t* info = a.info + (size_t)b * INFO;
+  if (!info[I_OK] || a.status[b] != 0) return;
+  const DecSample s = sample_of(a, b);
+  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= (int64_t)s.h * s.w) return;
+  const int y = (int)(pix / s.w), x = (int)(pix - (int64_t)y * s.w);
+  colour_pixel(a, b, s, y, x, a.out + s.out_offset + pix * 3);          // inside out: record_ok
+}
+
+// window colour: grid = (ceil(max_win_h * max_win_w / 256), B), one pixel of the window per thread, dense [rh][rw][3] at out_offset
+__global__ void __launch_bounds__(256) dec_colour_window_kernel(const DecArgs a) {
+  const int b = blockIdx.y;
+  const int32_t* info = a.info + (size_t)b * INFO;
+  if (!info[I_OK] || a.status[b] != 0) return;
+  const DecSample s = sample_of(a, b);
+  const Rect r = rect_of(a, b, s);
+  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= (int64_t)r.rh * r.rw) return;
+  const int py = (int)(pix / r.rw), px = (int)(pix - (int64_t)py * r.rw);
+  colour_pixel(a, b, s, r.y0 + py, r.x0 + px, a.out + s.out_offset + pix * 3);      // inside out and inside the picture: record_ok
 }
 
 // the workspace's parts, in bytes from its start
@@ -703,53 +814,78 @@ extern "C" int64_t fp_jpeg_decode_workspace_bytes(int32_t B, int32_t max_h, int3
   DecLayout l;
   return layout_of(B, max_h, max_w, max_scan_bytes, subseq_bits, &l) ? l.total : -1;
 }
+extern "C" int32_t fp_jpeg_decode_window_sample_bytes(void) { return (int32_t)sizeof(DecWinSample); }
 
-extern "C" int fp_jpeg_decode(const uint8_t* scans, int64_t scan_bytes, const void* samples, const uint32_t* tables, int32_t n_table_sets,
-                              uint8_t* out, int64_t out_bytes, int32_t* status, int32_t B, int32_t max_h, int32_t max_w, int32_t max_scan_bytes,
-                              int32_t subseq_bits, int32_t max_rounds, void* workspace, int64_t workspace_bytes, fp_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  FP_REQUIRE(scans && samples && tables && out && status && scan_bytes > 0 && out_bytes > 0 && n_table_sets > 0, "fp_jpeg_decode: bad arguments");
-  FP_REQUIRE(max_rounds >= 1 && max_rounds <= 65536, "fp_jpeg_decode: max_rounds must be 1..65536");
-  DecLayout l;
-  FP_REQUIRE(layout_of(B, max_h, max_w, max_scan_bytes, subseq_bits, &l), "fp_jpeg_decode: bad sizes or too large (fp_jpeg_decode_workspace_bytes)");
-  FP_REQUIRE(workspace && workspace_bytes >= l.total, "fp_jpeg_decode: workspace too small (fp_jpeg_decode_workspace_bytes)");
+namespace {
+
+int check_launch(const char* who, const char* kernel) {
+  char what[64];
+  snprintf(what, sizeof(what), "%s(%s)", who, kernel);
+  return fp_check_launch(what);
+}
+
+// What fp_jpeg_decode and fp_jpeg_decode_window share: the checks of the batch-level arguments, the kernels' arguments, and the entropy half
+// -- the statuses cleared, then destuff, init, max_rounds x sync, place, write, dc -- after which the coefficients of every sample whose
+// status is 0 are complete.  sample_bytes: of one record; win_h = win_w = 0: whole pictures.
+int decode_entropy(const char* who, const uint8_t* scans, int64_t scan_bytes, const void* samples, int32_t sample_bytes, const uint32_t* tables,
+                   int32_t n_table_sets, uint8_t* out, int64_t out_bytes, int32_t* status, int32_t B, int32_t max_h, int32_t max_w, int32_t win_h,
+                   int32_t win_w, int32_t max_scan_bytes, int32_t subseq_bits, int32_t max_rounds, void* workspace, int64_t workspace_bytes,
+                   hipStream_t stream, DecArgs* args, DecLayout* layout) {
+  FP_REQUIRE(scans && samples && tables && out && status && scan_bytes > 0 && out_bytes > 0 && n_table_sets > 0, "%s: bad arguments", who);
+  FP_REQUIRE(max_rounds >= 1 && max_rounds <= 65536, "%s: max_rounds must be 1..65536", who);
+  DecLayout& l = *layout;
+  FP_REQUIRE(layout_of(B, max_h, max_w, max_scan_bytes, subseq_bits, &l), "%s: bad sizes or too large (fp_jpeg_decode_workspace_bytes)", who);
+  FP_REQUIRE(workspace && workspace_bytes >= l.total, "%s: workspace too small (fp_jpeg_decode_workspace_bytes)", who);
   FP_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)status & 3) == 0 && ((uintptr_t)tables & 3) == 0 && ((uintptr_t)samples & 7) == 0,
-             "fp_jpeg_decode: the workspace must be 16-byte aligned, the sample records 8-byte, the status and the tables 4-byte");
+             "%s: the workspace must be 16-byte aligned, the sample records 8-byte, the status and the tables 4-byte", who);
   unsigned char* ws = (unsigned char*)workspace;
-  DecArgs a;
-  a.scans = scans; a.scans_bytes = scan_bytes; a.samples = (const DecSample*)samples; a.tables = tables; a.out = out; a.out_bytes = out_bytes;
+  DecArgs& a = *args;
+  a.scans = scans; a.scans_bytes = scan_bytes; a.samples = (const unsigned char*)samples; a.tables = tables; a.out = out; a.out_bytes = out_bytes;
   a.status = status; a.info = (int32_t*)(ws + l.info); a.stream = ws + l.stream; a.entry = (unsigned long long*)(ws + l.entry);
   a.done = (unsigned long long*)(ws + l.done); a.exits = (unsigned long long*)(ws + l.exits); a.count = (uint32_t*)(ws + l.count);
   a.coef = (int16_t*)(ws + l.coef); a.planes = ws + l.planes; a.stream_stride = l.stream_stride; a.plane_bytes = l.plane_bytes;
   a.B = B; a.n_sets = n_table_sets; a.max_h = max_h; a.max_w = max_w; a.max_scan = max_scan_bytes; a.subseq_bits = subseq_bits;
   a.max_sub = l.max_sub; a.max_blocks = l.max_blocks; a.round = 0;
   a.stage_words = subseq_bits <= STAGE_MAX_BITS ? 2 * subseq_bits + 4 : 0;
+  a.sample_stride = sample_bytes; a.windowed = win_h > 0 ? 1 : 0; a.max_win_h = win_h; a.max_win_w = win_w;
   const unsigned stage_bytes = (unsigned)a.stage_words * 4;
   // the statuses (a fill, not a launch through fp_launch: like fp_jpeg_encode this call is not recorded into a launch plan)
   hipError_t e = hipMemsetAsync(status, 0, ((size_t)B + 1) * 4, stream);
-  if (e != hipSuccess) return fp_set_error((int)e, "fp_jpeg_decode: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fp_set_error((int)e, "%s: %s", who, hipGetErrorString(e));
   // the sample records live on the device: every kernel is launched for the largest sample and leaves early where it has nothing to do
   const unsigned groups = (unsigned)fp_ceil_div(l.max_sub, GROUP);
   fp_launch(dec_destuff_kernel, dim3(B), dim3(1024), 0, stream, a);
-  int rc = fp_check_launch("fp_jpeg_decode(destuff)");
+  int rc = check_launch(who, "destuff");
   if (rc) return rc;
   fp_launch(dec_init_kernel, dim3((unsigned)std::min<int64_t>(fp_ceil_div((int64_t)l.max_blocks * 8, 256 * 4), 4096), B), dim3(256), 0, stream, a);
-  rc = fp_check_launch("fp_jpeg_decode(init)");
+  rc = check_launch(who, "init");
   if (rc) return rc;
   for (int r = 0; r < max_rounds; ++r) {
     a.round = r;
     fp_launch(dec_sync_kernel, dim3(groups, B), dim3(GROUP), stage_bytes, stream, a);
-    rc = fp_check_launch("fp_jpeg_decode(sync)");
+    rc = check_launch(who, "sync");
     if (rc) return rc;
   }
   fp_launch(dec_place_kernel, dim3(B), dim3(256), 0, stream, a, (int)max_rounds);
-  rc = fp_check_launch("fp_jpeg_decode(place)");
+  rc = check_launch(who, "place");
   if (rc) return rc;
   fp_launch(dec_write_kernel, dim3(groups, B), dim3(GROUP), stage_bytes, stream, a);
-  rc = fp_check_launch("fp_jpeg_decode(write)");
+  rc = check_launch(who, "write");
   if (rc) return rc;
   fp_launch(dec_dc_kernel, dim3(B), dim3(256), 0, stream, a);
-  rc = fp_check_launch("fp_jpeg_decode(dc)");
+  return check_launch(who, "dc");
+}
+
+}  // namespace
+
+extern "C" int fp_jpeg_decode(const uint8_t* scans, int64_t scan_bytes, const void* samples, const uint32_t* tables, int32_t n_table_sets,
+                              uint8_t* out, int64_t out_bytes, int32_t* status, int32_t B, int32_t max_h, int32_t max_w, int32_t max_scan_bytes,
+                              int32_t subseq_bits, int32_t max_rounds, void* workspace, int64_t workspace_bytes, fp_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  DecArgs a;
+  DecLayout l;
+  int rc = decode_entropy("fp_jpeg_decode", scans, scan_bytes, samples, (int32_t)sizeof(DecSample), tables, n_table_sets, out, out_bytes, status, B,
+                          max_h, max_w, 0, 0, max_scan_bytes, subseq_bits, max_rounds, workspace, workspace_bytes, stream, &a, &l);
   if (rc) return rc;
   fp_launch(dec_idct_kernel, dim3((unsigned)fp_ceil_div(l.max_blocks, 32), B), dim3(256), 0, stream, a);
   rc = fp_check_launch("fp_jpeg_decode(idct)");
@@ -757,3 +893,27 @@ extern "C" int fp_jpeg_decode(const uint8_t* scans, int64_t scan_bytes, const vo
   fp_launch(dec_colour_kernel, dim3((unsigned)fp_ceil_div((int64_t)max_h * max_w, 256), B), dim3(256), 0, stream, a);
   return fp_check_launch("fp_jpeg_decode(colour)");
 }
+
+extern "C" int fp_jpeg_decode_window(const uint8_t* scans, int64_t scan_bytes, const void* samples, const uint32_t* tables, int32_t n_table_sets,
+                                     uint8_t* out, int64_t out_bytes, int32_t* status, int32_t B, int32_t max_h, int32_t max_w,
+                                     int32_t max_win_h, int32_t max_win_w, int32_t max_scan_bytes, int32_t subseq_bits, int32_t max_rounds,
+                                     void* workspace, int64_t workspace_bytes, fp_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  FP_REQUIRE(max_win_h >= 1 && max_win_w >= 1 && max_win_h <= max_h && max_win_w <= max_w,
+             "fp_jpeg_decode_window: max_win_h / max_win_w must be 1..max_h / 1..max_w");
+  DecArgs a;
+  DecLayout l;
+  int rc = decode_entropy("fp_jpeg_decode_window", scans, scan_bytes, samples, (int32_t)sizeof(DecWinSample), tables, n_table_sets, out, out_bytes,
+                          status, B, max_h, max_w, max_win_h, max_win_w, max_scan_bytes, subseq_bits, max_rounds, workspace, workspace_bytes,
+                          stream, &a, &l);
+  if (rc) return rc;
+  // the most blocks a window needs: luma over the rectangle, two chroma planes over a footprint of at most the rectangle plus two samples
+  const int64_t items = std::min<int64_t>(span_blocks(max_win_h) * span_blocks(max_win_w) + 2 * span_blocks(max_win_h + 2) * span_blocks(max_win_w + 2),
+                                          l.max_blocks);
+  fp_launch(dec_idct_window_kernel, dim3((unsigned)fp_ceil_div(items, 32), B), dim3(256), 0, stream, a);
+  rc = fp_check_launch("fp_jpeg_decode_window(idct)");
+  if (rc) return rc;
+  fp_launch(dec_colour_window_kernel, dim3((unsigned)fp_ceil_div((int64_t)max_win_h * max_win_w, 256), B), dim3(256), 0, stream, a);
+  return fp_check_launch("fp_jpeg_decode_window(colour)");
+}
+

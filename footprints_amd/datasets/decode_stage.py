@@ -23,7 +23,11 @@ device), `host_parser` (refused by the parser), `host_status` (decoded again aft
 The trainer's loaders (datasets/device_path.py, --device_decode) run the same protocol with the halves of `queue` apart, because their
 host half and their device half live on two threads: fill + pack_into on the staging thread -- pack_into writes the scans, records and
 table blocks into pinned buffers of the SLOT, which grow when a batch needs more, so that a warmed-up ring allocates no pinned memory per
-training step -- queue_packed on the thread that launches, finish when the batch is collected."""
+training step -- queue_packed on the thread that launches, finish when the batch is collected.
+
+The segmentation trainer's assembler (device_path.SegBatchAssembler) lays its batch out itself -- the rectangle of each frame that its
+crop window needs, not the frame -- and hands the stage a batch description with 'rects': pack_into then writes fp_jpeg_decode_window's
+records, `_decode` calls ops.jpeg_decode_window_packed, and `finish` repairs the rectangle of a frame the device turned down."""
 import ctypes as C
 import io
 import time
@@ -168,7 +172,9 @@ class DecodeStage:
         if not idx:
             return None
         smp = batch["samples"]
-        return ops.jpeg_decode_pack([smp[b]["bytes"] for b in idx], [smp[b]["info"] for b in idx], out_offsets=[batch["offsets"][b] for b in idx])
+        rects = [batch["rects"][b] for b in idx] if batch.get("rects") else None        # a batch of windows: fp_jpeg_decode_window's records
+        return ops.jpeg_decode_pack([smp[b]["bytes"] for b in idx], [smp[b]["info"] for b in idx], out_offsets=[batch["offsets"][b] for b in idx],
+                                    rects=rects)
 
     def pack(self, batch):
         """ops.jpeg_decode_pack of the batch's device samples, every array in pinned memory, or None"""
@@ -240,7 +246,8 @@ class DecodeStage:
 
     def _decode(self, s, pack, batch):
         nd = len(batch["on_device"])
-        ops.jpeg_decode_packed(pack, out=s["d_src"], out_bytes=batch["total"], status=s["d_status"][:nd + 1], device=self.device)
+        decode = ops.jpeg_decode_window_packed if "rects" in pack else ops.jpeg_decode_packed
+        decode(pack, out=s["d_src"], out_bytes=batch["total"], status=s["d_status"][:nd + 1], device=self.device)
         s["h_status"][:nd + 1].copy_(s["d_status"][:nd + 1], non_blocking=True)
 
     def _status(self, s, nd):
@@ -269,8 +276,11 @@ class DecodeStage:
             if frame.shape != (h, w, 3):
                 raise ValueError("%s: the header says %d x %d, Pillow decoded %r" % (smp.get("path", "sample %d" % b), h, w, frame.shape))
             off = batch["offsets"][b]
-            s["h_src"].numpy()[off:off + h * w * 3] = frame.reshape(-1)
-            self._upload(s, off, h * w * 3)
+            if batch.get("rects"):                          # the buffer holds the sample's rectangle alone: that is what is repaired
+                y0, x0, rh, rw = batch["rects"][b]
+                frame = frame[y0:y0 + rh, x0:x0 + rw]
+            s["h_src"].numpy()[off:off + frame.size] = frame.reshape(-1)
+            self._upload(s, off, frame.size)
             self.counters["host_status"] += 1
-        return dict(src=s["d_src"], total=batch["total"], records=s["d_rec"], n=batch["n"], max_h=batch["max_h"], max_w=batch["max_w"],
+        return dict(src=s["d_src"], total=batch["total"], records=s.get("d_rec"), n=batch["n"], max_h=batch["max_h"], max_w=batch["max_w"],
                     shapes=batch["shapes"], status=status)

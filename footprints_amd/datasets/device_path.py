@@ -480,11 +480,22 @@ class SegBatchAssembler(SlotAssembler):
     the frame that the window's resize taps reach and the rectangle of the label image that the composed NEAREST tables address;
     `launch` copies them and runs one or two windowed resizes (csrc/seg_reader.hip; two when _preprocess AND prepare_size resize), the
     flip + ColorJitter + ToTensor kernel of the Footprints trainer, and the label kernel.  max_src_hw = the staged rectangle of a sample
-    the pinned buffers are sized for at the start (batch_size of them; they grow when a batch needs more)."""
+    the pinned buffers are sized for at the start (batch_size of them; they grow when a batch needs more).
 
-    def __init__(self, batch_size, height, width, max_src_hw, slots=3, device="cuda", stream=None, check=False):
+    device_decode=True (--device_decode): the image of a sample may also be the FILE, as decode_stage.read_sample(path, True) returns it.
+    {'path', 'image', 'refused'} is a frame the reader thread decoded and is staged like any array.  For {'path', 'bytes', 'info'} the plan
+    is drawn from the header's size, the same offset of the packed source buffer is reserved and nothing is copied: fp_jpeg_decode_window
+    decodes the staged rectangle -- not the frame -- straight to that offset, so a device-decoded sample and a host-decoded one occupy the
+    same bytes, and records, tables and resizes are the same either way.  The protocol is decode_stage.DecodeStage's, as for
+    DeviceBatchAssembler: scans, records and table blocks in pinned buffers of the slot, everything launched optimistically, the status
+    read in `collect` -- a DeviceLoader iteration after the decode was queued -- and a frame the device turned down decoded by `decode`
+    (bytes -> uint8 [h, w, 3]; Pillow by default), its rectangle uploaded to its offset and the image half of the chain (resizes,
+    fp_assemble_images) queued once more; the label half never read the frames.  `counters`: device / host_parser / host_status."""
+
+    def __init__(self, batch_size, height, width, max_src_hw, slots=3, device="cuda", stream=None, check=False, device_decode=False, decode=None):
         from ..preprocessing.segmentation.datasets import plan as P
         self.P = P
+        self.device_decode = bool(device_decode)
         lib = _lib.load()
         assert lib.fp_aug_params_bytes() == C.sizeof(AugParams)
         assert lib.fp_resize_window_sample_bytes() == C.sizeof(_lib.ResizeWindowSample)
@@ -519,6 +530,22 @@ class SegBatchAssembler(SlotAssembler):
                 self._pair(s, "rec%d" % k, B * C.sizeof(_lib.ResizeWindowSample), torch.uint8)
                 self._pair(s, "tab%d" % k, 2 * B * C.sizeof(_lib.ResizeWindowTable), torch.uint8)
                 self._pair(s, "coef%d" % k, B * (H + W + 64) * 24, torch.int32)
+        self.stage = self._make_stage(decode) if self.device_decode else None
+        if self.device_decode:              # the decode stage's part of a slot; its pinned scan / record / table buffers come with the first batch
+            for s in self.slots:
+                self._pair(s, "status", B + 1, torch.int32)
+                s.update(decoded=self.stage._event(), batch=None, pack=None)
+
+    def _make_stage(self, decode):
+        """the owner of the decode protocol (pack, status copy, fallback); its own layout, whole frames one after the other, is not used:
+        `fill` lays out rectangles"""
+        from .decode_stage import DecodeStage, host_decode
+        return DecodeStage(self.B, self.H, self.W, None, self.device, decode=decode or host_decode)
+
+    @property
+    def counters(self):
+        """DecodeStage.counters: frames decoded by the device, refused by the parser, decoded again after a non-zero status"""
+        return dict(self.stage.counters) if self.stage is not None else dict(device=0, host_parser=0, host_status=0)
 
     def _pair(self, s, name, n, dtype):
         """a pinned host buffer and its device twin"""
@@ -541,7 +568,14 @@ class SegBatchAssembler(SlotAssembler):
 
     def draw(self, samples, is_train=True, rng=random):
         """the reference's draws for every sample of a batch, in batch order -> list of SegPlan (the `draw` of a DeviceLoader)"""
-        return [self.P.draw_seg_plan(name, img.shape[:2], (self.H, self.W), is_train, rng) for name, img, _ in samples]
+        return [self.P.draw_seg_plan(name, self._frame_hw(img), (self.H, self.W), is_train, rng) for name, img, _ in samples]
+
+    @staticmethod
+    def _frame_hw(img):
+        """the frame's (h, w): an array's shape, a decoded file sample's, or the header's of a file the device decodes"""
+        if isinstance(img, dict):
+            return tuple(img["image"].shape[:2]) if "image" in img else (int(img["info"]["h"]), int(img["info"]["w"]))
+        return tuple(img.shape[:2])
 
     def loader(self, source, is_train=True, rng=random):
         return DeviceLoader(source, self, is_train, rng, draw=self.draw)
@@ -559,12 +593,26 @@ class SegBatchAssembler(SlotAssembler):
                 nearest[(a, b)] = ops.nearest_index(a, b)
             return nearest[(a, b)]
 
+        # ---- file samples (device_decode): a frame the reader thread decoded is an array from here on; a file stays a dict
+        files = [None] * self.B
+        if any(isinstance(img, dict) for _, img, _ in samples):
+            if not self.device_decode:
+                raise ValueError("a sample's image is a file sample (decode_stage.read_sample): that needs device_decode=True")
+            samples = list(samples)
+            for b, (name, img, labels) in enumerate(samples):
+                if isinstance(img, dict):
+                    if "image" in img:
+                        self.stage.counters["host_parser"] += 1 if "refused" in img else 0
+                        samples[b] = (name, img["image"], labels)
+                    else:
+                        files[b] = img
         # ---- geometry first: what every sample needs staged, so that the pinned buffers can grow before anything is copied
         geo = []
         for b, ((name, img, labels), plan) in enumerate(zip(samples, plans)):
-            if plan.dataset != name or tuple(plan.src_hw) != img.shape[:2] or labels.shape[:2] != img.shape[:2] or tuple(plan.window[2:]) != (H, W):
+            hw = self._frame_hw(img)
+            if plan.dataset != name or tuple(plan.src_hw) != hw or labels.shape[:2] != hw or tuple(plan.window[2:]) != (H, W):
                 raise ValueError("sample %d: the plan was drawn for another sample" % b)
-            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or labels.dtype != np.uint8:
+            if (files[b] is None and (img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3)) or labels.dtype != np.uint8:
                 raise ValueError("sample %d: the image must be uint8 [h, w, 3] and the labels uint8" % b)
             ade = name == "ADE20K"
             if ade and (labels.ndim != 3 or labels.shape[2] != 3):
@@ -580,12 +628,15 @@ class SegBatchAssembler(SlotAssembler):
         lrec = (_lib.SegLabelSample * self.B)()
         lidx = np.empty(self.B * (H + W), np.int32)
         src_off = lab_off = 0
+        src_offsets = []
         mid_off = self.out_bytes
         for b, ((name, img, labels), (stages, (y0, x0, rh, rw), rows, cols, (r0, r1, c0, c1), lc)) in enumerate(zip(samples, geo)):
             # ---- image: its staged rectangle and the records of its one or two resizes
             n = rh * rw * 3
-            src_np[src_off:src_off + n].reshape(rh, rw, 3)[:] = img[y0:y0 + rh, x0:x0 + rw]
-            offset, rect = src_off, (y0, x0, rh, rw)
+            if files[b] is None:
+                src_np[src_off:src_off + n].reshape(rh, rw, 3)[:] = img[y0:y0 + rh, x0:x0 + rw]
+            offset, rect = src_off, (y0, x0, rh, rw)                # a file: the decoder writes this rectangle to this offset
+            src_offsets.append(src_off)
             src_off += n
             for k, st in enumerate(stages):
                 last = k == len(stages) - 1
@@ -608,6 +659,13 @@ class SegBatchAssembler(SlotAssembler):
                                           _lib.SEG_LABELLED_NONZERO if name == "cityscapes" else _lib.SEG_LABELLED_ONES, P.DATASETS.index(name))
             lab_off += lab.size
         s["used"] = {"src": src_off, "lab": lab_off}
+        if self.device_decode:              # the decode call's part: the files' scans, window records and table blocks into the slot's pinned buffers
+            shapes = [self._frame_hw(img) for _, img, _ in samples]
+            s["batch"] = dict(n=self.B, samples=[f if f is not None else {"image": img} for f, (_, img, _) in zip(files, samples)], shapes=shapes,
+                              offsets=src_offsets, rects=[g[1] for g in geo], total=src_off, max_h=max(h for h, _ in shapes),
+                              max_w=max(w for _, w in shapes), on_host=[b for b in range(self.B) if files[b] is None],
+                              on_device=[b for b in range(self.B) if files[b] is not None])
+            self.stage.pack_into(s, s["batch"])
         s["calls"] = []
         for k, call in enumerate(calls):
             if call.samples:
@@ -623,9 +681,47 @@ class SegBatchAssembler(SlotAssembler):
 
     def _launch(self, s, copies=True):
         """copies=False: the kernels alone, on what an earlier launch of the slot uploaded (benchmarks)"""
+        decoding = self.device_decode and s["pack"] is not None
         for name, n in s["used"].items():
-            if n and copies:
-                s["d_" + name][:n].copy_(s["h_" + name][:n], non_blocking=True)
+            if n and copies and not (decoding and name == "src"):
+                self._upload(s, name, 0, n)
+        if decoding and copies:
+            # the staged rectangles of the frames that arrived decoded (neighbours in one copy), then the decode of the others into the
+            # gaps and the copy of its status words, which `collect` reads; nothing waits
+            batch, runs = s["batch"], []
+            for b in batch["on_host"]:
+                off, (_, _, rh, rw) = batch["offsets"][b], batch["rects"][b]
+                if runs and runs[-1][1] == off:
+                    runs[-1][1] = off + rh * rw * 3
+                else:
+                    runs.append([off, off + rh * rw * 3])
+            for lo, hi in runs:
+                self.stage._upload(s, lo, hi - lo)
+            self.stage._decode(s, s["pack"], batch)
+            s["decoded"].record()
+        self._image_half(s)
+        self._label_half(s)
+
+    def _upload(self, s, name, lo, n):
+        s["d_" + name][lo:lo + n].copy_(s["h_" + name][lo:lo + n], non_blocking=True)
+
+    def collect(self, slot):
+        s = self.slots[slot]
+        if self.device_decode and s["batch"] is not None:
+            with ops.on_stream(self.stream):
+                self._repair(s)
+        return super().collect(slot)
+
+    def _repair(self, s):
+        """the decode was queued a whole step ago (DeviceLoader): its status is there.  What the device turned down goes through `decode`
+        now, its rectangle to its offset, and the image half of the slot's chain runs again; the label half never read the frames"""
+        def again():
+            self._image_half(s)
+            s["ready"].record(self.stream)
+        self.stage.collect(s, again)
+
+    def _image_half(self, s):
+        """the one or two windowed resizes and the flip + jitter + ToTensor kernel: everything that reads the packed source buffer"""
         buf = s["d_buf"]
         for k, n, n_tables, coeffs_len, msh, msw, mwh, mww in s["calls"]:
             # the first call reads the staged rectangles; the second one reads the first one's windows inside `buf`
@@ -634,6 +730,8 @@ class SegBatchAssembler(SlotAssembler):
                                  msh, msw, mwh, mww, check=self.check)
         _lib.check(_lib.load().fp_assemble_images(buf.data_ptr(), s["d_par"].data_ptr(), s["sums"].data_ptr(), s["image"].data_ptr(),
                                                   self.B, self.H, self.W, ops.stream()), "fp_assemble_images")
+
+    def _label_half(self, s):
         ops.seg_labels(s["d_lab"], s["used"]["lab"], s["d_lrec"], self.B, s["d_lidx"], s["used"]["lidx"], self.ground_ids, self.set_offsets,
                        self.H, self.W, ground_mask=s["ground_mask"], labelled_pix=s["labelled_pix"], status=s["status"], check=self.check)
 

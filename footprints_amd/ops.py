@@ -2622,19 +2622,24 @@ def _jpeg_table_block(info):
 _jpeg_table_blocks = {}
 
 
-def jpeg_decode_pack(files, infos=None, out_offsets=None, pinned=False):
+def jpeg_decode_pack(files, infos=None, out_offsets=None, pinned=False, rects=None):
     """host half of the decoder for files jpeg_parse accepted: their entropy-coded segments one after the other in one uint8 buffer
     (pinned=True: a pinned torch tensor's), the fp_jpeg_decode_sample records, and one table block per distinct set of tables and
     selectors (most files share the standard tables).  out_offsets: where each picture goes in the output (default: one after the other)
-    -> dict(scans, scan_bytes, records, tables, n_sets, B, shapes, out_bytes, max_h, max_w, max_scan)"""
+    -> dict(scans, scan_bytes, records, tables, n_sets, B, shapes, out_bytes, max_h, max_w, max_scan).
+    rects: one (y0, x0, rh, rw) per file -- the pack is then jpeg_decode_window_packed's: fp_jpeg_decode_window_sample records, the output
+    holds the windows (dense [rh][rw][3]), and the dict also has rects, max_win_h and max_win_w.  A rectangle is not checked here: the device
+    refuses, per sample, one that is empty or not inside its picture."""
     import numpy as np
     infos = [jpeg_parse(f) for f in files] if infos is None else infos
     if not files or any(not i["device"] for i in infos):
         raise ValueError("footprints_amd.ops.jpeg_decode_pack: needs at least one file, and only files jpeg_parse accepts")
+    if rects is not None and len(rects) != len(files):
+        raise ValueError("footprints_amd.ops.jpeg_decode_pack: one rectangle per file")
     total = sum(i["scan_bytes"] for i in infos)
     holder = torch.empty(total, dtype=torch.uint8).pin_memory() if pinned else None
     scans = holder.numpy() if pinned else np.empty(total, dtype=np.uint8)
-    rec = (_lib.JpegDecodeSample * len(files))()
+    rec = ((_lib.JpegDecodeSample if rects is None else _lib.JpegDecodeWindowSample) * len(files))()
     sets, blocks, at, out_at = {}, [], 0, 0
     for b, (f, i) in enumerate(zip(files, infos)):
         key = (i["tq"], i["td"], i["ta"], tuple(sorted(i["quant"].items())), tuple(sorted(i["huff"].items())))
@@ -2648,12 +2653,26 @@ def jpeg_decode_pack(files, infos=None, out_offsets=None, pinned=False):
             blocks.append(block)
         scans[at:at + i["scan_bytes"]] = np.frombuffer(f, dtype=np.uint8, count=i["scan_bytes"], offset=i["scan_offset"])
         off = out_at if out_offsets is None else int(out_offsets[b])
-        rec[b] = _lib.JpegDecodeSample(at, off, i["scan_bytes"], i["h"], i["w"], i["ncomp"], i["hs"], i["vs"], sets[key], 0)
+        fields = (at, off, i["scan_bytes"], i["h"], i["w"], i["ncomp"], i["hs"], i["vs"], sets[key], 0)
+        if rects is None:
+            rec[b] = _lib.JpegDecodeSample(*fields)
+            out_at += i["h"] * i["w"] * 3
+        else:
+            y0, x0, rh, rw = (int(v) for v in rects[b])
+            rec[b] = _lib.JpegDecodeWindowSample(*fields, y0, x0, rh, rw)
+            out_at += max(rh, 0) * max(rw, 0) * 3
         at += i["scan_bytes"]
-        out_at += i["h"] * i["w"] * 3
-    return dict(scans=holder if pinned else scans, scan_bytes=total, records=np.frombuffer(bytes(rec), dtype=np.uint8).copy(),
+    pack = dict(scans=holder if pinned else scans, scan_bytes=total, records=np.frombuffer(bytes(rec), dtype=np.uint8).copy(),
                 tables=np.concatenate(blocks), n_sets=len(blocks), B=len(files), shapes=[(i["h"], i["w"]) for i in infos], out_bytes=out_at,
                 max_h=max(i["h"] for i in infos), max_w=max(i["w"] for i in infos), max_scan=max(i["scan_bytes"] for i in infos))
+    if rects is not None:
+        pack.update(jpeg_window_bounds(rects, pack["max_h"], pack["max_w"]), rects=[tuple(int(v) for v in r) for r in rects])
+    return pack
+
+
+def jpeg_window_bounds(rects, max_h, max_w):
+    """max_win_h / max_win_w of a call: the largest rectangle, kept inside 1..max_h / 1..max_w (a rectangle beyond is refused on the device)"""
+    return dict(max_win_h=min(max(1, max(int(r[2]) for r in rects)), max_h), max_win_w=min(max(1, max(int(r[3]) for r in rects)), max_w))
 
 
 def jpeg_decode_packed(pack, out=None, out_bytes=None, subseq_bits=None, max_rounds=None, status=None, device="cuda", want_info=False):
@@ -2662,6 +2681,42 @@ def jpeg_decode_packed(pack, out=None, out_bytes=None, subseq_bits=None, max_rou
     and jpeg_encode_packed read -> (out, shapes, status): status int32 device [B + 1], per sample and their maximum: 0 decoded, 1 record
     turned down, 2 not settled within max_rounds launches, 3 corrupt stream; a sample with a non-zero status wrote nothing.  Does not
     wait for the device.  want_info=True appends the kernels' counters, int32 device [B, 8] (include/footprints_hip.h)."""
+    if "rects" in pack:
+        raise ValueError("footprints_amd.ops.jpeg_decode_packed: the pack holds rectangles (jpeg_decode_window_packed)")
+    return _jpeg_decode_launch(pack, out, out_bytes, subseq_bits, max_rounds, status, device, want_info)
+
+
+def jpeg_decode_window_packed(pack, rects=None, out=None, out_offsets=None, out_bytes=None, subseq_bits=None, max_rounds=None, status=None,
+                              device="cuda", want_info=False):
+    """jpeg_decode_packed for one rectangle (y0, x0, rh, rw) per file (fp_jpeg_decode_window): `out` receives the bytes the whole picture
+    has at [y0:y0+rh, x0:x0+rw], dense [rh][rw][3] at the sample's offset, and nothing else -> (out, windows [(rh, rw)], status).  pack:
+    jpeg_decode_pack(files, rects=...) -- every array may be pinned, nothing is rebuilt -- or a plain pack with `rects` (and out_offsets,
+    default: one window after the other) given here, from which the window records are written.  A rectangle that is empty or not inside
+    its picture gives that sample status 1; the others are unaffected.  Does not wait for the device."""
+    if rects is not None:
+        import numpy as np
+        if "rects" in pack or len(rects) != pack["B"] or (out_offsets is not None and len(out_offsets) != pack["B"]):
+            raise ValueError("footprints_amd.ops.jpeg_decode_window_packed: one rectangle (and offset) per file, for a pack without rectangles")
+        plain = (_lib.JpegDecodeSample * pack["B"]).from_buffer_copy(np.asarray(pack["records"]).tobytes())
+        rec = (_lib.JpegDecodeWindowSample * pack["B"])()
+        at = 0
+        for b, r in enumerate(rects):
+            y0, x0, rh, rw = (int(v) for v in r)
+            p = plain[b]
+            rec[b] = _lib.JpegDecodeWindowSample(p.scan_offset, at if out_offsets is None else int(out_offsets[b]), p.scan_bytes, p.h, p.w, p.ncomp,
+                                                 p.hs, p.vs, p.table_set, 0, y0, x0, rh, rw)
+            at += max(rh, 0) * max(rw, 0) * 3
+        pack = dict(pack, records=np.frombuffer(bytes(rec), dtype=np.uint8).copy(), rects=[tuple(int(v) for v in r) for r in rects],
+                    out_bytes=at if out_offsets is None else max(int(o) + max(int(r[2]), 0) * max(int(r[3]), 0) * 3 for o, r in zip(out_offsets, rects)),
+                    tables=np.asarray(pack["tables"]), **jpeg_window_bounds(rects, pack["max_h"], pack["max_w"]))
+    elif "rects" not in pack:
+        raise ValueError("footprints_amd.ops.jpeg_decode_window_packed: no rectangles, neither in the pack nor in the call")
+    got = _jpeg_decode_launch(pack, out, out_bytes, subseq_bits, max_rounds, status, device, want_info)
+    return (got[0], [(r[2], r[3]) for r in pack["rects"]]) + tuple(got[2:])
+
+
+def _jpeg_decode_launch(pack, out, out_bytes, subseq_bits, max_rounds, status, device, want_info):
+    """jpeg_decode_packed and jpeg_decode_window_packed behind their checks: a pack with 'rects' goes to fp_jpeg_decode_window"""
     lib = _lib.load()
     B = pack["B"]
     subseq_bits = JPEG_DECODE_SUBSEQ_BITS if subseq_bits is None else int(subseq_bits)
@@ -2685,9 +2740,15 @@ def jpeg_decode_packed(pack, out=None, out_bytes=None, subseq_bits=None, max_rou
     if need < 0:
         raise RuntimeError("footprints_amd.ops.jpeg_decode_packed: bad sizes, or too large")
     ws = workspace(need, d_scans.device, "jpeg_decode")
-    _lib.check(lib.fp_jpeg_decode(_chk(d_scans, "scans"), int(pack["scan_bytes"]), _chk(d_rec, "samples"), _chk(d_tab, "tables"), pack["n_sets"],
-                                  _chk(out, "out"), out_bytes, _chk(status, "status"), B, pack["max_h"], pack["max_w"], pack["max_scan"],
-                                  subseq_bits, max_rounds, ws.data_ptr(), ws.numel(), stream()), "fp_jpeg_decode")
+    if "rects" in pack:
+        _lib.check(lib.fp_jpeg_decode_window(_chk(d_scans, "scans"), int(pack["scan_bytes"]), _chk(d_rec, "samples"), _chk(d_tab, "tables"),
+                                             pack["n_sets"], _chk(out, "out"), out_bytes, _chk(status, "status"), B, pack["max_h"], pack["max_w"],
+                                             pack["max_win_h"], pack["max_win_w"], pack["max_scan"], subseq_bits, max_rounds, ws.data_ptr(),
+                                             ws.numel(), stream()), "fp_jpeg_decode_window")
+    else:
+        _lib.check(lib.fp_jpeg_decode(_chk(d_scans, "scans"), int(pack["scan_bytes"]), _chk(d_rec, "samples"), _chk(d_tab, "tables"), pack["n_sets"],
+                                      _chk(out, "out"), out_bytes, _chk(status, "status"), B, pack["max_h"], pack["max_w"], pack["max_scan"],
+                                      subseq_bits, max_rounds, ws.data_ptr(), ws.numel(), stream()), "fp_jpeg_decode")
     if want_info:
         return out, pack["shapes"], status, ws[:B * 32].view(torch.int32).view(B, 8).clone()
     return out, pack["shapes"], status
@@ -2724,6 +2785,47 @@ def jpeg_decode(files, subseq_bits=None, max_rounds=None, return_status=False):
     for n, f in enumerate(files):
         if arrays[n] is None:
             arrays[n] = _jpeg_host_decode(f)
+    return (arrays, statuses) if return_status else arrays
+
+
+def jpeg_decode_window(files, rects, subseq_bits=None, max_rounds=None, return_status=False):
+    """`np.asarray(PIL.Image.open(f).convert("RGB"))[y0:y0+rh, x0:x0+rw]` for every file (bytes) and its rectangle (y0, x0, rh, rw), byte
+    for byte: jpeg_decode's division of work, with the device decoding the rectangles alone.  A rectangle that is empty or not inside its
+    picture is a ValueError.  WAITS for the device.  return_status=True -> (arrays, statuses) as jpeg_decode."""
+    files = [bytes(f) for f in files]
+    rects = [tuple(int(v) for v in r) for r in rects]
+    if len(rects) != len(files):
+        raise ValueError("footprints_amd.ops.jpeg_decode_window: one rectangle per file")
+
+    def inside(n, h, w):
+        y0, x0, rh, rw = rects[n]
+        if rh < 1 or rw < 1 or y0 < 0 or x0 < 0 or y0 + rh > h or x0 + rw > w:
+            raise ValueError("footprints_amd.ops.jpeg_decode_window: file %d: the rectangle %r is empty or not inside the picture of %d x %d"
+                             % (n, rects[n], h, w))
+
+    infos = [jpeg_parse(f) for f in files]
+    on_device = [n for n, i in enumerate(infos) if i["device"]]
+    for n in on_device:
+        inside(n, infos[n]["h"], infos[n]["w"])
+    arrays, statuses = [None] * len(files), [-1] * len(files)
+    if on_device:
+        pack = jpeg_decode_pack([files[n] for n in on_device], [infos[n] for n in on_device], rects=[rects[n] for n in on_device])
+        out, windows, status = jpeg_decode_window_packed(pack, subseq_bits=subseq_bits, max_rounds=max_rounds)
+        status = status.cpu().numpy()               # waits
+        host = out.cpu().numpy() if (status[:-1] == 0).any() else None
+        at = 0
+        for j, n in enumerate(on_device):
+            rh, rw = windows[j]
+            statuses[n] = int(status[j])
+            if statuses[n] == 0:
+                arrays[n] = host[at:at + rh * rw * 3].reshape(rh, rw, 3).copy()
+            at += rh * rw * 3
+    for n, f in enumerate(files):
+        if arrays[n] is None:
+            frame = _jpeg_host_decode(f)
+            inside(n, frame.shape[0], frame.shape[1])
+            y0, x0, rh, rw = rects[n]
+            arrays[n] = frame[y0:y0 + rh, x0:x0 + rw].copy()
     return (arrays, statuses) if return_status else arrays
 
 

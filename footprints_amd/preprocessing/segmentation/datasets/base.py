@@ -1,7 +1,8 @@
 """File readers of the segmentation trainer: what is left on the host of the reference's dataset classes
 (footprints/preprocessing/segmentation/datasets/*_dataset.py) -- decoding.  A reader yields (dataset name, image uint8 [h, w, 3],
 labels uint8) at the NATIVE size; every resize, crop, flip, jitter and label lookup happens on the device
-(footprints_amd/datasets/device_path.SegBatchAssembler)."""
+(footprints_amd/datasets/device_path.SegBatchAssembler).  With device_decode the image is the file itself and baseline JPEGs are decoded
+there too; footprints_amd/datasets/training.ThreadedBatchSource is BatchSource reading ahead on --num_workers threads."""
 import random
 
 import numpy as np
@@ -18,11 +19,22 @@ def pil_loader(path):
 class SegFileReader:
     name = None
 
-    def __init__(self, datapath, filenames):
-        self.datapath, self.filenames = datapath, list(filenames)
+    def __init__(self, datapath, filenames, device_decode=False):
+        """device_decode (--device_decode): the image of a sample is what datasets/decode_stage.read_sample(path, True) returns --
+        {'path', 'bytes', 'info'} for a baseline JPEG, which SegBatchAssembler(device_decode=True) decodes on the device, or
+        {'path', 'image', 'refused'} for a file the parser refuses (every PNG of Cityscapes, progressive JPEGs, ...), decoded by Pillow on
+        the reader's thread.  Labels are read as ever."""
+        self.datapath, self.filenames, self.device_decode = datapath, list(filenames), bool(device_decode)
 
     def __len__(self):
         return len(self.filenames)
+
+    def read_image(self, path):
+        """the decoded frame, or under device_decode the file sample"""
+        if self.device_decode:
+            from ....datasets.decode_stage import read_sample
+            return read_sample(path, True)
+        return pil_loader(path)
 
     def load_image(self, index):
         raise NotImplementedError

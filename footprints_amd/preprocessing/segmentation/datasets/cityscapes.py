@@ -9,7 +9,7 @@ class CityscapesReader(SegFileReader):
 
     def load_image(self, index):
         folder, city, frame = self.filenames[index].split()
-        return pil_loader(os.path.join(self.datapath, "leftImg8bit", folder, city, frame + "_leftImg8bit.png"))
+        return self.read_image(os.path.join(self.datapath, "leftImg8bit", folder, city, frame + "_leftImg8bit.png"))
 
     def load_labels(self, index):                   # fine ground truth, else coarse; all channels are equal, the device reads one
         folder, city, frame = self.filenames[index].split()

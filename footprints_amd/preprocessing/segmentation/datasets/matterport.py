@@ -3,7 +3,7 @@ import os
 
 import numpy as np
 
-from .base import SegFileReader, pil_loader
+from .base import SegFileReader
 
 
 class MatterportReader(SegFileReader):
@@ -14,8 +14,8 @@ class MatterportReader(SegFileReader):
 
     def load_image(self, index):
         scan, pos, height, direction = self._parts(index)
-        return pil_loader(os.path.join(self.datapath, "sample_dataset/v1/scans", scan, scan, "matterport_color_images",
-                                       "{}_i{}_{}.jpg".format(pos, height, direction)))
+        return self.read_image(os.path.join(self.datapath, "sample_dataset/v1/scans", scan, scan, "matterport_color_images",
+                                            "{}_i{}_{}.jpg".format(pos, height, direction)))
 
     def load_labels(self, index):
         scan, pos, height, direction = self._parts(index)

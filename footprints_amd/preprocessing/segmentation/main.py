@@ -1,5 +1,6 @@
 """python -m footprints_amd.preprocessing.segmentation.main: train the ground-segmentation network on device-assembled batches (TensorBoard
-files under <log_path>/<model_name>/{train,val} every `--log_freq` steps unless `--no_summaries` is given), or
+files under <log_path>/<model_name>/{train,val} every `--log_freq` steps unless `--no_summaries` is given; the files of upcoming batches
+read on `--num_workers` threads, and with `--device_decode` the baseline JPEGs among them decoded on the device), or
 (`--mode inference`) run the trained network over a dataset's train and val frames and write the ground-probability maps that
 ground_truth_generation reads (reference: footprints/preprocessing/segmentation/main.py)."""
 from .options import SegmentationOptions

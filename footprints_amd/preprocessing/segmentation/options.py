@@ -22,7 +22,9 @@ class SegmentationOptions:
         p.add_argument("--batch_size", help="number of images in each batch", type=int, default=12)
         p.add_argument("--val_batches", help="number of validation batches to average over", type=int, default=10)
         p.add_argument("--lr", help="the learning rate", type=float, default=1e-4)
-        p.add_argument("--num_workers", help="the number of workers for dataloading", type=int, default=4)
+        p.add_argument("--num_workers", type=int, default=4,
+                       help="the number of threads that read the files of upcoming batches (validation: at most 2); 0: one batch at a time "
+                            "on the staging thread")
         p.add_argument("--model_name", help="the name of the model for saving", type=str, default="model")
         p.add_argument("--log_path", help="the path to save logs and trained models to", type=str, default="./logs")
         p.add_argument("--no_summaries", action="store_true",
@@ -36,8 +38,9 @@ class SegmentationOptions:
         p.add_argument("--device_jpeg", action="store_true",
                        help="with --save_test_visualisations: encode the pictures on the GPU (same files as Pillow writes)")
         p.add_argument("--device_decode", action="store_true",
-                       help="inference mode: decode baseline JPEG frames on the GPU, one batch ahead of the network (same files; "
-                            "what the decoder does not take goes to Pillow)")
+                       help="decode baseline JPEG frames on the GPU; what the decoder does not take (PNG, progressive files, ...) goes to "
+                            "Pillow, and the results are the same either way.  Inference mode: one batch ahead of the network.  Training "
+                            "mode: inside batch assembly, only the rectangle of a frame that its crop window needs")
 
     def parse(self, args=None):
         self.options = self.parser.parse_args(args)

@@ -56,23 +56,33 @@ class Trainer:
 
     def create_dataloaders(self):
         """train.py:64-101 with the file readers of datasets/ and the device path: ConcatDataset of the chosen datasets, shuffled, so
-        one batch mixes datasets.  max_src_hw is Cityscapes' cropped frame, the largest of the three."""
+        one batch mixes datasets.  max_src_hw is Cityscapes' cropped frame, the largest of the three.  The samples of upcoming batches
+        are read on --num_workers threads (train; min(2, num_workers) for validation, as the Footprints trainer's loaders): the shuffle,
+        the batch boundaries and the `random` stream are BatchSource's; num_workers <= 0 keeps the plain BatchSource, which reads a batch's
+        files one after the other on the staging thread.  --device_decode: the readers hand over files and the assemblers decode baseline
+        JPEGs on the device (datasets/device_path.SegBatchAssembler)."""
         import yaml
         from ...datasets.device_path import SegBatchAssembler
+        from ...datasets.training import ThreadedBatchSource
         from .datasets import READERS, BatchSource
         with open(self.opt.config_path) as fh:
             config = yaml.safe_load(fh)
+        device_decode = bool(getattr(self.opt, "device_decode", False))
+        num_workers = int(getattr(self.opt, "num_workers", 0))
         loaders = []
-        for split, is_train in (("train", True), ("val", False)):
+        for split, is_train, workers in (("train", True, num_workers), ("val", False, min(2, num_workers))):
             readers = []
             for dataset in self.opt.training_datasets:
                 with open(os.path.join("splits", dataset, split + ".txt")) as fh:
                     files = fh.read().splitlines()
                 if dataset == "matterport" and is_train:
                     files = files[:5000]
-                readers.append(READERS[dataset](config[dataset]["dataset"], files))
-            source = BatchSource(readers, self.opt.batch_size, shuffle=True)
-            asm = SegBatchAssembler(self.opt.batch_size, self.opt.height, self.opt.width, max_src_hw=(1280, 2048))
+                readers.append(READERS[dataset](config[dataset]["dataset"], files, device_decode=device_decode))
+            if workers > 0:
+                source = ThreadedBatchSource(readers, self.opt.batch_size, shuffle=True, rng=random, num_workers=workers)
+            else:
+                source = BatchSource(readers, self.opt.batch_size, shuffle=True)
+            asm = SegBatchAssembler(self.opt.batch_size, self.opt.height, self.opt.width, max_src_hw=(1280, 2048), device_decode=device_decode)
             loader = asm.loader(source, is_train, random)
             loader.dataset = source.dataset
             loaders.append(loader)
@@ -122,6 +132,11 @@ class Trainer:
                                                                                            self.history[-1]["train"]["loss"],
                                                                                            self.history[-1]["val"]["loss"]))
             self.step += 1
+        for name, loader in (("train", self.train_loader), ("val", self.val_loader)):
+            if getattr(getattr(loader, "asm", None), "device_decode", False):            # --device_decode: where the frames were decoded
+                c = loader.counters
+                print("Epoch {} -- {} frames decoded so far: device {}, host (parser) {}, host (status) {}".format(
+                    self.epoch, name, c["device"], c["host_parser"], c["host_status"]))
         self.save_model()
 
     def run_validation(self, batches=10):

@@ -900,6 +900,32 @@ int64_t fp_jpeg_decode_workspace_bytes(int32_t B, int32_t max_h, int32_t max_w, 
 int fp_jpeg_decode(const uint8_t* scans, int64_t scan_bytes, const void* samples, const uint32_t* tables, int32_t n_table_sets, uint8_t* out,
                    int64_t out_bytes, int32_t* status, int32_t B, int32_t max_h, int32_t max_w, int32_t max_scan_bytes, int32_t subseq_bits,
                    int32_t max_rounds, void* workspace, int64_t workspace_bytes, fp_stream_t stream);
+/* One rectangle of a picture: fp_jpeg_decode_sample's fields, then the rectangle. */
+typedef struct fp_jpeg_decode_window_sample {
+  int64_t scan_offset;
+  int64_t out_offset;  /* of the WINDOW's first byte in the output; dense uint8 [rh][rw][3] */
+  int32_t scan_bytes;
+  int32_t h, w;        /* of the picture */
+  int32_t ncomp;
+  int32_t hs, vs;
+  int32_t table_set;
+  int32_t reserved;
+  int32_t y0, x0;      /* the rectangle's first row and column in the picture */
+  int32_t rh, rw;      /* its size: 1 <= rh <= h - y0, 1 <= rw <= w - x0 */
+} fp_jpeg_decode_window_sample;
+int32_t fp_jpeg_decode_window_sample_bytes(void);
+/* fp_jpeg_decode for one rectangle per sample: writes the bytes fp_jpeg_decode's picture has at [y0 : y0 + rh, x0 : x0 + rw], densely at
+ * out_offset, and nothing else.  samples: B fp_jpeg_decode_window_sample records on the device.  The entropy half is fp_jpeg_decode's (a scan
+ * has no random access); the inverse DCT runs on the blocks the rectangle needs -- the luma blocks that intersect it, the chroma blocks
+ * that intersect its chroma footprint grown by one sample on every side -- and the colour pass on the rectangle's pixels: both grids are
+ * sized by max_win_h x max_win_w (1..max_h, 1..max_w), the largest rectangle of the call.  The upsampler's edge rules are the picture's.
+ * The workspace is fp_jpeg_decode_workspace_bytes' (the component planes stay frame-sized) and begins with the same counters.  status as
+ * fp_jpeg_decode; 1 also for a rectangle that is empty, reaches outside its picture or is larger than max_win_h x max_win_w.  A sample
+ * with a non-zero status writes nothing, and the other samples are unaffected.  Does not wait for the device. */
+int fp_jpeg_decode_window(const uint8_t* scans, int64_t scan_bytes, const void* samples, const uint32_t* tables, int32_t n_table_sets,
+                          uint8_t* out, int64_t out_bytes, int32_t* status, int32_t B, int32_t max_h, int32_t max_w, int32_t max_win_h,
+                          int32_t max_win_w, int32_t max_scan_bytes, int32_t subseq_bits, int32_t max_rounds, void* workspace,
+                          int64_t workspace_bytes, fp_stream_t stream);
 
 /* ---- pyramid pooling of the ground-segmentation network (footprints/preprocessing/segmentation/network.py:174-207) ---- */
 /* nn.AdaptiveAvgPool2d(P) (network.py:180,188): y[N][P][P][C] = window means of x[N][H][W][C]; windows floor(i*H/P) .. ceil((i+1)*H/P) */
