@@ -332,8 +332,10 @@ def sigmoid_to_depth(disp, min_depth=0.1, max_depth=100):
 
 
 def _bce_logits(x, t):
-    """BCEWithLogitsLoss(reduction='none') closed form (losses.py:114)."""
-    return torch.clamp(x, min=0) - x * t + torch.log1p(torch.exp(-torch.abs(x)))
+    """BCEWithLogitsLoss(reduction='none') closed form (losses.py:114).  max(x, 0) is written (x + |x|) / 2: the same bits forward and
+    backward for x != 0, and at x == 0 autograd then gives the loss's true derivative sigmoid(0) - t = 1/2 - t (clamp's one-sided
+    derivative gave 1 - t there)."""
+    return 0.5 * (x + torch.abs(x)) - x * t + torch.log1p(torch.exp(-torch.abs(x)))
 
 
 def loss_manager(predictions, targets, depth_range=(0.1, 100), prior=0.25):

@@ -50,6 +50,20 @@ def loss_blocks(npix):
     return max(1, min(2048, ceil_div(npix, 256 * 4)))
 
 
+SEG_BLK = 64              # csrc/seg_loss.hip:15: partial-sum workgroups per image
+
+
+def seg_loss_workspace(B, H, W):
+    """csrc/seg_loss.hip:141 fp_seg_loss_workspace: four full-resolution gradient planes, then per image SEG_BLK labelled-pixel partials and
+    SEG_BLK x 4 loss partials"""
+    return (4 * B * H * W + B * SEG_BLK * 5) * 4
+
+
+def seg_down_grid(B, h, w):
+    """csrc/seg_loss.hip:174: one thread per low-resolution element, capped at 4096 workgroups"""
+    return min(4096, ceil_div(B * h * w, 256))
+
+
 def ew_grid(total, cap=8192):
     """csrc/bn_pool.hip:339 and csrc/loss_adam_misc.hip:11 ew_grid (same rule, default cap 8192); csrc/psp.hip:150 grid_for is the
     same rule with cap 4096"""
@@ -150,6 +164,27 @@ def colsum_regime(M, C):
     return frozenset([("colsum", ceil_div(M, R * 16) > 512, nblk * R > M, 256 % C4 != 0, _final_lanes(nblk))])
 
 
+def loss_regime(B, H, W):
+    """("loss", capped, passes, ragged_last_pass, final_lanes_loop) for loss_kernel + loss_final_kernel (loss_adam_misc.hip:33,85):
+    passes = grid-stride iterations of the busiest thread as 1 or 2 (2 = more than one); ragged = the last pass does not fill the grid
+    (for one pass: the last workgroup is not full)"""
+    npix = B * H * W
+    nblk = loss_blocks(npix)
+    passes = ceil_div(npix, nblk * 256)
+    ragged = (npix % (nblk * 256) != 0) if passes > 1 else (npix % 256 != 0)
+    return frozenset([("loss", ceil_div(npix, 1024) > 2048, min(passes, 2), ragged, _final_lanes(nblk))])
+
+
+def seg_loss_regime(B, H, W):
+    """("seg_loss", passes, ragged_last_pass) of seg_valid_kernel / seg_loss_kernel (seg_loss.hip:37,57: SEG_BLK x 256 threads stride over one
+    image) and ("seg_down", scale index, capped) per gradient map of the decoder's sizes H / 8 .. H / 1 (seg_loss.hip:113,174)"""
+    HW = H * W
+    passes = ceil_div(HW, SEG_BLK * 256)
+    ragged = (HW % (SEG_BLK * 256) != 0) if passes > 1 else (HW % 256 != 0)
+    down = [("seg_down", i, ceil_div(B * (H // s) * (W // s), 256) > 4096) for i, s in enumerate((8, 4, 2, 1))]
+    return frozenset([("seg_loss", min(passes, 2), ragged)] + down)
+
+
 # ---- chain lengths -----------------------------------------------------------------------------------------------------------------
 # L = the longest chain of dependent float32 additions behind one reduced output: iterations of one thread, then the in-LDS merges, then
 # the shuffle tree, then the final kernel's per-lane loop (and its tree).  Stages a kernel runs in double are counted all the same: the
@@ -183,6 +218,19 @@ def head_chain(Cin):
     """head_fwd_kernel (head.hip:79-88): 9 taps x 4 channels in one lane, then log2(Q) shuffle steps, then the bias"""
     Q = Cin // 4
     return 36 + int(math.log2(Q)) + 1
+
+
+def loss_chain(npix):
+    """loss_kernel + loss_final_kernel (loss_adam_misc.hip:33,85): one thread's pixels, the wave tree (6), the four waves in LDS (3), the final
+    kernel's lane loop over the partial blocks and its tree (6)"""
+    nblk = loss_blocks(npix)
+    return ceil_div(npix, nblk * 256) + 6 + 3 + ceil_div(nblk, 64) + 6
+
+
+def seg_loss_chain(HW):
+    """seg_loss_kernel + seg_final_kernel (seg_loss.hip:51,88): one thread's pixels, the wave tree (6), the four waves in LDS as two pairs
+    (2), then SEG_BLK partial blocks added serially by one thread (64)"""
+    return ceil_div(HW, SEG_BLK * 256) + 6 + 2 + SEG_BLK
 
 
 def sum_bound(L, k, abs_terms, result):

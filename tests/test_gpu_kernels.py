@@ -768,6 +768,7 @@ def test_loss_against_oracle_and_golden():
     ops, L = _ops()
     from oracle import restatement as R
     from tests.golden.digest import load
+    from tests.parity import chan_relerr
     from tests.test_oracle_golden import g4_inputs
     gold = load("g4_loss")
     preds, batch = g4_inputs()
@@ -777,8 +778,9 @@ def test_loss_against_oracle_and_golden():
     dp = [torch.empty_like(p) for p in pd]
     ops.loss_fwd_bwd(pd, tg, out, dp)
     np.testing.assert_allclose(out.cpu().double().numpy(), gold["loss.values"], rtol=2e-5)
-    for k, d in zip(R.SCALES, dp):
-        check(d, torch.from_numpy(gold["loss.dpred" + k]), "dpred" + k, 1e-5)
+    for k, d in zip(R.SCALES, dp):       # per channel: the depth channels' gradients are hundreds of times the BCE channels'
+        errs = chan_relerr(d, torch.from_numpy(gold["loss.dpred" + k]))
+        assert max(errs) <= 1e-5, "dpred%s: per-channel rel-to-max errors %s" % (k, errs)
     # a second, larger, case against the oracle (forward only + backward)
     B, H, W = 3, 40, 72
     batch = R.make_batch(B, H, W, tag="lossbig")
@@ -794,7 +796,8 @@ def test_loss_against_oracle_and_golden():
     ref = np.array([float(losses[k]) for k in R.LOSS_KEYS])
     np.testing.assert_allclose(out.cpu().double().numpy(), ref, rtol=2e-5)
     for k, d in zip(R.SCALES, dp):
-        check(d, pr[k].grad, "dpred big " + k, 1e-5)
+        errs = chan_relerr(d, pr[k].grad)
+        assert max(errs) <= 1e-5, "dpred big %s: per-channel rel-to-max errors %s" % (k, errs)
     out2 = torch.empty(21, device="cuda")
     ops.loss_fwd_bwd(pd, {k: v.cuda() for k, v in batch.items()}, out2, None)      # forward-only, bit-stable
     assert torch.equal(out, out2)

@@ -191,6 +191,11 @@ def test_segmentation_loss_kernel_against_oracle(B, H, W):
     lm[0, : H // 2] = 0.0                                    # an image with a large unlabelled region
     ref = R.seg_loss(outs, gm.double(), lm.double(), H, W)
     ref.backward()
+    with torch.no_grad():       # the per-scale means of the per-image losses: what the Evaluator tracks under ground_loss_<scale>
+        per = [(F.binary_cross_entropy_with_logits(F.interpolate(o, size=(H, W), mode="bilinear", align_corners=False).squeeze(1), gm.double(),
+                                                   reduction="none") * lm.double()).sum(dim=[1, 2]) / (lm.double().sum(dim=[1, 2]) + 1e-7) for o in outs]
+    want = {"ground_loss_%d" % s: float(per[s].mean()) for s in range(4)}
+    assert abs(sum(want.values()) / 4 - float(ref.detach())) <= 1e-12
     for sliced in (False, True):
         if sliced:      # [B,2,h,w] buffers, channel 0 handed out
             bufs = [torch.zeros(B, 2, o.shape[2], o.shape[3], device="cuda") for o in outs]
@@ -208,4 +213,6 @@ def test_segmentation_loss_kernel_against_oracle(B, H, W):
             assert err <= 2e-6, err
         tr = sl.tracked()
         assert set(tr) == {"loss"} | {"ground_loss_%d" % s for s in range(4)} and abs(float(tr["loss"]) - float(ref)) <= 1e-6 * abs(float(ref))
+        for key, w in want.items():
+            assert abs(float(tr[key]) - w) <= 1e-6 * abs(w), (key, float(tr[key]), w)
         assert sl.tracked() == {}

@@ -7,6 +7,8 @@ bounds those tests use tight enough to see one dropped row?
    when a launch rule changes, this is the test that says which small shape stopped standing in for the product's.
 3. For every reduction case the float64 reference is recomputed without the last row and without the last workgroup's rows; one
    reduced output at least must move by more than ten times its bound (tests/step_kernel_refs.py), else the bound could not see it.
+4. The two training losses: the launch arithmetic of csrc/seg_loss.hip against fp_seg_loss_workspace, and the regimes the trainers' shapes
+   run (Footprints 12x192x640, 4x512x640, 12x512x640; segmentor 12x192x640) against the cases of tests/test_gpu_losses.py.
 """
 import ctypes
 
@@ -151,6 +153,40 @@ def test_loss_blocks_match_library():
     for B, H, W in [(1, 1, 1), (1, 32, 32), (1, 32, 33), (12, 192, 640), (4, 512, 640), (3, 40, 72), (20, 192, 640), (2, 1024, 1024),
                     (2, 1024, 1025)] + [(2, h, 37) for h in _sweep(5, 30, 1, 40000)]:
         assert lib.fp_loss_workspace(B, H, W) == LR.loss_blocks(B * H * W) * 16 * 4, (B, H, W)
+
+
+def test_seg_loss_launch_matches_library():
+    lib = _lib()
+    for B, H, W in [(1, 8, 8), (2, 16, 24), (3, 64, 96), (2, 136, 128), (12, 192, 640), (2, 512, 1032)] + [(3, h, 41) for h in _sweep(6, 20, 1, 20000)]:
+        assert lib.fp_seg_loss_workspace(B, H, W) == LR.seg_loss_workspace(B, H, W), (B, H, W)
+    assert LR.SEG_BLK * 256 == 16384 and LR.seg_down_grid(12, 192, 640) == 4096 and LR.seg_down_grid(2, 136, 128) == 136
+
+
+# ---- the two losses: which regimes the trainers' shapes run, and that the GPU cases of tests/test_gpu_losses.py reach them ----------
+LOSS_WORKLOAD = [(12, 192, 640), (4, 512, 640), (12, 512, 640)]       # Footprints trainer: KITTI, Matterport, Matterport at the KITTI batch size
+SEG_LOSS_WORKLOAD = [(12, 192, 640)]                                  # segmentation trainer
+
+
+def test_loss_regimes_of_the_trainers_occur_in_the_gpu_cases():
+    from tests import loss_refs as LF
+    assert LR.loss_regime(12, 192, 640) == LR.loss_regime(4, 512, 640) == frozenset([("loss", False, 2, False, 2)])
+    assert LR.loss_regime(12, 512, 640) == frozenset([("loss", True, 2, True, 2)])          # 3840 blocks wanted, capped at 2048
+    have = set().union(*(LR.loss_regime(c.B, c.H, c.W) for c in LF.FP_CASES))
+    for shape in LOSS_WORKLOAD:
+        missing = LR.loss_regime(*shape) - have
+        assert not missing, "Footprints loss at %s runs %s: no GPU case does (cases reach %s)" % (shape, sorted(missing), sorted(have))
+    # the structural edges the cases add on purpose: one partial workgroup; lanes of the final kernel without a partial block
+    assert ("loss", False, 1, True, 0) in have and LR.loss_blocks(2 * 160 * 208) == 65 and LR.ceil_div(2 * 1024 * 1030, 1024) == 2060
+    assert (2 * 1024 * 1030) % (2048 * 256) != 0            # under the cap some threads take five trips, the others four
+    # an image boundary inside a workgroup: 1024 x 1030 pixels are a multiple of 256, so the capped case does not have one; 40 x 72 does
+    assert (1024 * 1030) % 256 == 0 and (40 * 72) % 256 != 0 and any(c.B > 1 and (c.H, c.W) == (40, 72) for c in LF.FP_CASES)
+    assert LR.seg_loss_regime(12, 192, 640) == frozenset([("seg_loss", 2, True), ("seg_down", 0, False), ("seg_down", 1, False),
+                                                          ("seg_down", 2, False), ("seg_down", 3, True)])
+    seg = set().union(*(LR.seg_loss_regime(c.B, c.H, c.W) for c in LF.SEG_CASES if c.backward))
+    for shape in SEG_LOSS_WORKLOAD:
+        missing = LR.seg_loss_regime(*shape) - seg
+        assert not missing, "segmentation loss at %s runs %s: no GPU case does (cases reach %s)" % (shape, sorted(missing), sorted(seg))
+    assert ("seg_loss", 1, True) in seg and ("seg_loss", 1, False) in seg
 
 
 def test_issue_table_rows():
