@@ -74,6 +74,22 @@ SCALE_KEYS = ("1/8", "1/4", "1/2", "1/1")
 _ALL_SCALES = frozenset(range(4))
 
 
+def trainable_ranges(offsets, total, flags):
+    """maximal [lo, hi) runs of adjacent trainable slots of the flat buffers, each slot with its padding to 16 bytes (slot i spans
+    offsets[i] .. offsets[i + 1], the last one .. total): what the optimiser updates and what a frozen set leaves out.  Both ends are
+    multiples of 4; an all-trainable model gives the single range [0, total)."""
+    out = []
+    ends = list(offsets[1:]) + [total]
+    for lo, hi, t in zip(offsets, ends, flags):
+        if not t or hi == lo:
+            continue
+        if out and out[-1][1] == lo:
+            out[-1] = (out[-1][0], hi)
+        else:
+            out.append((lo, hi))
+    return out
+
+
 class ConvRec:
     """One convolution: parameters + packed copies for the implicit-GEMM kernels (self.lay)."""
 
@@ -92,6 +108,7 @@ class ConvRec:
         self.folded = None   # ... of the BN-folded weights self.fw: a second `fwd` role (Engine._build_fold)
         self.gw = None    # gradient views (flat grad buffer)
         self.gb = None
+        self.tw = self.tb = True     # weight / bias trainable (Engine.sync_frozen; tb is False without a bias)
 
     def facts(self):
         return WL.Facts(self.Cout, self.Cin, self.K, self.stride, self.stem, self.head, self.up2)
@@ -108,6 +125,7 @@ class BNRec:
         self.invstd = torch.empty(self.C, device=device)
         self.gg = None
         self.gb = None
+        self.tw = self.tb = True     # weight / bias trainable (Engine.sync_frozen)
 
 
 class BlockRec:
@@ -268,6 +286,11 @@ class Engine:
             self.decoders = [DecoderRec("mask_decoder", model.mask_decoder), DecoderRec("depth_decoder", model.depth_decoder)]
         self._bufs = {}
         self.amax = AmaxBook(dev)
+        self._enc_bns = [self.bn0] + [b for blk in self.blocks for b in (blk.bn1, blk.bn2, blk.bnd) if b is not None]
+        self._frozen_key = None     # requires_grad of every live parameter as sync_frozen last saw it
+        self.first_stage = 0        # lowest encoder stage (0 = stem + bn0 .. 4) that holds a trainable tensor; 5: the encoder is wholly frozen
+        self.adam_ranges = None     # trainable_ranges of the current frozen set
+        self._saving = False
         self._flatten()
         self._alloc_packed()
         # 1-channel heads (segmentation) run through the Cin -> 2 head kernels with a zero second filter: padded copies of the
@@ -344,6 +367,8 @@ class Engine:
             total += (p.numel() + 3) // 4 * 4
         self.flat_param = torch.zeros(total, device=self.device)
         self.flat_grad = torch.zeros(total, device=self.device)
+        self._frozen_key = None
+        self._fold_ready = False
         ops.bump_alloc_generation()
         self.offsets = offs
         self.grad_views = []
@@ -389,6 +414,59 @@ class Engine:
         self.weights_dirty = True
         self._fold_ready = False
 
+    # ------------------------------------------------------------------------------------------------
+    # fine-tuning: BatchNorm mode and frozen parameters
+    # ------------------------------------------------------------------------------------------------
+    def bn_training(self):
+        """the mode of the encoder's BatchNorm layers, read from the modules themselves (PyTorch's rule: `model.train(); model.encoder.eval()`
+        runs them on their running statistics): True = batch statistics, False = frozen statistics; a mixture raises"""
+        on = [r for r in self._enc_bns if r.bn.training]
+        if len(on) == len(self._enc_bns):
+            return True
+        if not on:
+            return False
+        off = next(r for r in self._enc_bns if not r.bn.training)
+        raise RuntimeError("footprints_amd: the encoder's BatchNorm layers are in mixed modes (%s is in train mode, %s in eval mode); the HIP "
+                           "engine runs all of them on batch statistics or all of them on their running statistics -- "
+                           "model.freeze_bn_stats() / model.encoder.eval() switch every one" % (on[0].name, off.name))
+
+    def frozen_key(self):
+        return tuple(p.requires_grad for p in self.live_params)
+
+    def sync_frozen(self):
+        """derive the frozen set from the parameters' requires_grad flags (once per change; True: it changed): per-record flags, the lowest
+        trainable encoder stage, the optimiser's ranges -- and the frozen slots of the flat gradient buffer are zero-filled, so that an
+        all-reduce over them carries zeros.  A change drops recorded launch plans."""
+        key = self.frozen_key()
+        if key == self._frozen_key:
+            return False
+        flag = dict(zip(self.live_names, key))
+        convs = self.all_convs() + [hd for d in self.decoders for hd in d.heads]
+        for c in convs:
+            c.tw, c.tb = flag[c.name + ".weight"], (c.b is not None and flag[c.name + ".bias"])
+        for r in self._enc_bns:
+            r.tw, r.tb = flag[r.name + ".weight"], flag[r.name + ".bias"]
+        stages = [int(n[len("encoder.layer")]) for n, t in flag.items() if t and n.startswith("encoder.layer")]
+        self.first_stage = min(stages) if stages else 5
+        total = self.flat_grad.numel()
+        self.adam_ranges = trainable_ranges(self.offsets, total, key)
+        p = 0
+        for lo, hi in self.adam_ranges + [(total, total)]:       # the complement: frozen slots with their padding
+            if lo > p:
+                ops.fill(self.flat_grad[p:lo], 0.0)
+            p = hi
+        if self._frozen_key is not None:
+            ops.bump_alloc_generation()
+        self._fold_ready = False
+        self._frozen_key = key
+        return True
+
+    def mark_updated(self):
+        """the optimiser wrote the trainable parameters: the packed copies are stale, the BN-folded encoder only if the encoder can train"""
+        self.weights_dirty = True
+        if self.first_stage <= 4:
+            self._fold_ready = False
+
     def params_alias_flat(self):
         p0 = self.live_params[0]
         return p0.data_ptr() == self.flat_param.data_ptr()
@@ -422,6 +500,9 @@ class Engine:
         key = (self.flat_param.data_ptr(), bool(self.inference_bf16x2))
         if not (force or self.weights_dirty or vers != self._versions or key != self._pack_table_key):
             return
+        # a wholly frozen encoder whose weights nobody wrote (the optimiser's update of the decoders is what made the copies stale) keeps its
+        # BN-folded copies: fine-tuning the decoders on the folded forward would otherwise rebuild them every step
+        keep_fold = self.first_stage > 4 and not force and vers == self._versions and key == self._pack_table_key
         if self._pack_table is None or self._pack_table_key != key:
             # (re)building the device-resident job tables allocates and fills small tensors from pageable host memory: like a first touch in
             # _need32 it drains the device first (start-up and the step after a first touch only; never under stream capture)
@@ -479,7 +560,8 @@ class Engine:
                 if hd.pad:
                     hd.w2[0].copy_(hd.w.data[0])
                     hd.b2[0:1].copy_(hd.b.data)
-        self._fold_ready = False
+        if not keep_fold:
+            self._fold_ready = False
         self._versions = vers
         self.weights_dirty = False
         self._w32_fresh = set(self._w32_used)       # exactly the lazy layouts the tables above contain
@@ -522,6 +604,9 @@ class Engine:
             ops.bn_train_stats(z.view(M, rec.C), bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var,
                                bn.num_batches_tracked, rec.mean, rec.invstd, rec.scale, rec.shift, bn.eps,
                                bn.momentum if bn.momentum is not None else 0.1)
+        elif self._saving:       # frozen statistics under a backward pass: the running statistics where the backward reads the batch's
+            ops.bn_eval_coeffs_saved(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, rec.scale, rec.shift, rec.mean, rec.invstd,
+                                     bn.eps)
         else:
             ops.bn_eval_coeffs(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, rec.scale, rec.shift, bn.eps)
 
@@ -547,6 +632,9 @@ class Engine:
         the convolutions' weight gradients (_wgrad) -- nothing on the data-gradient chain reads it, and at full resolution it is 160 us of
         HBM-bound work that used to sit in front of the first big data gradient of the backward pass (ordered trace, profiles/round5_*).
         The caller keeps x and dzl untouched until the join at the end of Engine.backward: dzl lives in a buffer of its own per scale."""
+        if not (hd.tw or hd.tb):
+            return self._skip_side(side if _HEAD_WGRAD_SIDE else None, True)
+
         def launch():
             if not hd.pad:
                 return ops.head_wgrad(x, dzl, hd.gw, hd.gb, accumulate=acc)
@@ -558,6 +646,12 @@ class Engine:
                 hd.gw.copy_(hd.gw2[0:1])
                 hd.gb.copy_(hd.gb2[0:1])
         self._on_side(side if _HEAD_WGRAD_SIDE else None, launch)
+
+    def _skip_side(self, side, fork):
+        """a frozen tensor's weight-gradient launch is left out; the fork it would have made stays, because the next launch on `side` may
+        have been told that it shares this one (fork=False)"""
+        if side is not None and fork:
+            ops.event_wait(side, self._record(ops.current_stream()))
 
     def _on_side(self, side, launch, fork=True):
         """launch() on the stream `side`, ordered behind everything queued on the current stream (fork=False: the caller has just forked
@@ -841,6 +935,8 @@ class Engine:
         if not self.params_alias_flat():
             self._flatten()
             self.weights_dirty = True
+        self.sync_frozen()
+        self._saving = save_for_backward
         self.refresh_packed(overlap=True)
         if _HP:
             self.amax.begin()
@@ -850,7 +946,9 @@ class Engine:
         buf = self.buf
         if training:
             self._fold_ready = False          # running statistics are about to change
-        folded = (not training) and self.fold_eval and not save_for_backward
+        # inference, and the decoder-only fine-tuning recipe (frozen statistics, no trainable encoder tensor): the decoders' backward reads
+        # nothing of the encoder but S["feats"]
+        folded = (not training) and self.fold_eval and (not save_for_backward or self.first_stage > 4)
         if folded:
             self._encoder_eval_folded(image, N, H, W, S)
             return self._decoders_forward(S, outputs, save_for_backward)
@@ -963,7 +1061,8 @@ class Engine:
         for (P, c, off), pooled in zip(dec.psp.blocks, D["psp"]):
             dred = ops.bilinear_ac_bwd(dcat, buf("g.%s.psp.dred%d" % (dec.name, P), (N, P, P, 128)), off)
             dw = ops.make_desc(N, P, P, P, P, 512, 0, 128, 1, 1, 0, L.GATHER_FWD_ZERO)
-            ops.conv_wgrad(dw, pooled, None, dred, c.gw, accumulate=acc)
+            if c.tw:
+                ops.conv_wgrad(dw, pooled, None, dred, c.gw, accumulate=acc)
             dd = ops.make_desc(N, P, P, P, P, 128, 0, 512, 1, 1, 0, L.GATHER_DGRAD_ZERO)
             dpool = ops.conv_igemm(dd, dred, None, self._need32(c.lay.dgrad.f32), buf("g.%s.psp.dpool%d" % (dec.name, P), (N, P, P, 512)))
             ops.adaptive_avgpool_bwd(dpool, dF4, accumulate=True)
@@ -1018,6 +1117,8 @@ class Engine:
         fork=False: no new event -- the caller has just forked `side` from this stream (the previous _wgrad call) and launched nothing since.
         Every fork is a barrier packet on the launching stream: ~6 us in which the data-gradient chain does not advance (ordered trace,
         profiles/round4_notes.md), so the two weight gradients of a residual block share one."""
+        if not (c.tw or c.tb):
+            return self._skip_side(side, fork)
         d = ops.make_desc(N, OH, OW, IH, IW, C0, C1, c.Cout, c.K, c.stride, c.pad, gather)
         split = _WBF3 and src1 is None and ops.conv_wgrad_bf3_supported(d)
         # fp16-pair operands: both amax slots are settled on THIS stream (the producers', or a reduction here) before the side stream forks
@@ -1036,6 +1137,8 @@ class Engine:
         """weight (+bias) gradient of a conv over cat[nearest_x2(low), skip]: upsampled half by output phase, skip half as a
         channel slice of the same gradient tensor; shapes the phase kernel does not take keep the fused-gather kernel.  fork: see _wgrad."""
         H, W = 2 * hl, 2 * wl
+        if not (c.tw or c.tb):
+            return self._skip_side(side, fork)
         if c.up2 is None or not ops.up2_phase_wgrad_supported(N, hl, wl, C0, c.Cout):
             d_lo = ops.make_desc(N, H, W, H, W, C0, 0, c.Cout, 3, 1, 1, L.GATHER_FWD_REFLECT_UP2)
             d_sk = ops.make_desc(N, H, W, H, W, C1, 0, c.Cout, 3, 1, 1, L.GATHER_FWD_REFLECT) if C1 else None
@@ -1112,12 +1215,12 @@ class Engine:
         S = self.saved
         if S is None:
             raise RuntimeError("backward called without a saved forward")
-        if not S["training"]:
-            raise RuntimeError("backward through eval-mode BatchNorm is not supported by the HIP engine")
-        if not all(p.requires_grad for p in self.live_params):
-            frozen = [n for n, p in zip(self.live_names, self.live_params) if not p.requires_grad]
-            raise RuntimeError("footprints_amd: frozen parameters (requires_grad=False) are not supported by the fused backward / "
-                               "Adam -- they would be trained silently: %s ..." % frozen[:3])
+        self.sync_frozen()
+        K = self.first_stage           # stages below K hold no trainable tensor: nothing of their backward is launched
+        if K <= 4 and not S["blocks"]:
+            raise RuntimeError("footprints_amd: this forward ran the BN-folded encoder (no trainable encoder tensor, frozen statistics) and "
+                               "kept none of its activations; an encoder parameter was made trainable since -- run the forward again")
+        frozen_stats = not S["training"]
         N = S["N"]
         feats, dims = S["feats"], S["dims"]
         buf = self.buf
@@ -1145,8 +1248,26 @@ class Engine:
             """the BatchNorm-backward side output (ops.BnOut) for a tile data gradient at (h_, w_, C_): a pair of partial sums per tile and channel"""
             part = buf(name, (self._partials_cap(N, h_, w_, C_, 2),))
             return part, ops.bn_bwd_out(part, z.view(-1, C_), rec.mean, rec.invstd)
-        for i in range(nblk - 1, -1, -1):
+
+        # BatchNorm backward of one layer: batch statistics (S["training"]) or frozen running statistics -- rec.mean / rec.invstd hold
+        # whichever the forward normalised with; the sums go only to trainable affine parameters
+        def bn_bwd(rec, dy, ro, z, dz, g_out=None, amax_out=None):
+            fn = ops.bn_bwd_frozen if frozen_stats else ops.bn_bwd
+            fn(dy, ro, z, rec.mean, rec.invstd, rec.bn.weight.data, dz, rec.gg if rec.tw else None, rec.gb if rec.tb else None,
+               g_out=g_out, accumulate=accumulate, amax_out=amax_out)
+
+        def bn_bwd_part(rec, g_, z, dz, part, npart, amax_out=None):
+            gg, gb = rec.gg if rec.tw else None, rec.gb if rec.tb else None
+            if frozen_stats:
+                ops.bn_bwd_frozen_partials(g_, rec.invstd, rec.bn.weight.data, dz, gg, gb, part, npart, accumulate=accumulate, amax_out=amax_out)
+            else:
+                ops.bn_bwd_partials(g_, z, rec.mean, rec.invstd, rec.bn.weight.data, dz, gg, gb, part, npart, accumulate=accumulate,
+                                    amax_out=amax_out)
+        layer_of = [feat_of_block[min(k for k in feat_of_block if k >= i)] for i in range(nblk)]
+        first_live = next((i for i in range(nblk) if layer_of[i] >= K), nblk)      # (nblk: the loop below is not entered)
+        for i in range(nblk - 1, first_live - 1, -1):
             blk, B = self.blocks[i], S["blocks"][i]
+            feeds = K == 0 or i > first_live      # the gradient wrt this block's input has a consumer (not so below the lowest trainable stage)
             h, w, hin, win = B["h"], B["w"], B["hin"], B["win"]
             C, Cin = blk.Cout, blk.Cin
             M = N * h * w
@@ -1156,12 +1277,11 @@ class Engine:
                 # the next block's conv1 data gradient stored g = (its sum + the residual gradient) * (out > 0) and the two per-channel sums
                 # of this BatchNorm's backward with it: no reduction pass, no separate g
                 g = dout
-                ops.bn_bwd_partials(g.view(M, C), B["z2"].view(M, C), blk.bn2.mean, blk.bn2.invstd, blk.bn2.bn.weight.data, dz2.view(M, C),
-                                    blk.bn2.gg, blk.bn2.gb, dnext_part[0], dnext_part[1], accumulate=accumulate, amax_out=self._sink_slot(dz2))
+                bn_bwd_part(blk.bn2, g.view(M, C), B["z2"].view(M, C), dz2.view(M, C), dnext_part[0], dnext_part[1], amax_out=self._sink_slot(dz2))
             else:
                 g = buf("g.g", (N, h, w, C))
-                ops.bn_bwd(dout.view(M, C), B["out"].view(M, C), B["z2"].view(M, C), blk.bn2.mean, blk.bn2.invstd, blk.bn2.bn.weight.data,
-                           dz2.view(M, C), blk.bn2.gg, blk.bn2.gb, g_out=g.view(M, C), accumulate=accumulate, amax_out=self._sink_slot(dz2))
+                bn_bwd(blk.bn2, dout.view(M, C), B["out"].view(M, C), B["z2"].view(M, C), dz2.view(M, C), g_out=g.view(M, C),
+                       amax_out=self._sink_slot(dz2))
             dnext_part = None
             self._sink_done(dz2)
             ev_ds = None
@@ -1169,21 +1289,22 @@ class Engine:
             dgd = ops.make_desc(N, hin, win, h, w, C, 0, Cin, 3, blk.stride, 1, L.GATHER_DGRAD_ZERO)
 
             def conv1_dgrad_acc():       # on top of the previous layer's feature gradient (which already holds the decoders' gradients)
+                if not feeds:
+                    return
                 dgd.epi = L.EPI_ACCUM
                 self._cv(dgd, dz1, blk.c1.lay.dgrad, dF[feat_of_block[i - 1]])
 
             def downsample(between=None):       # BN backward, weight gradient, [between], data gradient into the previous layer's feature gradient
                 dzd = buf("g.dzd.%d" % i, (N, h, w, C))
-                ops.bn_bwd(g.view(M, C), None, B["zd"].view(M, C), blk.bnd.mean, blk.bnd.invstd, blk.bnd.bn.weight.data,
-                           dzd.view(M, C), blk.bnd.gg, blk.bnd.gb, accumulate=accumulate,
-                           amax_out=self._sink_slot(dzd) if blk.ds.hp_ig else None)
+                bn_bwd(blk.bnd, g.view(M, C), None, B["zd"].view(M, C), dzd.view(M, C), amax_out=self._sink_slot(dzd) if blk.ds.hp_ig else None)
                 if blk.ds.hp_ig:
                     self._sink_done(dzd)
                 self._wgrad(blk.ds, L.GATHER_FWD_ZERO, B["x"], None, dzd, N, h, w, hin, win, Cin, 0, accumulate, side)
                 if between is not None:
                     between()
-                d1 = ops.make_desc(N, hin, win, h, w, C, 0, Cin, 1, blk.stride, 0, L.GATHER_DGRAD_ZERO, epi=L.EPI_ACCUM)
-                self._cv(d1, dzd, blk.ds.lay.dgrad, dF[feat_of_block[i - 1]])
+                if feeds:
+                    d1 = ops.make_desc(N, hin, win, h, w, C, 0, Cin, 1, blk.stride, 0, L.GATHER_DGRAD_ZERO, epi=L.EPI_ACCUM)
+                    self._cv(d1, dzd, blk.ds.lay.dgrad, dF[feat_of_block[i - 1]])
             if blk.ds is not None and self.concurrent and _DS_AUX:
                 # on the aux stream, its data gradient FIRST; the main branch's conv1 data gradient accumulates on top after the join (fixed order)
                 ops.event_wait(self.aux, self._record(ops.current_stream()))
@@ -1201,16 +1322,12 @@ class Engine:
                 part, bo = bnb_arm("bnb.part1", h, w, C, B["z1"], blk.bn1)
                 self._cv(d2, dz2, blk.c2.lay.dgrad, da1, actsrc=B["a1"], bn_out=bo)
                 if bo.nblk > 0:
-                    ops.bn_bwd_partials(da1.view(M, C), B["z1"].view(M, C), blk.bn1.mean, blk.bn1.invstd, blk.bn1.bn.weight.data,
-                                        dz1.view(M, C), blk.bn1.gg, blk.bn1.gb, part, bo.nblk, accumulate=accumulate,
-                                        amax_out=self._sink_slot(dz1))
+                    bn_bwd_part(blk.bn1, da1.view(M, C), B["z1"].view(M, C), dz1.view(M, C), part, bo.nblk, amax_out=self._sink_slot(dz1))
                 else:                                   # split grid: the mask is applied, the sums are not there
-                    ops.bn_bwd(da1.view(M, C), None, B["z1"].view(M, C), blk.bn1.mean, blk.bn1.invstd, blk.bn1.bn.weight.data,
-                               dz1.view(M, C), blk.bn1.gg, blk.bn1.gb, accumulate=accumulate, amax_out=self._sink_slot(dz1))
+                    bn_bwd(blk.bn1, da1.view(M, C), None, B["z1"].view(M, C), dz1.view(M, C), amax_out=self._sink_slot(dz1))
             else:
                 self._cv(d2, dz2, blk.c2.lay.dgrad, da1)
-                ops.bn_bwd(da1.view(M, C), B["a1"].view(M, C), B["z1"].view(M, C), blk.bn1.mean, blk.bn1.invstd, blk.bn1.bn.weight.data,
-                           dz1.view(M, C), blk.bn1.gg, blk.bn1.gb, accumulate=accumulate, amax_out=self._sink_slot(dz1))
+                bn_bwd(blk.bn1, da1.view(M, C), B["a1"].view(M, C), B["z1"].view(M, C), dz1.view(M, C), amax_out=self._sink_slot(dz1))
             self._sink_done(dz1)
             if _WGRAD_PAIR_FORK:                         # both weight gradients of the block behind ONE fork (dz2 has its own buffer per block)
                 if _HP_WGRAD and side is not None:       # a missing amax slot is reduced on THIS stream: before the fork, not between the two launches
@@ -1227,9 +1344,10 @@ class Engine:
                     downsample(between=conv1_dgrad_acc)
                 dnext = None
             elif first_of_layer:                        # layer1 block 0: input is the max-pool output
-                dpool = buf("g.dpool", (N, hin, win, Cin))
-                self._cv(dgd, dz1, blk.c1.lay.dgrad, dpool, addend=g)
-                ops.maxpool_bwd(dpool, self._bufs["pool.argmax"][:dpool.numel()].view(dpool.shape), dF[0], accumulate=True)
+                if feeds:
+                    dpool = buf("g.dpool", (N, hin, win, Cin))
+                    self._cv(dgd, dz1, blk.c1.lay.dgrad, dpool, addend=g)
+                    ops.maxpool_bwd(dpool, self._bufs["pool.argmax"][:dpool.numel()].view(dpool.shape), dF[0], accumulate=True)
                 dnext = None
             else:
                 dx = buf("g.dx%d" % (i & 1), (N, hin, win, Cin))
@@ -1250,21 +1368,27 @@ class Engine:
             if self.debug_hook is not None:
                 self.debug_hook(i, dict(dout=dout, g=g, dz2=dz2, da1=da1, dz1=dz1, dnext=dnext, B=B))
             if first_of_layer and on_stage is not None:       # this layer's weight gradients live on the side stream: see stage_streams()
-                on_stage("encoder.layer%d" % (feat_of_block[min(k for k in feat_of_block if k >= i)]))
+                on_stage("encoder.layer%d" % layer_of[i])
+        if on_stage is not None:                        # the wholly frozen layers: their (zero) gradients are "complete" all the same
+            for li in range(min(K, 5) - 1, 0, -1):
+                on_stage("encoder.layer%d" % li)
         # ---- stem ---------------------------------------------------------------------------------------
-        h0, w0 = dims[0]
-        M0 = N * h0 * w0
-        z0 = self._bufs["z0"][:M0 * 64].view(M0, 64)
-        dz0 = buf("g.dz0", (N, h0, w0, 64))
-        d = ops.make_desc(N, h0, w0, S["H"], S["W"], 3, 0, 64, 7, 2, 3, L.GATHER_STEM)
-        stem_hp = self.stem.lay.fwd.hp is not None and ops.conv_stem_hp_supported(d)         # fp16-pair weight gradient: dz0's amax out of bn_bwd
-        ops.bn_bwd(dF[0].view(M0, 64), feats[0].view(M0, 64), z0, self.bn0.mean, self.bn0.invstd, self.bn0.bn.weight.data,
-                   dz0.view(M0, 64), self.bn0.gg, self.bn0.gb, accumulate=accumulate, amax_out=self._sink_slot(dz0) if stem_hp else None)
-        if stem_hp:
-            self._sink_done(dz0)
-            ops.conv_stem_wgrad_hp(d, S["image"], dz0, self.stem.gw, self.amax.get(dz0), accumulate=accumulate)
-        else:
-            ops.conv_wgrad(d, S["image"], None, dz0, self.stem.gw, accumulate=accumulate)
+        if K == 0:
+            h0, w0 = dims[0]
+            M0 = N * h0 * w0
+            z0 = self._bufs["z0"][:M0 * 64].view(M0, 64)
+            dz0 = buf("g.dz0", (N, h0, w0, 64))
+            d = ops.make_desc(N, h0, w0, S["H"], S["W"], 3, 0, 64, 7, 2, 3, L.GATHER_STEM)
+            stem_hp = self.stem.lay.fwd.hp is not None and ops.conv_stem_hp_supported(d)         # fp16-pair weight gradient: dz0's amax out of bn_bwd
+            bn_bwd(self.bn0, dF[0].view(M0, 64), feats[0].view(M0, 64), z0, dz0.view(M0, 64), amax_out=self._sink_slot(dz0) if stem_hp else None)
+            if stem_hp:
+                self._sink_done(dz0)
+            if not self.stem.tw:
+                pass                                    # (bn0 alone is trainable)
+            elif stem_hp:
+                ops.conv_stem_wgrad_hp(d, S["image"], dz0, self.stem.gw, self.amax.get(dz0), accumulate=accumulate)
+            else:
+                ops.conv_wgrad(d, S["image"], None, dz0, self.stem.gw, accumulate=accumulate)
         if side is not None:
             ops.stream_wait_stream(main, side)                # join: every weight gradient is complete
             ops.stream_wait_stream(main, self.dwg[0])
@@ -1417,9 +1541,10 @@ class Engine:
                 self._sink_done(A)
                 if not first:
                     order_dF(3 - bi)
-                ds = ops.make_desc(N, hh, ww, hh, ww, cout, 0, cout, 3, 1, 1, L.GATHER_DGRAD_REFLECT,
-                                   epi=L.EPI_ACCUM if accum_feat else 0)
-                self._cv(ds, Bz, blk["post1"].lay.skip_dgrad, dF[3 - bi])
+                if 3 - bi >= self.first_stage:      # (a feature gradient below the lowest trainable encoder stage has no consumer)
+                    ds = ops.make_desc(N, hh, ww, hh, ww, cout, 0, cout, 3, 1, 1, L.GATHER_DGRAD_REFLECT,
+                                       epi=L.EPI_ACCUM if accum_feat else 0)
+                    self._cv(ds, Bz, blk["post1"].lay.skip_dgrad, dF[3 - bi])
             else:
                 XV = self._dgrad_dec(blk["post1"], Bz, N, hh, ww, buf(pfx + "XV", (N, hh, ww, 2 * cout)))
                 if not first:
@@ -1444,7 +1569,7 @@ class Engine:
                 if dec.psp is not None:
                     dcat = self._dgrad_dec(blk["pre1"], Bz, N, hl, wl, buf(pfx + "psp.dcat", (N, hl, wl, cin)))
                     self._psp_backward(dec, D, dcat, dF[4], N, hl, wl, acc, accum_feat)
-                else:
+                elif self.first_stage <= 4:
                     self._dgrad_dec(blk["pre1"], Bz, N, hl, wl, dF[4], accum=accum_feat)
                 if first:
                     order_dF(4)
@@ -1458,7 +1583,8 @@ class Engine:
     def bind_grads(self, accumulate_existing=True):
         """Point every live parameter's .grad at its view of the flat gradient buffer."""
         for p, v in zip(self.live_params, self.grad_views):
-            p.grad = v
+            if p.requires_grad:
+                p.grad = v
 
 
 class NetFunction(torch.autograd.Function):
@@ -1467,7 +1593,7 @@ class NetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eng, image, *params):
         ctx.eng = eng
-        outs = eng.forward(image, training=eng.model.training, save_for_backward=True)
+        outs = eng.forward(image, training=eng.bn_training(), save_for_backward=True)
         ctx.token = eng.saved
         return tuple(outs)
 
@@ -1481,17 +1607,28 @@ class NetFunction(torch.autograd.Function):
         grads = [torch.zeros(shape, device=eng.device) if g is None else g.contiguous() for g in gouts]
         # .grad semantics of autograd: ACCUMULATE into existing gradients.  Gradients live in the flat buffer, so decide per
         # parameter where its previous gradient is: nowhere (None), already in its flat slot (aliased), or in a foreign tensor.
-        state = [0 if p.grad is None else (1 if p.grad.data_ptr() == v.data_ptr() else 2) for p, v in zip(eng.live_params, eng.grad_views)]
+        # Frozen parameters (requires_grad=False) take no part: they get no .grad and do not decide.
+        # One left-over is refused: a tensor frozen AFTER a backward pass that still holds its flat-buffer view as .grad.  The frozen slots of
+        # the flat buffer are zero-filled (Engine.sync_frozen), so that .grad no longer is what autograd left there, and torch.optim.Adam
+        # would go on training such a tensor with it (it looks at .grad, not at requires_grad) where FusedAdam does not.
+        stale = [n for n, p, v in zip(eng.live_names, eng.live_params, eng.grad_views)
+                 if not p.requires_grad and p.grad is not None and p.grad.data_ptr() == v.data_ptr()]
+        if stale:
+            raise RuntimeError("footprints_amd: frozen parameters (requires_grad=False) still hold a .grad from before they were frozen, a view "
+                               "of the engine's flat gradient buffer whose frozen slots are zero-filled: %s ... -- set it to None "
+                               "(zero_grad(set_to_none=True)) after freezing" % stale[:3])
+        live = [(p, v) for p, v in zip(eng.live_params, eng.grad_views) if p.requires_grad]
+        state =[0 if p.grad is None else (1 if p.grad.data_ptr() == v.data_ptr() else 2) for p, v in live]
         if all(s == 0 for s in state):
             eng.backward(grads, accumulate=False)           # the usual step: zero_grad(set_to_none=True) -> overwrite
         else:
             if not all(s == 1 for s in state):               # mixed: bring every previous gradient into its flat slot first
-                for p, v, s in zip(eng.live_params, eng.grad_views, state):
+                for (p, v), s in zip(live, state):
                     if s == 0:
                         v.zero_()
                     elif s == 2:
                         v.copy_(p.grad)
             eng.backward(grads, accumulate=True)
-        for p, v in zip(eng.live_params, eng.grad_views):    # hand the flat views to the parameters without a copy
+        for p, v in live:                                    # hand the flat views to the parameters without a copy
             p.grad = v
         return (None, None) + tuple(None for _ in eng.live_params)

@@ -111,7 +111,44 @@ def is_dead_param(name):
     return "decoder" in name and (".bn1." in name or ".bn2." in name)
 
 
-class FootprintNetwork(nn.Module):
+class FineTuneMixin:
+    """Fine-tuning surface shared by FootprintNetwork and Segmentor (both own `self.encoder`; the engine reads the BatchNorm mode from
+    the encoder's BatchNorm modules and the frozen set from the parameters' requires_grad flags, so the plain PyTorch idioms --
+    `model.train(); model.encoder.eval()`, `p.requires_grad_(False)` -- do the same)."""
+
+    _freeze_bn_stats = False
+
+    def freeze_bn_stats(self, flag=True):
+        """train with the encoder's BatchNorm layers on their running statistics, which are then never written; gradients still flow
+        through them and into their weight / bias.  Sticky: `model.train()` leaves those layers in eval mode while the flag is set."""
+        self._freeze_bn_stats = bool(flag)
+        for m in self.encoder.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.train(self.training and not self._freeze_bn_stats)
+        return self
+
+    def train(self, mode=True):
+        super().train(mode)
+        if mode and self._freeze_bn_stats:
+            for m in self.encoder.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    m.eval()
+        return self
+
+    def freeze(self, prefixes):
+        """requires_grad_(False) on every parameter whose name starts with one of `prefixes` (("encoder",): train the decoders only);
+        -> the names frozen"""
+        prefixes = (prefixes,) if isinstance(prefixes, str) else tuple(prefixes)
+        names = [n for n, p in self.named_parameters() if n.startswith(prefixes)]
+        if not names:
+            raise ValueError("freeze: no parameter name starts with any of %s" % (prefixes,))
+        for n, p in self.named_parameters():
+            if n.startswith(prefixes):
+                p.requires_grad_(False)
+        return names
+
+
+class FootprintNetwork(FineTuneMixin, nn.Module):
     """forward(x: float32 [B,3,H,W] in [0,1], H,W % 32 == 0) -> {'1/8','1/4','1/2','1/1': [B,4,H,W]} (network.py:21-30).
 
     Channels: 0 visible-ground logit, 1 all-ground logit, 2 depth sigmoid-disparity, 3 ground-depth
@@ -154,7 +191,7 @@ class FootprintNetwork(nn.Module):
             eng.inference_bf16x2 = getattr(self, "inference_precision", "exact") == "bf16x2"     # opt-in, see Engine.__init__
             want = getattr(self, "inference_scales", None)
             idx = None if want is None else sorted(keys.index(k) for k in want)
-            outs = eng.forward(input_image, training=self.training, save_for_backward=False, scales=idx)
+            outs = eng.forward(input_image, training=eng.bn_training(), save_for_backward=False, scales=idx)
             if idx is not None:
                 return OrderedDict((keys[i], outs[i]) for i in idx)
         return OrderedDict(zip(("1/8", "1/4", "1/2", "1/1"), outs))

@@ -653,6 +653,36 @@ def bn_eval_coeffs(gamma, beta, rm, rv, scale, shift, eps=1e-5):
                                              stream()), "fp_bn_eval_coeffs")
 
 
+def bn_eval_coeffs_saved(gamma, beta, rm, rv, scale, shift, save_mean, save_invstd, eps=1e-5):
+    """bn_eval_coeffs for a forward that a backward pass follows (frozen statistics): also save_mean = rm, save_invstd = 1 / sqrt(rv + eps)"""
+    _lib.check(_lib.load().fp_bn_eval_coeffs_saved(_f32(gamma), _f32(beta), _f32(rm), _f32(rv), eps, gamma.numel(), _f32(scale), _f32(shift),
+                                                   _f32(save_mean), _f32(save_invstd), stream()), "fp_bn_eval_coeffs_saved")
+
+
+def bn_bwd_frozen(dy2d, relu_out, z2d, mean, invstd, gamma, dz2d, dgamma, dbeta, g_out=None, accumulate=False, amax_out=None):
+    """backward of a BatchNorm that normalised with (mean, invstd) = its running statistics: dz = g * gamma * invstd in one pass; the sums
+    dgamma / dbeta (each optional) from the same pass.  With neither, z2d / mean may be None and are not read."""
+    lib = _lib.load()
+    M, Cn = dy2d.shape
+    ws_ptr, ws_n = 0, 0
+    if dgamma is not None or dbeta is not None:
+        ws = workspace(lib.fp_bn_workspace(M, Cn), dy2d.device)
+        ws_ptr, ws_n = ws.data_ptr(), ws.numel()
+    _lib.check(lib.fp_bn_bwd_frozen(_f32(dy2d), _f32(relu_out), _f32(z2d), _f32(mean), _f32(invstd), _f32(gamma), _f32(dz2d), _f32(dgamma),
+                                    _f32(dbeta), _f32(g_out), int(bool(accumulate)), M, Cn, ws_ptr, ws_n, _u32(amax_out, "amax_out"), stream()),
+               "fp_bn_bwd_frozen")
+    return dz2d
+
+
+def bn_bwd_frozen_partials(g2d, invstd, gamma, dz2d, dgamma, dbeta, part, nblk, accumulate=False, amax_out=None):
+    """bn_bwd_frozen on a masked g whose producer wrote the partial sums (sum g, sum g * xhat) per pixel tile and channel"""
+    M, Cn = g2d.shape
+    _lib.check(_lib.load().fp_bn_bwd_frozen_partials(_f32(g2d), _f32(invstd), _f32(gamma), _f32(dz2d), _f32(dgamma), _f32(dbeta),
+                                                     int(bool(accumulate)), M, Cn, _f32(part), int(nblk), _u32(amax_out, "amax_out"), stream()),
+               "fp_bn_bwd_frozen_partials")
+    return dz2d
+
+
 def scale_rows(w, scale, out):
     rows = w.shape[0]
     _lib.check(_lib.load().fp_scale_rows(_f32(w), _f32(scale), _f32(out), rows, w.numel() // rows, stream()), "fp_scale_rows")

@@ -41,6 +41,11 @@ class Options:
         # absent from the namespace unless given, like the inference flags below
         p.add_argument("--no_summaries", action="store_true", default=argparse.SUPPRESS,
                        help="train without writing TensorBoard files under <log_path>/<model_name>/{train,val}")
+        # fine-tuning a loaded checkpoint (row N20); applied by TrainManager after --load_path is loaded
+        p.add_argument("--freeze_bn", action="store_true", default=argparse.SUPPRESS,
+                       help="train with the encoder's BatchNorm layers on their running statistics (never written); sound for batches of 2-4")
+        p.add_argument("--freeze", nargs="+", metavar="PREFIX", default=argparse.SUPPRESS,
+                       help="parameters whose names start with a PREFIX are not trained (--freeze encoder: the decoders only)")
         # inference mode of this build (row N12), and with --device_decode the training readers (row N18).  Off unless given -- and absent
         # from the namespace then (read them with getattr(opt, name, False)), so that a plain parse still yields the reference's flags and
         # the two additions above, nothing else

@@ -15,7 +15,7 @@ No CPU compute path: a non-CUDA input raises.
 import torch
 import torch.nn as nn
 
-from ...network import ConvBlock, ConvUpsampleAndConcatBlock, ResnetEncoder, _NoForward, is_dead_param
+from ...network import ConvBlock, ConvUpsampleAndConcatBlock, FineTuneMixin, ResnetEncoder, _NoForward, is_dead_param
 
 
 SCALE_KEYS = ("1/8", "1/4", "1/2", "1/1")          # the positions of forward's list
@@ -69,7 +69,7 @@ class SkipDecoder(_NoForward):
         self.outconv4 = nn.Sequential(ConvBlock(64, 32), OutConvBlock(32, 1))
 
 
-class Segmentor(nn.Module):
+class Segmentor(FineTuneMixin, nn.Module):
     """forward(x: float32 [B,3,H,W] in [0,1], H, W % 32 == 0) -> [logits 1/8, 1/4, 1/2, 1/1], each [B,1,h,w] (network.py:20-25)"""
 
     def __init__(self, pretrained=True, use_PSP=False):
@@ -103,6 +103,6 @@ class Segmentor(nn.Module):
             from ...engine import NetFunction
             outs = NetFunction.apply(eng, input_image, *eng.live_params)
         else:
-            outs = eng.forward(input_image, training=self.training, save_for_backward=False, scales=idx)
+            outs = eng.forward(input_image, training=eng.bn_training(), save_for_backward=False, scales=idx)
         # channel 1 of every buffer is the padding filter's zero output; a skipped head leaves None at its position
         return [o[:, 0:1] if idx is None or i in idx else None for i, o in enumerate(outs)]

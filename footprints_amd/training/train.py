@@ -51,6 +51,7 @@ class TrainStep:
         self._plans = {}            # (input pointers, shapes) -> (plan handle, stage marks, node index where Adam starts, node count)
         self._plan_shape = None
         self._plan_gen = None       # ops.alloc_generation() the plans were recorded at
+        self._mode_key = None       # (frozen set, BatchNorm mode) the plans / the graph were recorded under
         self._graph = None
         self._eager_steps = 0
         self._static = None
@@ -78,6 +79,18 @@ class TrainStep:
 
     def __call__(self, batch):
         """batch: dict with the reference schema (image [B,3,H,W] + six [B,H,W] label maps), already on the GPU."""
+        # fine-tuning: the frozen set (requires_grad flags) and the BatchNorm mode (batch / frozen running statistics) decide which launches
+        # a step consists of, so a recorded plan or a captured graph holds for one pair only: a change drops them (two eager steps, then
+        # a new recording); the optimiser refuses a changed frozen set once it has taken a step
+        if not self.model.training:                       # (a model with frozen BatchNorm statistics keeps them: freeze_bn_stats is sticky)
+            self.model.train()
+        mode = (self.eng.frozen_key(), self.eng.bn_training())
+        if mode != self._mode_key:
+            if self._mode_key is not None and mode[0] != self._mode_key[0]:
+                self.optimiser._ranges(self.eng, pin=False)      # raises after the first step
+            self._drop_plans()
+            self._graph, self._eager_steps = None, 0
+            self._mode_key = mode
         if self.use_plan:
             return self._planned(batch)
         if not self.use_graph:
@@ -200,9 +213,7 @@ class TrainStep:
             B, _, H, W = img.shape
             self.outputs = [torch.empty((B, 4, H, W), device=eng.device) for _ in range(4)]
             self.dpreds = [torch.empty((B, 4, H, W), device=eng.device) for _ in range(4)]
-        if not self.model.training:
-            self.model.train()
-        eng.forward(img, training=True, save_for_backward=True, outputs=self.outputs)
+        eng.forward(img, training=eng.bn_training(), save_for_backward=True, outputs=self.outputs)
         ops.loss_fwd_bwd(self.outputs, batch, self.losses, self.dpreds, self.depth_range, self.prior)
         # zero_grad + backward: gradients are overwritten; buckets are all-reduced as soon as they are complete
         on_stage = None
@@ -212,8 +223,8 @@ class TrainStep:
                 if on_mark is not None:
                     on_mark(stage)
                 self.reducer.stage_ready(stage, eng.stage_streams())
-        elif self.reducer is None and self._adam_ranges is not None and eng.stage_streams() is not None:
-            armed = True
+        elif self.reducer is None and self._adam_ranges is not None and eng.stage_streams() is not None and all(self.eng.frozen_key()):
+            armed = True                                  # (with frozen parameters the stages' ranges are not the update's: unstaged)
             opt, side = self.optimiser, eng.dwg[0]        # the mask decoder's weight-gradient stream: idle for most of the encoder's backward
             if hyper_dev is None:
                 opt.begin_fused_step(eng)
@@ -362,6 +373,11 @@ class TrainManager:
         if getattr(self.opt, "load_path", None) is not None:
             self.model_manager.load_model(weights_path=self.opt.load_path, load_optimiser=True)   # train.py:63-64
         self.model = self.model_manager.model
+        # fine-tuning (--freeze_bn, --freeze PREFIX ...): applied to the loaded weights, before the first step fixes the frozen set
+        if getattr(self.opt, "freeze_bn", False):
+            self.model.freeze_bn_stats()
+        if getattr(self.opt, "freeze", None):
+            self.log("frozen: {} tensors under {}".format(len(self.model.freeze(self.opt.freeze)), list(self.opt.freeze)))
         self.optimiser, self.scheduler = self.model_manager.optimiser, self.model_manager.scheduler
         self.val_iter = iter(self.val_loader) if self.val_loader is not None else None
         depth_range = tuple(self.opt.depth_range)

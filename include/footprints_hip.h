@@ -336,6 +336,25 @@ int fp_bn_bwd_partials(const float* g, const float* z, const float* save_mean, c
 /* eval mode: scale/shift from running statistics */
 int fp_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                       float eps, int32_t C, float* scale, float* shift, fp_stream_t stream);
+/* ... and for a backward pass through the layer (fine-tuning with frozen statistics): the same coefficients, with save_mean = running_mean and
+ * save_invstd = 1 / sqrt(running_var + eps) left where fp_bn_bwd_frozen and the data gradients' epilogue sinks (fp_aux.bnb_*) read them;
+ * scale = gamma * save_invstd is built from that float32 value. */
+int fp_bn_eval_coeffs_saved(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                            int32_t C, float* scale, float* shift, float* save_mean, float* save_invstd, fp_stream_t stream);
+/* Backward of nn.BatchNorm2d in eval mode (aten::native_batch_norm_backward with train=False; torchvision BatchNorm2d behind
+ * footprints/network.py:38-44 with frozen statistics): g = dy * (relu_out > 0 if relu_out); dz = g * gamma * invstd; g_out (optional) = g;
+ * dbeta (+)= sum g; dgamma (+)= sum g * (z - mean) * invstd.  One pass; with dgamma == dbeta == NULL a single launch that never reads z /
+ * mean (both may be NULL, workspace too); otherwise per-workgroup partial sums + a small combining launch (double, fixed order, no atomics),
+ * workspace >= fp_bn_workspace(M, C).  amax_out (optional): the amax slot that receives max |dz|, published like fp_bn_bwd's (the slot
+ * itself is the argument: these two launches have no other side output to ask for). */
+int fp_bn_bwd_frozen(const float* dy, const float* relu_out, const float* z, const float* mean, const float* invstd, const float* gamma,
+                     float* dz, float* dgamma, float* dbeta, float* g_out, int accumulate, int64_t M, int32_t C, void* workspace,
+                     int64_t workspace_bytes, uint32_t* amax_out, fp_stream_t stream);
+/* ... on a masked g and the partial sums (sum g, sum g * xhat) that the producing data gradient's epilogue wrote (fp_aux.bn_part with bnb_mean /
+ * bnb_invstd = the running statistics): they ARE dbeta / dgamma; only their combination (skipped with dgamma == dbeta == NULL) and the
+ * element-wise dz remain. */
+int fp_bn_bwd_frozen_partials(const float* g, const float* invstd, const float* gamma, float* dz, float* dgamma, float* dbeta, int accumulate,
+                              int64_t M, int32_t C, const float* part, int32_t nblk, uint32_t* amax_out, fp_stream_t stream);
 /* out[r][:] = w[r][:] * scale[r]: folds the eval-mode scale into the preceding conv's OIHW weights (the shift becomes the
  * conv's bias), so inference runs conv + bias + ReLU (+ residual) in one launch -- SURVEY.md section 8(f) N1. */
 int fp_scale_rows(const float* w, const float* scale, float* out, int64_t rows, int64_t inner, fp_stream_t stream);
