@@ -1,4 +1,4 @@
-"""The host launch arithmetic of the step's non-convolution kernels, restated in plain Python, and what follows from it for a
+"""The host launch arithmetic of the step's non-convolution kernels and (at the end) of the 3x3 stride-1 tile kernels, restated in plain Python, and what follows from it for a
 test: which launch REGIME a shape runs in, and how long the longest chain of dependent float32 additions behind one reduced output is.
 
 Every function names the file:line it restates.  tests/test_launch_regimes_cpu.py sweeps these against the library's own answers
@@ -236,3 +236,136 @@ def seg_loss_chain(HW):
 def sum_bound(L, k, abs_terms, result):
     """first-order summation bound: (L + k) u sum|terms| + u |result|; k = roundings inside one term"""
     return (L + k) * U * abs_terms + U * abs(result)
+
+
+# ---- the 3x3 stride-1 tile kernels (conv3x3_tile_bf3.hip, wgrad3x3_bf3.hip) ---------------------------------------------------------
+# Operand formats: "exact" (three bf16 terms, six products), "pair" (scaled fp16 pairs), "two" (two bf16 terms: the opt-in inference mode,
+# forward gathers only).  Families: "fwd" (gathers zero / reflect / up2), "flip" (data gradient, zero padding), "fold" (data gradient
+# of reflection padding).
+TILE3_GATHERS = {"zero": "fwd", "reflect": "fwd", "up2": "fwd", "dgrad": "flip", "dgrad_reflect": "fold"}
+
+
+def tile3_plan(N, H, W, C0, C1, Nout, up2=False, fmt="exact"):
+    """conv3x3_tile_bf3.hip:811 plan3 (every FP_TILE_* variable unset) and what run_tile3 adds (:925-926 wmajor, :940-951 the
+    instantiation) -> dict, or None where fp_conv3x3_bf3_supported answers 0.  H x W = output = input size (stride 1, pad 1)"""
+    if C0 % 4:
+        return None
+    if up2:
+        if C0 % 16 or C1 % 4 or C1 < 0 or H % 2 or W % 2:
+            return None
+    elif C1:
+        return None
+    if H < 2 or W < 2:
+        return None
+
+    def waste_ok(th, tw):                                       # :824 at most 25 % padded work
+        return ceil_div(H, th) * ceil_div(W, tw) * 128 * 4 <= H * W * 5
+    if waste_ok(8, 16):
+        th, tw = 8, 16
+    elif waste_ok(6, 20):
+        th, tw = 6, 20
+    else:
+        return None
+    bn = 32 if Nout <= 32 else 64
+    tx, ty, tn = ceil_div(W, tw), ceil_div(H, th), ceil_div(Nout, bn)
+    tiles = N * ty * tx * tn
+    KC16 = (C0 + C1 + 15) // 16
+    sk = 1
+    if tiles < 160:                                             # :853 no split from 160 tiles
+        sk = max(1, min(768 // tiles, KC16 // 2, 16))           # :855-859 target 768, >= 2 chunks per split, <= 16 partial copies
+    cps = ceil_div(KC16, sk)
+    SK = ceil_div(KC16, cps)
+    if tiles * SK < 128:                                        # :863
+        return None
+    nwg = tiles * SK
+    hp = fmt == "pair"
+    inst = ("pair_wpf" if (bn == 64 and nwg <= 400) else "pair") if hp else fmt          # :943
+    return {"th": th, "tw": tw, "bn": bn, "tilesX": tx, "tilesY": ty, "tilesN": tn, "KC16": KC16, "SK": SK, "cps": cps, "nwg": nwg,
+            "wmajor": 9 * (C0 + C1) * Nout * (4 if hp else 6) > (4 << 20), "inst": inst,
+            "workspace": SK * N * H * W * Nout * 4 if SK > 1 else 0}                         # :873
+
+
+def _chunk_class(n):
+    """trips of a loop that is unrolled by two with up to two items in flight ahead: 1, 2, 3, an even count >= 4, an odd count >= 5"""
+    return n if n <= 3 else ("even" if n % 2 == 0 else "odd")
+
+
+def _rem_class(n, t):
+    """pixels of the last tile along one axis: 0 (a full tile), 1, 2, or 3 = three and more"""
+    return min(n % t, 3)
+
+
+def tile3_regime(gather, fmt, N, H, W, C0, C1, Nout):
+    """frozenset of ("tile3", instantiation key, axis, value).  key = (family, tile height, BN, instantiation): one compiled kernel;
+    the axes are what differs between launches of one kernel:
+      gather   zero / reflect / up2 (a.mode, a.Clo at :299-311)
+      split    (False, 0) unsplit, or (True, SK % 4): the tail loop of the reduce launch
+      chunks   class of c_end - c_begin (:330-331), every split of the launch counted; the loop is unrolled by two and the halo sets
+               prefetch up to two chunks ahead (:746-751)
+      ctail    C % 16 != 0 (zero_tail, :355);  c1: for the concat gather "none" / "tail" (C1 % 16 != 0) / "whole"
+      ntail    Nout % BN != 0 (:314, :517);  wmajor (:926)
+      ragx / ragy   pixels of the last tile of a row / column of tiles (:512 the epilogue's `interior`, :300-302 the halo's validity)
+      foldy / foldx (fold only, :316-317) (rows 1 and OH-2 share a tile, OH-2 lies in the last tile or in the one before it)"""
+    family = TILE3_GATHERS[gather]
+    assert fmt != "two" or family == "fwd"
+    p = tile3_plan(N, H, W, C0, C1, Nout, gather == "up2", fmt)
+    assert p is not None, (gather, fmt, N, H, W, C0, C1, Nout)
+    key = (family, p["th"], p["bn"], p["inst"])
+    C = C0 + C1
+    out = [("gather", gather), ("split", (p["SK"] > 1, p["SK"] % 4 if p["SK"] > 1 else 0)), ("ctail", C % 16 != 0),
+           ("ntail", Nout % p["bn"] != 0), ("wmajor", p["wmajor"]), ("ragx", _rem_class(W, p["tw"])), ("ragy", _rem_class(H, p["th"]))]
+    for s in range(p["SK"]):
+        out.append(("chunks", _chunk_class(min(p["KC16"], (s + 1) * p["cps"]) - s * p["cps"])))
+    if gather == "up2":
+        out.append(("c1", "none" if C1 == 0 else "tail" if C1 % 16 else "whole"))
+    if family == "fold":
+        for ax, n, t, tiles in (("foldy", H, p["th"], p["tilesY"]), ("foldx", W, p["tw"], p["tilesX"])):
+            out.append((ax, (1 // t == (n - 2) // t, "last" if (n - 2) // t == tiles - 1 else "before")))
+    return frozenset(("tile3", key) + o for o in out)
+
+
+W3_CH, W3_CW = 4, 16      # wgrad3x3_bf3.hip:45 pixel chunk of the weight gradient: 4 rows x 16 columns
+
+
+def wgrad3_plan(N, H, W, C0, Nout, up2=False):
+    """wgrad3x3_bf3.hip:797 eligible and :812 plan (FP_WGRAD_* unset) -> dict, or None where fp_conv_wgrad_bf3_workspace answers -1"""
+    if up2 and (H % 2 or W % 2):
+        return None
+    if H < 2 or W < 2 or C0 % 32 or Nout % 32:
+        return None
+    cy, cx = ceil_div(H, W3_CH), ceil_div(W, W3_CW)
+    if cy * W3_CH * cx * W3_CW * 10 > H * W * 22:               # :807 padded work up to 2.2x
+        return None
+    if N * cy * cx < 16:                                        # :808
+        return None
+    nchunks = N * cy * cx
+    citiles, cotiles = C0 // 32, Nout // 32
+    S = max(1, min(ceil_div(256, citiles * cotiles), nchunks // 4, 512))       # :822-825
+    cps = ceil_div(nchunks, S)
+    S = ceil_div(nchunks, cps)
+    return {"S": S, "cps": cps, "nchunks": nchunks, "cy": cy, "cx": cx, "citiles": citiles, "cotiles": cotiles,
+            "workspace": S * (9 * C0 * Nout + Nout) * 4}         # :837
+
+
+def wgrad3_regime(mode, fmt, N, H, W, C0, Nout):
+    """frozenset of ("wgrad3", key, axis, value).  key = (kernel, mode, fmt): "ring" = wgrad3x3_hp_pf_kernel, "v3" = the third
+    generation, which keeps the exact format's up2 gather (:900).  Axes:
+      remy / remx   rows / columns of the last 4 x 16 chunk (0 = full)
+      chunks   "border" or "both": does a launch hold fast (interior) chunks beside the border ones (:415; never for up2)
+      cnt      parity of the chunk count of a split (:362; two ring slots, two LDS buffers), every split counted
+      stride   (S >= chunks per image: dcn > 0, S % chunksX == 0: dcx == 0) (:365)
+      reduce   "plain", "capped" (its 4096-block cap), "transposing" (:935-949);  s4: S % 4 (the partial-sum loops' tail)"""
+    p = wgrad3_plan(N, H, W, C0, Nout, mode == "up2")
+    assert p is not None, (mode, fmt, N, H, W, C0, Nout)
+    key = ("v3" if (fmt == "exact" and mode == "up2") else "ring", mode, fmt)
+    fast = mode != "up2" and any(y0 >= 1 and y0 + W3_CH + 1 <= H and x0 >= 1 and x0 + W3_CW + 1 <= W
+                                 for y0 in range(0, H, W3_CH) for x0 in range(0, W, W3_CW))
+    if (Nout // 32) * (C0 // 8) >= 512:
+        reduce = "transposing"
+    else:
+        reduce = "capped" if ceil_div(9 * C0 * Nout, 256) > 4096 else "plain"
+    S = p["S"]
+    out = [("remy", H % W3_CH), ("remx", _rem_class(W, W3_CW)), ("chunks", "both" if fast else "border"),
+           ("stride", (S >= p["cy"] * p["cx"], S % p["cx"] == 0)), ("reduce", reduce), ("s4", S % 4)]
+    out += [("cnt", ((p["nchunks"] - 1 - s) // S + 1) % 2) for s in range(S)]
+    return frozenset(("wgrad3", key) + o for o in out)

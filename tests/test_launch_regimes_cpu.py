@@ -9,12 +9,17 @@ bounds those tests use tight enough to see one dropped row?
    reduced output at least must move by more than ten times its bound (tests/step_kernel_refs.py), else the bound could not see it.
 4. The two training losses: the launch arithmetic of csrc/seg_loss.hip against fp_seg_loss_workspace, and the regimes the trainers' shapes
    run (Footprints 12x192x640, 4x512x640, 12x512x640; segmentor 12x192x640) against the cases of tests/test_gpu_losses.py.
+5. The 3x3 stride-1 tile kernels: plan3 / run_tile3 (csrc/conv3x3_tile_bf3.hip) and eligible / plan (csrc/wgrad3x3_bf3.hip) restated and
+   swept against fp_conv3x3_bf3_supported, fp_conv3x3_bf3_workspace and fp_conv_wgrad_bf3_workspace; TILE_WORKLOAD lists the 3x3 stride-1
+   convolutions of one train step with their data and weight gradients (footprints 12x192x640, 4x512x640, 12x128x416; segmentor
+   12x192x640), and every regime tuple of it must occur among the cases of tests/test_gpu_conv_tile_edges.py (tests/conv_tile_refs.py).
 """
 import ctypes
 
 import pytest
 import torch
 
+from tests import conv_tile_refs as TR
 from tests import launch_regimes as LR
 from tests import step_kernel_refs as SR
 
@@ -291,3 +296,180 @@ def test_head_wgrad_bounds_see_a_dropped_pixel(shape):
     inp = SR.head_inputs(shape)
     _assert_sensitive("head_wgrad %s" % (shape,), lambda keep: SR.head_wgrad_ref(inp, keep), N * h * w, 256 // (Cin // 4),
                       LR.head_wgrad_blocks(N * h * w, Cin), ("dw", "db"))
+
+
+# ---- 5. the 3x3 stride-1 tile kernels: restatement against the library, workload against the cases of test_gpu_conv_tile_edges.py ----
+TILE_CHANNELS = [(32, 0, 32), (64, 0, 64), (20, 0, 72), (112, 0, 40), (12, 0, 16), (80, 0, 96), (32, 20, 64), (16, 0, 32), (64, 64, 64),
+                 (512, 0, 256), (256, 256, 256), (30, 0, 32)]
+_GATHER_ID = {"zero": 0, "reflect": 1, "up2": 2, "dgrad": 3, "dgrad_reflect": 4}
+
+
+def _desc(N, H, W, C0, C1, Nout, gather):
+    from footprints_amd import ops
+    return ops.make_desc(N, H, W, H, W, C0, C1, Nout, 3, 1, 1, _GATHER_ID[gather])
+
+
+def _tile_sweep_shapes():
+    hs = sorted(set([2, 3, 5, 6, 7, 8, 11, 12, 15, 16, 20, 24, 26, 31, 32, 33, 40, 48, 64, 65, 96, 128, 140] + _sweep(11, 14, 2, 141)))
+    ws = sorted(set([2, 3, 15, 16, 19, 20, 26, 40, 65, 66, 80, 82, 104, 121, 122, 140] + _sweep(12, 12, 2, 141)))
+    ns = [1, 2, 3, 4, 7, 12, 13, 26, 43, 64]
+    return hs, ws, ns
+
+
+def _tile_switched():
+    import os
+    return sorted(k for k in os.environ if k.startswith("FP_TILE_") or k.startswith("FP_WGRAD_"))
+
+
+def test_tile3_plan_matches_library():
+    """fp_conv3x3_bf3_supported and fp_conv3x3_bf3_workspace (host-only queries) against tile3_plan over ~60 000 descriptors"""
+    if _tile_switched():
+        pytest.skip("the launch rules are switched by %s: the restatement is that of the default build" % ", ".join(_tile_switched()))
+    import ctypes as C
+    lib = _lib()
+    assert _GATHER_ID == {"zero": 0, "reflect": 1, "up2": 2, "dgrad": 3, "dgrad_reflect": 4}
+    hs, ws, ns = _tile_sweep_shapes()
+    n = 0
+    for C0, C1, Nout in TILE_CHANNELS:
+        for gather in (("up2",) if C1 else ("zero", "up2", "dgrad_reflect")):
+            for H in hs:
+                for W in ws:
+                    for N in ns:
+                        d = _desc(N, H, W, C0, C1, Nout, gather)
+                        p = LR.tile3_plan(N, H, W, C0, C1, Nout, gather == "up2")
+                        assert bool(lib.fp_conv3x3_bf3_supported(C.byref(d))) == (p is not None), (gather, N, H, W, C0, C1, Nout)
+                        assert lib.fp_conv3x3_bf3_workspace(C.byref(d)) == (p["workspace"] if p else 0), (gather, N, H, W, C0, C1, Nout)
+                        if p and p["SK"] > 1:
+                            assert p["workspace"] == p["SK"] * N * H * W * Nout * 4
+                        n += 1
+    assert n > 3000
+
+
+def test_wgrad3_plan_matches_library():
+    """fp_conv_wgrad_bf3_workspace against wgrad3_plan: S (9 C0 Nout + Nout) 4 bytes, or -1"""
+    if _tile_switched():
+        pytest.skip("the launch rules are switched by %s: the restatement is that of the default build" % ", ".join(_tile_switched()))
+    import ctypes as C
+    lib = _lib()
+    hs, ws, ns = _tile_sweep_shapes()
+    n = 0
+    for C0, Nout in [(32, 32), (32, 64), (64, 32), (32, 96), (96, 32), (256, 256), (512, 256), (480, 256), (20, 32), (32, 40), (128, 128)]:
+        for mode in ("zero", "reflect", "up2"):
+            for H in hs:
+                for W in ws:
+                    for N in ns:
+                        p = LR.wgrad3_plan(N, H, W, C0, Nout, mode == "up2")
+                        got = lib.fp_conv_wgrad_bf3_workspace(C.byref(_desc(N, H, W, C0, 0, Nout, mode)))
+                        assert got == (p["workspace"] if p else -1), (mode, N, H, W, C0, Nout)
+                        if p:
+                            assert p["workspace"] == p["S"] * (9 * C0 * Nout + Nout) * 4
+                        n += 1
+    assert n > 3000
+
+
+def tile_workload(N, H, W, psp=False):
+    """the 3x3 stride-1 convolutions of one train step as (tile cases without format, weight-gradient cases without format), by
+    engine.py line; a superset where a switch or a shape test decides between the tile kernels and another path.
+    Encoder (engine.py:787 forward, :1318 data gradient, :1122 weight gradient): conv2 of every block and conv1 of the stride-1 blocks.
+    Decoder block bi at (h, w) = level 4 - bi (engine.py:1091-1096): pre1 cin -> cout, pre2 at (h, w); post1 over cat[up2(y2), skip]
+    (or its skip half alone beside the phase kernels, :900), post2 at (2h, 2w); o41 / o42 at full resolution (:1105-1106).
+    Data gradients :1183 (:1501 :1508 :1530 :1545 :1549 :1559 :1570-1573), weight gradients :1129 :1152-1154 :1173 (:1500 :1503 :1529-1565)"""
+    tile, wg = [], []
+    for s, c in ((2, 64), (3, 128), (4, 256), (5, 512)):
+        h, w = H >> s, W >> s
+        tile += [("zero", N, h, w, c, 0, c), ("dgrad", N, h, w, c, 0, c)]
+        wg.append(("zero", N, h, w, c, c))
+    chans = [(1024 if psp else 512, 256), (256, 128), (128, 64), (64, 64)]
+    for bi, (cin, cout) in enumerate(chans):
+        h, w = (H >> 5) << bi, (W >> 5) << bi
+        hh, ww = 2 * h, 2 * w
+        tile += [("reflect", N, h, w, cin, 0, cout), ("reflect", N, h, w, cout, 0, cout), ("up2", N, hh, ww, cout, cout, cout),
+                 ("reflect", N, hh, ww, cout, 0, cout),                                   # post1's skip half, and post2
+                 ("dgrad_reflect", N, h, w, cout, 0, cin), ("dgrad_reflect", N, h, w, cout, 0, cout),
+                 ("dgrad_reflect", N, hh, ww, cout, 0, cout), ("dgrad_reflect", N, hh, ww, cout, 0, 2 * cout)]
+        wg += [("reflect", N, h, w, cin, cout), ("reflect", N, h, w, cout, cout), ("reflect", N, hh, ww, cout, cout),
+               ("up2", N, hh, ww, cout, cout)]
+    tile += [("up2", N, H, W, 64, 0, 32), ("reflect", N, H, W, 32, 0, 32), ("dgrad_reflect", N, H, W, 32, 0, 32),
+             ("dgrad_reflect", N, H, W, 32, 0, 64)]
+    wg += [("up2", N, H, W, 64, 32), ("reflect", N, H, W, 32, 32)]
+    return tile, wg
+
+
+TILE_WORKLOAD = {"footprints 12x192x640": tile_workload(12, 192, 640), "footprints 4x512x640": tile_workload(4, 512, 640),
+                 "footprints 12x128x416": tile_workload(12, 128, 416), "psp segmentor 12x192x640": tile_workload(12, 192, 640, psp=True)}
+TILE_FORMATS = ("exact", "pair")
+
+
+def tile_workload_regimes():
+    """{regime tuple: (workload name, launch) of its first occurrence} over both training formats; launches the planners turn down
+    (they take the flattened kernels) are no part of it"""
+    need = {}
+    for name, (tile, wg) in TILE_WORKLOAD.items():
+        for fmt in TILE_FORMATS:
+            for gather, N, H, W, C0, C1, Nout in tile:
+                if LR.tile3_plan(N, H, W, C0, C1, Nout, gather == "up2", fmt):
+                    for r in LR.tile3_regime(gather, fmt, N, H, W, C0, C1, Nout):
+                        need.setdefault(r, (name, (gather, fmt, N, H, W, C0, C1, Nout)))
+            for mode, N, H, W, C0, Nout in wg:
+                if LR.wgrad3_plan(N, H, W, C0, Nout, mode == "up2"):
+                    for r in LR.wgrad3_regime(mode, fmt, N, H, W, C0, Nout):
+                        need.setdefault(r, (name, (mode, fmt, N, H, W, C0, Nout)))
+    return need
+
+
+def tile_case_regimes():
+    have = set()
+    for c in TR.TILE_CASES:
+        have |= LR.tile3_regime(*c)
+    for c in TR.WGRAD_CASES:
+        have |= LR.wgrad3_regime(*c)
+    return have
+
+
+def test_tile_cases_are_launchable():
+    """every GPU case is a shape its launcher takes (an unsupported case is an error of the table, never a skip)"""
+    for gather, fmt, N, H, W, C0, C1, Nout in TR.TILE_CASES + TR.TILE_TWO_TERM:
+        assert LR.tile3_plan(N, H, W, C0, C1, Nout, gather == "up2", fmt), (gather, fmt, N, H, W, C0, C1, Nout)
+    for mode, fmt, N, H, W, C0, Nout in TR.WGRAD_CASES:
+        assert LR.wgrad3_plan(N, H, W, C0, Nout, mode == "up2"), (mode, fmt, N, H, W, C0, Nout)
+
+
+def test_tile_workload_regimes_occur_in_cases():
+    have = tile_case_regimes()
+    missing = {r: w for r, w in tile_workload_regimes().items() if r not in have}
+    lines = ["%s: first run by %s %s" % (r, w[0], w[1]) for r, w in sorted(missing.items(), key=repr)]
+    assert not missing, "%d launch regimes of the train step that no GPU case of tests/conv_tile_refs.py runs:\n%s" % (len(lines), "\n".join(lines))
+
+
+def _split_sizes(c):
+    gather, fmt, N, H, W, C0, C1, Nout = c
+    p = LR.tile3_plan(N, H, W, C0, C1, Nout, gather == "up2", fmt)
+    return p, tuple(min(p["KC16"], (s + 1) * p["cps"]) - s * p["cps"] for s in range(p["SK"]))
+
+
+def test_tile_cases_reach_the_structural_edges():
+    """edges the cases add on purpose, whether or not a train step runs them today"""
+    have = tile_case_regimes()
+    axes = {}
+    for r in have:
+        if r[0] == "tile3":
+            axes.setdefault((r[1][1], r[2]), set()).add(r[3])          # (tile height, axis) -> values over all kernels
+    for th in (8, 6):
+        assert axes[(th, "ragx")] == {0, 1, 2, 3} and axes[(th, "ragy")] >= {0, 1, 3}, (th, axes[(th, "ragx")], axes[(th, "ragy")])
+        assert axes[(th, "chunks")] == {1, 2, 3, "even", "odd"}, (th, axes[(th, "chunks")])
+        assert {(False, "before"), (False, "last")} <= axes[(th, "foldx")] and (True, "last") in axes[(th, "foldy")]
+        assert {True, False} <= axes[(th, "ctail")] and {True, False} <= axes[(th, "ntail")] and {True, False} <= axes[(th, "wmajor")]
+    assert axes[(8, "c1")] == {"none", "tail", "whole"} and axes[(6, "c1")] >= {"none", "whole"}
+    sizes = {(c[0], c[1]): _split_sizes(c)[1] for c in TR.TILE_CASES if _split_sizes(c)[1] == (3, 3, 1)}
+    assert {"fwd", "fold", "flip"} <= {LR.TILE3_GATHERS[g] for g, _ in sizes} and {"exact", "pair"} <= {f for _, f in sizes}, sizes
+    p, s = _split_sizes(("up2", "pair", 9, 8, 66, 48, 64, 40))
+    assert s == (3, 3, 1) and p["cps"] * 16 == 48                      # the concat gather switches sources exactly where the second split begins
+    single = [c for c in TR.TILE_CASES if c[3:5] == (7, 15)]           # one partial tile per image, in both formats
+    assert {c[1] for c in single} == {"exact", "pair"}
+    assert any(_split_sizes(c)[0]["inst"] == "pair" and _split_sizes(c)[0]["bn"] == 64 for c in TR.TILE_CASES)       # above 400 workgroups
+    wg = {}
+    for r in have:
+        if r[0] == "wgrad3":
+            wg.setdefault(r[2], set()).add(r[3])
+    assert wg["remy"] == {0, 1, 2, 3} and wg["remx"] == {0, 1, 2, 3} and wg["reduce"] == {"plain", "capped", "transposing"}
+    assert wg["chunks"] == {"border", "both"} and wg["cnt"] == {0, 1} and wg["s4"] == {0, 1, 2, 3}
