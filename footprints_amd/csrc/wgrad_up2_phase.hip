@@ -369,7 +369,7 @@ __global__ void __launch_bounds__(256) up2_wgrad_uncollapse_kernel(const float* 
 
 struct PPlan { int S, chunksPerSplit, nchunks, citiles, cotiles, cy, cx; };
 bool eligible(int N, int h, int w, int C0, int Nout) {
-  if (C0 % 32 || Nout % 32 || h < 1 || w < 1) return false;
+  if (N < 1 || C0 < 1 || Nout < 1 || C0 % 32 || Nout % 32 || h < 1 || w < 1) return false;   // (no channels: plan() would divide by 0 tiles)
   const int64_t cy = fp_ceil_div(h, CHL), cx = fp_ceil_div(w, CW);
   if (cy * CHL * cx * CW * 10 > (int64_t)h * w * 13) return false;   // > 30 % padded work
   if ((int64_t)N * cy * cx < 16) return false;

@@ -1,4 +1,4 @@
-"""The host launch arithmetic of the step's non-convolution kernels and (at the end) of the 3x3 stride-1 tile kernels, restated in plain Python, and what follows from it for a
+"""The host launch arithmetic of the step's non-convolution kernels and (at the end) of the 3x3 stride-1 tile kernels and the nearest-x2 phase kernels, restated in plain Python, and what follows from it for a
 test: which launch REGIME a shape runs in, and how long the longest chain of dependent float32 additions behind one reduced output is.
 
 Every function names the file:line it restates.  tests/test_launch_regimes_cpu.py sweeps these against the library's own answers
@@ -369,3 +369,145 @@ def wgrad3_regime(mode, fmt, N, H, W, C0, Nout):
            ("stride", (S >= p["cy"] * p["cx"], S % p["cx"] == 0)), ("reduce", reduce), ("s4", S % 4)]
     out += [("cnt", ((p["nchunks"] - 1 - s) // S + 1) % 2) for s in range(S)]
     return frozenset(("wgrad3", key) + o for o in out)
+
+
+# ---- the nearest-x2 phase kernels (conv_up2_phase.hip, wgrad_up2_phase.hip) ---------------------------------------------------------
+# Operand formats: "f32" (fp32 MFMA), "exact" (three bf16 terms), "pair" (scaled fp16 pairs).  h x w is the LOW-resolution grid throughout.
+PH_TH, PH_TW = 8, 16      # conv_up2_phase.hip:23 the low-resolution tile of the forward and data-gradient kernels
+PW_CH, PW_CW = 2, 16      # wgrad_up2_phase.hip:30 pixel chunk of the weight gradient: 2 rows x 16 columns
+PHASE_FORMATS = ("f32", "exact", "pair")
+
+
+def phase_ok(h, w):
+    """engine.py:895 _phase_ok: the caller keeps the fused-gather path when under 60 % of the 8 x 16 tiles would be pixels"""
+    return h * w * 10 >= ceil_div(h, 8) * 8 * ceil_div(w, 16) * 16 * 6
+
+
+def phase_fwd_plan(N, h, w, C0, Nout, fmt="exact"):
+    """conv_up2_phase.hip:593-608 (f32) and :615-636 (split formats) -> dict, or None where the launcher refuses the arguments"""
+    if min(N, h, w, C0, Nout) < 1 or C0 % 4:
+        return None
+    if fmt != "f32" and (N * 4 * h * w * Nout >= 1 << 29 or N * h * w * C0 >= 1 << 29):          # :617 32-bit byte offsets
+        return None
+    bn = 32 if Nout <= 32 else 64                                # :626
+    tx, ty, tn = ceil_div(w, PH_TW), ceil_div(h, PH_TH), ceil_div(Nout, bn)
+    return {"bn": bn, "tilesX": tx, "tilesY": ty, "tilesN": tn, "KC16": ceil_div(C0, 16), "nwg": N * ty * tx * tn * 4}
+
+
+def phase_dgrad_plan(N, h, w, Cout, C0, fmt="exact"):
+    """conv_up2_phase.hip:654-674: tiles of the EXTENDED (h + 2) x (w + 2) grid, BN over the C0 result channels, chunks over Cout; one
+    workgroup runs all four phases (4 KC16 steps)"""
+    if min(N, h, w, Cout, C0) < 1 or Cout % 4 or fmt == "f32":          # (no fp32 phase data gradient: that path is conv_igemm)
+        return None
+    if N * 4 * h * w * Cout >= 1 << 29 or N * (h + 2) * (w + 2) * C0 >= 1 << 29:
+        return None
+    bn = 32 if C0 <= 32 else 64                                  # :664
+    tx, ty, tn = ceil_div(w + 2, PH_TW), ceil_div(h + 2, PH_TH), ceil_div(C0, bn)
+    kc = ceil_div(Cout, 16)
+    return {"bn": bn, "tilesX": tx, "tilesY": ty, "tilesN": tn, "KC16": kc, "nsteps": 4 * kc, "nwg": N * ty * tx * tn}
+
+
+def phase_wgrad_plan(N, h, w, C0, Nout):
+    """wgrad_up2_phase.hip:371 eligible and :378 plan (FP_PWGRAD_TARGET_WGS unset: 768) -> dict, or None where
+    fp_conv_up2_phase_wgrad_workspace answers -1"""
+    if C0 % 32 or Nout % 32 or h < 1 or w < 1 or C0 < 1 or Nout < 1:
+        return None
+    cy, cx = ceil_div(h, PW_CH), ceil_div(w, PW_CW)
+    if cy * PW_CH * cx * PW_CW * 10 > h * w * 13:                # :374 more than 30 % padded work
+        return None
+    if N * cy * cx < 16:                                         # :375
+        return None
+    nchunks = N * cy * cx
+    citiles, cotiles = C0 // 32, Nout // 32
+    S = max(1, min(ceil_div(768, citiles * cotiles), nchunks // 4, 512))       # :385-388 one round of three workgroups per CU
+    cps = ceil_div(nchunks, S)
+    S = ceil_div(nchunks, cps)
+    return {"S": S, "cps": cps, "nchunks": nchunks, "cy": cy, "cx": cx, "citiles": citiles, "cotiles": cotiles,
+            "workspace": (S * 16 * C0 * Nout + S * Nout) * 4}    # :400
+
+
+def _clamp_class(n, t):
+    """does the halo of ONE tile leave the image on both sides of an axis: "no", "both" (n < t), "one" (a single row / column: every
+    halo row is the same pixel row)"""
+    return "one" if n == 1 else "both" if n < t else "no"
+
+
+def _cnt_class(n):
+    """chunks of one split of the weight gradient (one-deep prefetch, two LDS buffers in the fp32 kernel): 1, 2, an even count, an odd count"""
+    return n if n <= 2 else ("even" if n % 2 == 0 else "odd")
+
+
+def phase_wgrad_split_counts(p, fmt):
+    """chunks per split: the fp32 kernel takes `cps` contiguous chunks (wgrad_up2_phase.hip:45-46, the last split short), the split-operand
+    kernels stride them: c = s, s + S, ... (:176)"""
+    if fmt == "f32":
+        return [min(p["nchunks"], (s + 1) * p["cps"]) - s * p["cps"] for s in range(p["S"])]
+    return [len(range(s, p["nchunks"], p["S"])) for s in range(p["S"])]
+
+
+def phase_wgrad_sum_groups(S):
+    """up2_wgrad_sum_kernel (wgrad_up2_phase.hip:340-345): group g of four walks s = g, g + 4, ...: (trips of the 16-stride loop > 0, trips of the tail)"""
+    out = []
+    for g in range(4):
+        s, main = g, 0
+        while s + 12 < S:
+            s += 16
+            main += 1
+        out.append((main > 0, len(range(s, S, 4))))
+    return out
+
+
+def phase_regime(kind, fmt, N, h, w, C0, C1, Nout, epi=(), kslice=(0, 0)):
+    """frozenset of ("phase", key, axis, value); key = (kind, BN or the weight-gradient kernel, fmt): one compiled instantiation.
+    kind "fwd": low [N, h, w, C0] -> y [N, 2h, 2w, Nout] (C1 = channels of the skip half, which another kernel runs: it decides the
+    `addend` epilogue only); "dgrad": dz [N, 2h, 2w, Nout] -> ext [N, h + 2, w + 2, C0]; "wgrad": dw [Nout, k_begin + C0 + k_after, 3, 3],
+    kslice = (k_begin, k_after).  Axes:
+      ragx / ragy   (pixels of the last 8 x 16 tile as _rem_class, more than one tile along the axis) (dgrad: of the extended grid; wgrad: of
+                    the last 2 x 16 chunk, ragy = h % 2: an eligible shape has two rows at least)
+      grid          (N > 1, more than one tile of result channels) (wgrad: N > 1, more than one tile of 32 input / output channels)
+      chunks        class of KC16 (fwd: over C0, :110; dgrad: over Nout, :404 -- with one chunk every step changes phase)
+      ctail / ntail contracted channels % 16 != 0 (hzero, :262 :435) / result channels % BN != 0 (:278 :341 :451 :524)
+      clampy / clampx   "no" / "both" / "one" (_clamp_class; wgrad: clampx alone, a single row is not eligible)
+      epi (fwd)     the sorted subset of bias / addend / act (:342-364)
+    wgrad: s1 (S == 1: no sum launch, :432), s4 (S % 4, the bias reduce's tail :327), sum (per group of up2_wgrad_sum_kernel), cnt (per
+    split), short (fp32: the last split is shorter), db, kslice (k_begin > 0, channels behind the slice)"""
+    assert fmt in PHASE_FORMATS, fmt
+    if kind == "fwd":
+        p = phase_fwd_plan(N, h, w, C0, Nout, fmt)
+        assert p is not None, (kind, fmt, N, h, w, C0, C1, Nout)
+        key = ("fwd", p["bn"], fmt)
+        out = [("ragx", (_rem_class(w, PH_TW), p["tilesX"] > 1)), ("ragy", (_rem_class(h, PH_TH), p["tilesY"] > 1)),
+               ("chunks", _chunk_class(p["KC16"])), ("ctail", C0 % 16 != 0), ("ntail", Nout % p["bn"] != 0), ("clampy", _clamp_class(h, PH_TH)),
+               ("clampx", _clamp_class(w, PH_TW)), ("grid", (N > 1, p["tilesN"] > 1)), ("epi", tuple(sorted(epi)))]
+    elif kind == "dgrad":
+        p = phase_dgrad_plan(N, h, w, Nout, C0, fmt)
+        assert p is not None, (kind, fmt, N, h, w, C0, C1, Nout)
+        key = ("dgrad", p["bn"], fmt)
+        out = [("ragx", (_rem_class(w + 2, PH_TW), p["tilesX"] > 1)), ("ragy", (_rem_class(h + 2, PH_TH), p["tilesY"] > 1)),
+               ("chunks", _chunk_class(p["KC16"])), ("ctail", Nout % 16 != 0), ("ntail", C0 % p["bn"] != 0), ("clampy", _clamp_class(h, PH_TH)),
+               ("clampx", _clamp_class(w, PH_TW)), ("grid", (N > 1, p["tilesN"] > 1))]
+    else:
+        assert kind == "wgrad", kind
+        p = phase_wgrad_plan(N, h, w, C0, Nout)
+        assert p is not None, (kind, fmt, N, h, w, C0, C1, Nout)
+        key = ("wgrad", "fp32" if fmt == "f32" else "split", fmt)
+        S = p["S"]
+        counts = phase_wgrad_split_counts(p, fmt)
+        out = [("ragx", (_rem_class(w, PW_CW), p["cx"] > 1)), ("ragy", h % PW_CH), ("s1", S == 1), ("s4", S % 4), ("db", fmt != "f32"),
+               ("kslice", (kslice[0] > 0, kslice[1] > 0)), ("clampx", _clamp_class(w, PW_CW)), ("grid", (N > 1, p["citiles"] > 1, p["cotiles"] > 1))]
+        out += [("cnt", _cnt_class(c)) for c in counts]
+        if S > 1:
+            out += [("sum", g) for g in phase_wgrad_sum_groups(S)]
+        if fmt == "f32":
+            out.append(("short", counts[-1] < p["cps"]))
+    return frozenset(("phase", key) + o for o in out)
+
+
+EW["up2_fold"] = (lambda N, h, w, C: N * h * w * (C // 4), 4096)                           # conv_up2_phase.hip:584-586, :691
+
+
+def fold_regime(N, h, w, C, addend, ylow):
+    """up2_fold_bwd_kernel (conv_up2_phase.hip:543): the grid-stride loop as an "ew" regime, the optional operands, and how many extended
+    positions fold onto one pixel along each axis (1 / 2 inside and on a border, 3 where h == 1: :556-561)"""
+    return ew_regime("up2_fold", N, h, w, C) | frozenset([("fold", "operands", (bool(addend), bool(ylow))), ("fold", "ny", min(h, 2) == 1),
+                                                          ("fold", "nx", min(w, 2) == 1)])

@@ -13,12 +13,16 @@ bounds those tests use tight enough to see one dropped row?
    swept against fp_conv3x3_bf3_supported, fp_conv3x3_bf3_workspace and fp_conv_wgrad_bf3_workspace; TILE_WORKLOAD lists the 3x3 stride-1
    convolutions of one train step with their data and weight gradients (footprints 12x192x640, 4x512x640, 12x128x416; segmentor
    12x192x640), and every regime tuple of it must occur among the cases of tests/test_gpu_conv_tile_edges.py (tests/conv_tile_refs.py).
+6. The nearest-x2 phase kernels that run beside them (csrc/conv_up2_phase.hip, csrc/wgrad_up2_phase.hip): the launchers' tiling restated,
+   eligible / plan swept against fp_conv_up2_phase_wgrad_workspace, phase_workload lists the phase launches of the same four train steps,
+   and every regime tuple of it must occur among the cases of tests/test_gpu_conv_phase_edges.py (tests/conv_phase_refs.py).
 """
 import ctypes
 
 import pytest
 import torch
 
+from tests import conv_phase_refs as PR
 from tests import conv_tile_refs as TR
 from tests import launch_regimes as LR
 from tests import step_kernel_refs as SR
@@ -473,3 +477,186 @@ def test_tile_cases_reach_the_structural_edges():
             wg.setdefault(r[2], set()).add(r[3])
     assert wg["remy"] == {0, 1, 2, 3} and wg["remx"] == {0, 1, 2, 3} and wg["reduce"] == {"plain", "capped", "transposing"}
     assert wg["chunks"] == {"border", "both"} and wg["cnt"] == {0, 1} and wg["s4"] == {0, 1, 2, 3}
+
+
+# ---- 6. the nearest-x2 phase kernels: restatement against the library, workload against the cases of test_gpu_conv_phase_edges.py ----
+def _phase_switched():
+    import os
+    return sorted(k for k in os.environ if k.startswith("FP_PWGRAD_"))
+
+
+def test_phase_wgrad_plan_matches_library():
+    """fp_conv_up2_phase_wgrad_workspace against phase_wgrad_plan: (S 16 C0 Nout + S Nout) 4 bytes, or -1; the bytes give S"""
+    if _phase_switched():
+        pytest.skip("the launch rules are switched by %s: the restatement is that of the default build" % ", ".join(_phase_switched()))
+    lib = _lib()
+    hs = sorted(set([1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 16, 24, 26, 32, 48, 64, 96, 128, 256] + _sweep(21, 8, 1, 130)))
+    ws = sorted(set([1, 2, 12, 13, 14, 15, 16, 17, 18, 19, 20, 26, 29, 32, 33, 40, 48, 52, 80, 104, 160, 208, 320] + _sweep(22, 8, 1, 330)))
+    ns = [1, 2, 3, 4, 5, 7, 8, 12, 16, 64]
+    n = 0
+    for C0, Nout in [(32, 32), (32, 64), (64, 32), (64, 64), (96, 32), (128, 128), (256, 256), (1024, 768), (512, 1536), (20, 32), (32, 40), (0, 32), (32, 0), (-32, 32)]:      # (no channels: the query once divided by zero tiles)
+        for h in hs:
+            for w in ws:
+                for N in ns:
+                    p = LR.phase_wgrad_plan(N, h, w, C0, Nout)
+                    got = lib.fp_conv_up2_phase_wgrad_workspace(N, h, w, C0, Nout)
+                    assert got == (p["workspace"] if p else -1), (N, h, w, C0, Nout, got, p)
+                    if p:
+                        assert got % ((16 * C0 * Nout + Nout) * 4) == 0 and got // ((16 * C0 * Nout + Nout) * 4) == p["S"]
+                        assert sum(LR.phase_wgrad_split_counts(p, "f32")) == p["nchunks"] == sum(LR.phase_wgrad_split_counts(p, "exact"))
+                        assert min(LR.phase_wgrad_split_counts(p, "f32")) >= 1
+                    n += 1
+    assert n > 3000
+
+
+def test_phase_tile_plans():
+    """the forward and data-gradient launchers have no host query: the restatement is checked against its own definition at the shapes of a
+    train step (workgroups = tiles x phases; the data gradient tiles the extended grid and runs the four phases inside a workgroup)"""
+    p = LR.phase_fwd_plan(12, 48, 160, 64, 64)
+    assert (p["bn"], p["tilesY"], p["tilesX"], p["tilesN"], p["KC16"], p["nwg"]) == (64, 6, 10, 1, 4, 12 * 60 * 4)
+    p = LR.phase_fwd_plan(12, 96, 320, 64, 32, "pair")
+    assert (p["bn"], p["tilesN"], p["nwg"]) == (32, 1, 12 * 12 * 20 * 4)
+    p = LR.phase_dgrad_plan(12, 96, 320, 32, 64)
+    assert (p["bn"], p["tilesY"], p["tilesX"], p["KC16"], p["nsteps"], p["nwg"]) == (64, 13, 21, 2, 8, 12 * 13 * 21)
+    p = LR.phase_dgrad_plan(4, 8, 10, 256, 256)
+    assert (p["tilesY"], p["tilesX"], p["tilesN"], p["KC16"]) == (2, 1, 4, 16)
+    assert LR.phase_fwd_plan(1, 4, 4, 18, 16) is None and LR.phase_dgrad_plan(1, 4, 4, 18, 16) is None           # channels % 4
+    assert LR.phase_dgrad_plan(1, 4, 4, 16, 16, "f32") is None                                                       # that path is conv_igemm
+    assert LR.phase_fwd_plan(64, 512, 512, 16, 8, "exact") is None and LR.phase_fwd_plan(64, 512, 512, 16, 8, "f32")  # 2^29 elements: split formats only
+    assert LR.phase_ok(12, 40) and LR.phase_ok(8, 26) and not LR.phase_ok(6, 20) and not LR.phase_ok(4, 13)
+    assert LR.phase_ok(26, 42) and LR.phase_ok(6, 15) and not LR.phase_ok(18, 22) and not LR.phase_ok(10, 28)       # extended grids
+
+
+def phase_workload(N, H, W):
+    """the phase launches of one train step: (forward (N, h, w, C0, C1, Nout), data gradient (N, h, w, C0, Nout), fold (N, h, w, C0, addend,
+    ylow), weight gradient (N, h, w, C0, C1, Nout)) at LOW resolution h x w, by engine.py line.
+    Decoder block bi (engine.py:1091-1096): post1 over cat[up2(y2), skip] with C0 = C1 = Nout = cout at level 4 - bi; o41 over up2(x4) alone
+    with 64 -> 32 at H/2 x W/2 (:1105).  Forward :897-910 (the skip half first, then the phase kernel adds in place, bias + ELU); weight
+    gradient :1136-1179 (k_begin = 0 of a gradient of C0 + C1 channels, the bias gradient in the same pass); data gradient :1186-1196 on the
+    extended grid; fold :1503-1540 (o41: + the head's gradient, * ELU'; blocks: * ELU')"""
+    fwd, dg, fold, wg = [], [], [], []
+    for bi, cout in enumerate((256, 128, 64, 64)):
+        h, w = (H >> 5) << bi, (W >> 5) << bi
+        fwd.append((N, h, w, cout, cout, cout))
+        dg.append((N, h, w, cout, cout))
+        fold.append((N, h, w, cout, False, True))
+        wg.append((N, h, w, cout, cout, cout))
+    h0, w0 = H // 2, W // 2
+    return fwd + [(N, h0, w0, 64, 0, 32)], dg + [(N, h0, w0, 64, 32)], fold + [(N, h0, w0, 64, True, True)], wg + [(N, h0, w0, 64, 0, 32)]
+
+
+PHASE_WORKLOAD = {"footprints 12x192x640": phase_workload(12, 192, 640), "footprints 4x512x640": phase_workload(4, 512, 640),
+                  "footprints 12x128x416": phase_workload(12, 128, 416), "psp segmentor 12x192x640": phase_workload(12, 192, 640)}
+
+
+def phase_workload_regimes():
+    """({regime tuple: (workload name, launch) of its first occurrence}, [launches the gates turn down]) over both training formats.
+    Gates: forward engine.py:898 _phase_ok(h, w); data gradient :1190 _phase_ok(h + 2, w + 2); weight gradient :1142 eligible.  The fold
+    runs either way (:1512 :1540: a turned-down data gradient fills the same extended grid through conv_igemm)."""
+    need, down = {}, []
+    for name, (fwd, dg, fold, wg) in PHASE_WORKLOAD.items():
+        for fmt in TILE_FORMATS:
+            for N, h, w, C0, C1, Nout in fwd:
+                if not LR.phase_ok(h, w):
+                    down.append((name, "fwd", N, h, w))
+                    continue
+                epi = ("act", "bias") + (("addend",) if C1 else ())
+                for r in LR.phase_regime("fwd", fmt, N, h, w, C0, C1, Nout, epi=epi):
+                    need.setdefault(r, (name, ("fwd", fmt, N, h, w, C0, C1, Nout)))
+            for N, h, w, C0, Nout in dg:
+                if not LR.phase_ok(h + 2, w + 2):
+                    down.append((name, "dgrad", N, h, w))
+                    continue
+                for r in LR.phase_regime("dgrad", fmt, N, h, w, C0, 0, Nout):
+                    need.setdefault(r, (name, ("dgrad", fmt, N, h, w, C0, Nout)))
+            for N, h, w, C0, C1, Nout in wg:
+                if not LR.phase_wgrad_plan(N, h, w, C0, Nout):
+                    down.append((name, "wgrad", N, h, w))
+                    continue
+                for r in LR.phase_regime("wgrad", fmt, N, h, w, C0, 0, Nout, kslice=(0, C1)):
+                    need.setdefault(r, (name, ("wgrad", fmt, N, h, w, C0, C1, Nout)))
+        for N, h, w, C0, addend, ylow in fold:
+            for r in LR.fold_regime(N, h, w, C0, addend, ylow):
+                need.setdefault(r, (name, ("fold", N, h, w, C0, addend, ylow)))
+    return need, sorted(set(down))
+
+
+def phase_case_regimes():
+    have = set()
+    for kind, table in (("fwd", PR.PHASE_FWD), ("dgrad", PR.PHASE_DGRAD), ("wgrad", PR.PHASE_WGRAD), ("fold", PR.PHASE_FOLD)):
+        for c in table:
+            have |= PR.case_regimes(kind, c)
+    return have
+
+
+def test_phase_gates_turn_down_the_deepest_levels():
+    """which launches of a train step the gates keep away from the phase kernels.  The forward gate looks at h x w, the data gradient's at the
+    extended (h + 2) x (w + 2): 6 x 20 fails as a forward (62 % of 8 x 32 is under the 60 % rule's 6/10 of 256) and passes as 8 x 22;
+    16 x 20 passes as a forward and fails as 18 x 22; 8 x 26 passes and 10 x 28 fails; 4 x 13 fails and its 6 x 15 -- one partial tile --
+    passes.  The weight gradient's own rule (30 % padded 2 x 16 chunks) turns down 6 x 20 and 16 x 20 and takes 4 x 13."""
+    _, down = phase_workload_regimes()
+    assert down == [("footprints 12x128x416", "dgrad", 12, 8, 26), ("footprints 12x128x416", "fwd", 12, 4, 13),
+                    ("footprints 12x192x640", "fwd", 12, 6, 20), ("footprints 12x192x640", "wgrad", 12, 6, 20),
+                    ("footprints 4x512x640", "dgrad", 4, 16, 20), ("footprints 4x512x640", "wgrad", 4, 16, 20),
+                    ("psp segmentor 12x192x640", "fwd", 12, 6, 20), ("psp segmentor 12x192x640", "wgrad", 12, 6, 20)], down
+
+
+def test_phase_cases_are_launchable():
+    """an unsupported row in a table is an error, never a skip"""
+    for fmt, N, h, w, C0, C1, Nout in PR.PHASE_FWD:
+        assert fmt in LR.PHASE_FORMATS and LR.phase_fwd_plan(N, h, w, C0, Nout, fmt) and C1 % 4 == 0, (fmt, N, h, w, C0, C1, Nout)
+    for fmt, N, h, w, C0, C1, Nout in PR.PHASE_DGRAD:
+        assert fmt in ("exact", "pair") and C1 == 0 and C0 % 4 == 0 and LR.phase_dgrad_plan(N, h, w, Nout, C0, fmt), (fmt, N, h, w, C0, Nout)
+    for fmt, N, h, w, C0, ks, Nout in PR.PHASE_WGRAD:
+        assert fmt in LR.PHASE_FORMATS and len(ks) == 2 and LR.phase_wgrad_plan(N, h, w, C0, Nout), (fmt, N, h, w, C0, ks, Nout)
+    for kind, c in PR.PHASE_CANCEL:
+        assert c[0] in ("exact", "pair") and c[4] % 4 == 0 and c[6] % 4 == 0
+        assert LR.phase_fwd_plan(*c[1:5], c[6], c[0]) if kind == "fwd" else LR.phase_dgrad_plan(c[1], c[2], c[3], c[6], c[4], c[0])
+    for t in (PR.PHASE_FWD, PR.PHASE_DGRAD, PR.PHASE_WGRAD, PR.PHASE_FOLD):
+        assert len(set(t)) == len(t)
+
+
+def test_phase_workload_regimes_occur_in_cases():
+    have = phase_case_regimes()
+    need, _ = phase_workload_regimes()
+    missing = {r: w for r, w in need.items() if r not in have}
+    lines = ["%s: first run by %s %s" % (r, w[0], w[1]) for r, w in sorted(missing.items(), key=repr)]
+    assert not missing, "%d launch regimes of the train step that no GPU case of tests/conv_phase_refs.py runs:\n%s" % (len(lines), "\n".join(lines))
+
+
+def test_phase_cases_reach_the_structural_edges():
+    """edges the cases add on purpose, whether or not a train step runs them today -- per compiled kernel, not only over all of them"""
+    axes = {}
+    for r in phase_case_regimes():
+        if r[0] == "phase":
+            axes.setdefault(r[1], {}).setdefault(r[2], set()).add(r[3])
+    keys = [(k, bn, f) for k, fmts in (("fwd", LR.PHASE_FORMATS), ("dgrad", ("exact", "pair"))) for bn in (32, 64) for f in fmts]
+    for key in keys:
+        a = axes[key]
+        assert a["chunks"] == {1, 2, 3, "even", "odd"}, (key, a["chunks"])            # KC16 = 1: every step of the data gradient changes phase
+        many = {(r, True) for r in (0, 1, 2, 3)}                                     # every remainder behind a full tile, and a single partial tile
+        assert many <= a["ragx"] and many <= a["ragy"] and any(not m for _, m in a["ragx"]) and any(not m for _, m in a["ragy"]), (key, a["ragx"], a["ragy"])
+        assert a["grid"] == {(n, t) for n in (False, True) for t in (False, True) if key[1] == 64 or not t}, (key, a["grid"])
+        assert a["ctail"] == {True, False} and a["ntail"] == {True, False}, (key, a["ctail"], a["ntail"])
+        assert a["clampy"] == {"no", "both", "one"} and a["clampx"] == {"no", "both", "one"}, (key, a["clampy"], a["clampx"])       # h == 1, w == 1, h < 8
+        if key[0] == "fwd":
+            assert a["epi"] == set(PR.FWD_EPIS), (key, a["epi"])
+    for fmt in ("exact", "pair"):                                                     # h == w == 1: nine extended positions fold onto one pixel
+        assert any(c[0] == fmt and c[2] == c[3] == 1 for c in PR.PHASE_DGRAD) and any(c[0] == fmt and c[2] == c[3] == 1 for c in PR.PHASE_FWD)
+    for key in [("wgrad", "fp32", "f32"), ("wgrad", "split", "exact"), ("wgrad", "split", "pair")]:
+        a = axes[key]
+        assert {(r, True) for r in (0, 1, 2, 3)} <= a["ragx"] and a["ragy"] == {0, 1} and a["clampx"] == {"no", "both"}, (key, a)
+        assert {(True, False, False), (True, True, False), (True, False, True), (True, True, True), (False, True, True)} <= a["grid"], (key, a["grid"])
+        assert a["s1"] == {True, False} and a["s4"] == {0, 1, 2, 3}, (key, a["s1"], a["s4"])
+        assert a["kslice"] == {(False, False), (False, True), (True, False), (True, True)}, (key, a["kslice"])
+        assert {"even", "odd"} <= a["cnt"], (key, a["cnt"])
+        assert {(False, 1), (False, 2), (False, 3), (True, 0), (True, 1), (True, 2), (True, 3)} <= a["sum"], (key, a["sum"])
+        assert a["db"] == {key[2] != "f32"}
+    f32 = axes[("wgrad", "fp32", "f32")]
+    assert f32["short"] == {True, False} and {1, 2, "even", "odd"} <= f32["cnt"], (f32["short"], f32["cnt"])
+    fold = {}
+    for r in phase_case_regimes():
+        if r[0] == "fold":
+            fold.setdefault(r[1], set()).add(r[2])
+    assert fold["ny"] == {True, False} and fold["nx"] == {True, False} and fold["operands"] == {(True, True), (False, True)}
+    assert {("ew", "up2_fold", 1, True), ("ew", "up2_fold", 2, True), ("ew", "up2_fold", 2, False)} <= phase_case_regimes()
